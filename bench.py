@@ -8,12 +8,23 @@ reset the node snapshot (device-side copy) and run every scheduling cycle
 Inputs (cluster SoA + pod queue) are resident in HBM before the timed region.
 
   python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--mode p100|adapt]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line.  --full adds what takes
+runs of its own: the per-kernel table and the roofline of the dominant kernel
+("kernels", "roofline"), config 2's ADAPT line ("adapt") and the CPU baseline
+("cpu_baseline", "vs_cpu"); --no-adapt / --no-cpu drop one of them again.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64, at most 64 MB in all): the node snapshot's dynamic state
+after the step, the step's counters, and the placements (dump_outputs()).
 
 Workloads:
   config 2 (default)  N = 1: 5,000 nodes x 50,000 pods, default profile, P100;
-                      the same workload under ADAPT (the simulator's forced
-                      default, percentageOfNodesToScore 0) is timed beside it
-                      ("adapt" in the JSON line).
+                      with --full the same workload under ADAPT (the
+                      simulator's forced default, percentageOfNodesToScore 0)
+                      is timed beside it ("adapt" in the JSON line).
                       N > 1: node-sharded weak scaling, --nodes-per-gpu (5,000)
                       x N nodes, the same 50,000 pods; one process per GPU, per
                       batch an RCCL all-gather of candidates + all-reduce (max).
@@ -718,11 +729,20 @@ def main():
                     help="compile configs 1 / 3 with the Python encoder (ksim/encode.py) instead of the native one")
     ap.add_argument("--host-match", action="store_true",
                     help="config 3: match the count classes' selectors on the host instead of ksim_match_terms")
-    ap.add_argument("--no-adapt", action="store_true", help="skip the secondary ADAPT measurement (config 2)")
+    ap.add_argument("--no-adapt", action="store_true", help="skip the secondary ADAPT measurement (config 2, --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel table and roofline, config 2's "
+                         "ADAPT line, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample per thread count")
     ap.add_argument("--cpu-threads", default="sweep",
                     help='CPU baseline threads: "sweep" (16, 64, every logical CPU; best reported) or a comma list')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and args.mode == "fw":
+        ap.error("--dump-outputs: --mode fw has no timed steps to dump")
 
     # The JSON line goes to the original stdout; native libraries (RCCL's
     # version banner) that write to fd 1 land on stderr instead.
@@ -857,13 +877,138 @@ def main():
         # sharded: every rank ran the same cycles (count them once)
         cycles = int(c[1].item()) // (world if sharded else 1)
 
-    # Roofline of the evaluation kernel: per-kernel HIP events on an engine
-    # stream, over this rank's nodes (a sharded rank times its own shard).
+    ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, st, pods.n_pods, cfg, sharded, rank)
+
     geom = engine.batch_geometry()
     from ksim.profile import num_feasible_nodes_to_find
     geom["adapt_k"] = num_feasible_nodes_to_find(cluster.n_nodes, sp.percentage_of_nodes_to_score)
     if st.batches > 0 and st.perpod_cycles == 0:
         geom["tb_pods_per_batch"] = st.pods / st.batches   # the topology batches' mean size (config 3)
+    seeds = {1: "0x4B53494D0001", 2: "0x4B53494D0002", 3: "0x4B53494D0003", 4: "0x4B53494D0004", 5: "0x4B53494D0002/0005"}
+    result = {
+        "metric": "pod x node filter+score evals/sec",
+        "value": evals / elapsed,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": f"synthetic (SplitMix64 seed {seeds[cfg]})",
+        "config": {"workload": desc, "nodes": cluster.n_nodes, "pods": pods.n_pods, "mode": args.mode,
+                   "parallelism": (f"node-sharded over {world} GPUs (RCCL)" if sharded else
+                                   f"{world} independent replicas" if world > 1 else "single GPU")},
+        "pods_per_s": cycles / elapsed,
+        "batch_stats": {"batches": st.batches, "truncations": st.truncations,
+                        "perpod_cycles": st.perpod_cycles},
+        "batch_geometry": geom,
+    }
+    if args.full:
+        result.update(kernel_lines(args, engine, shard, profile, eng, cluster, pods, sp, cfg, sharded, rank, world,
+                                   local, geom, ms_per_step))
+    if HOST_COMPILE:
+        result["host_compile"] = HOST_COMPILE
+    if SWEEP.get("placements") is not None:
+        from ksim import sweep
+        pl = SWEEP["placements"]
+        result["sweep"] = {"vectors": int(pl.shape[0]), "pods": int(pl.shape[1]),
+                           "placements_gathered": "rank 0, [vectors][pods] int32, one all-gather per step (C4)",
+                           "scheduled_per_vector_mean": float((pl >= 0).sum(axis=1).mean()),
+                           "digest": sweep.placement_digest(pl)}
+    if args.full and cfg == 2 and world == 1 and args.mode == "p100" and not args.no_adapt:
+        # the simulator's forced default (percentageOfNodesToScore = 0) on the
+        # same cluster and pods, timed the same way: a secondary line item
+        asp = profile.SchedulerProfile(percentage_of_nodes_to_score=0)
+        aeng = engine.Engine(local)
+        aeng.set_profile(profile.compile_profile(asp))
+        aeng.set_cluster(cluster)
+        aeng.load_pods(pods)
+        aeng.schedule_loaded(0, pods.n_pods, want_chosen=False)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        aev = 0
+        for _ in range(args.steps):
+            aeng.reset_cluster()
+            _, ast = aeng.schedule_loaded(0, pods.n_pods, want_chosen=False)
+            aev += ast.evals
+        torch.cuda.synchronize()
+        adt = time.perf_counter() - t0
+        result["adapt"] = {"mode": "ADAPT (percentageOfNodesToScore 0, K = %d of %d nodes)" %
+                           (_k_adapt(cluster.n_nodes), cluster.n_nodes),
+                           "value": aev / adt, "unit": "evals/s", "pods_per_s": pods.n_pods * args.steps / adt,
+                           "ms_per_step": adt / args.steps * 1e3, "batches": ast.batches,
+                           "perpod_cycles": ast.perpod_cycles}
+        log(f"[rank 0] adapt: {aev / adt:.3e} evals/s")
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
+        log("[rank 0] cpu baseline ...")
+        result["cpu_baseline"] = cpu_baseline(cluster, pods, sp, args.cpu_seconds, cpu_threads_sweep(args.cpu_threads),
+                                              f"config-{cfg}")
+        result["vs_cpu"] = result["value"] / result["cpu_baseline"]["value"]
+    if rank == 0:
+        print(json.dumps(result), file=out, flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def dump_outputs(dirname, eng, st, n_pods, cfg, sharded, rank):
+    """--dump-outputs: what the last timed step left, as DIR/<name>.npy
+    (written by rank 0; every rank of a sharded run joins the placement pass).
+
+    stats.npy        the counters schedule_loaded returned for the step
+                     (pods, scheduled, unschedulable, evals, batches,
+                     truncations, perpod_cycles), float64;
+    node_<col>.npy   the node snapshot's dynamic columns after the step (read
+                     back from the device, unsharded single-engine configs);
+    next_start.npy   the scan's next start index after the step;
+    placements.npy   the node chosen for every pod (-1: unschedulable).  The
+                     timed step passes no placement buffer, so this is one
+                     more pass of the same step (snapshot reset, same loaded
+                     pods) with the buffer; config 5 keeps the placements its
+                     step gathered ([vectors][pods]).
+
+    Every value is an integer below 2^53, exact in float64.  An array that
+    would take the files past 64 MB is cut to a fixed seeded sample of its
+    elements (<name>_index.npy holds their flat positions)."""
+    import numpy as np
+    arrays = {"stats": np.array([getattr(st, f) for f in ("pods", "scheduled", "unschedulable", "evals", "batches",
+                                                           "truncations", "perpod_cycles")], np.float64)}
+    if cfg == 5:
+        arrays["placements"] = np.asarray(SWEEP["placements"])
+    else:
+        if not sharded:
+            for k, v in eng.node_state().items():
+                arrays[f"node_{k}"] = v
+            arrays["next_start"] = np.array([eng.next_start])
+        eng.reset_cluster()
+        chosen, _ = eng.schedule_loaded(0, n_pods)
+        arrays["placements"] = chosen
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    budget = 64 * 1000 * 1000 - 4096 * 2 * len(arrays)      # .npy headers stay inside the limit
+    for name in sorted(arrays, key=lambda k: arrays[k].size):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float64)
+        if a.nbytes > budget // 2:                           # sample: values + their positions
+            idx = np.sort(np.random.default_rng(0x4B53494D).choice(a.size, budget // 32, replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            budget -= idx.size * 8
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        budget -= a.nbytes
+    log(f"[rank 0] outputs of the last step written under {dirname}: {sorted(arrays)}")
+
+
+def kernel_lines(args, engine, shard, profile, eng, cluster, pods, sp, cfg, sharded, rank, world, local, geom,
+                 ms_per_step) -> dict:
+    """--full: the "kernels" table and the "roofline" of the dominant kernel,
+    from runs of their own after the timed steps."""
+    # Roofline of the evaluation kernel: per-kernel HIP events on an engine
+    # stream, over this rank's nodes (a sharded rank times its own shard).
     if sharded:
         base, cnt = shard.partition(cluster.n_nodes, world)[rank]
         keng = engine.Engine(local)
@@ -884,7 +1029,7 @@ def main():
     # the evaluation kernel's mean duration: HIP events around back-to-back
     # launches on the engine's stream (no event records between launches,
     # which add 2-4 us each in the per-kernel table above)
-    ktab = kernel_table(kt, kt_pods, pods.n_pods, elapsed / args.steps * 1e3, knodes, n_norm, geom, sharded,
+    ktab = kernel_table(kt, kt_pods, pods.n_pods, ms_per_step, knodes, n_norm, geom, sharded,
                         concurrent=cfg == 5)
     avg_ms, timing = ktab[dominant]["avg_ms"], ("per-kernel HIP events inside the run, reconciled with the "
                                                 "graph-replayed step (kernels table)")
@@ -936,73 +1081,9 @@ def main():
             if ve.get("valu_mix_per_launch"):
                 valu["mix_per_launch"] = ve["valu_mix_per_launch"]
 
-    seeds = {1: "0x4B53494D0001", 2: "0x4B53494D0002", 3: "0x4B53494D0003", 4: "0x4B53494D0004", 5: "0x4B53494D0002/0005"}
-    result = {
-        "metric": "pod x node filter+score evals/sec",
-        "value": evals / elapsed,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": f"synthetic (SplitMix64 seed {seeds[cfg]})",
-        "config": {"workload": desc, "nodes": cluster.n_nodes, "pods": pods.n_pods, "mode": args.mode,
-                   "parallelism": (f"node-sharded over {world} GPUs (RCCL)" if sharded else
-                                   f"{world} independent replicas" if world > 1 else "single GPU")},
-        "pods_per_s": cycles / elapsed,
-        "kernels": ktab,
-        "batch_stats": {"batches": st.batches, "truncations": st.truncations,
-                        "perpod_cycles": st.perpod_cycles},
-        "roofline": dict(roofline_entry(dominant, achieved, traffic, alg, avg_ms, timing, knodes, by_time, valu),
-                         live_avg_launch_ms=live_ms, live_timing=live_timing),
-        "batch_geometry": geom,
-    }
-    if HOST_COMPILE:
-        result["host_compile"] = HOST_COMPILE
-    if SWEEP.get("placements") is not None:
-        from ksim import sweep
-        pl = SWEEP["placements"]
-        result["sweep"] = {"vectors": int(pl.shape[0]), "pods": int(pl.shape[1]),
-                           "placements_gathered": "rank 0, [vectors][pods] int32, one all-gather per step (C4)",
-                           "scheduled_per_vector_mean": float((pl >= 0).sum(axis=1).mean()),
-                           "digest": sweep.placement_digest(pl)}
-    if cfg == 2 and world == 1 and args.mode == "p100" and not args.no_adapt:
-        # the simulator's forced default (percentageOfNodesToScore = 0) on the
-        # same cluster and pods, timed the same way: a secondary line item
-        asp = profile.SchedulerProfile(percentage_of_nodes_to_score=0)
-        aeng = engine.Engine(local)
-        aeng.set_profile(profile.compile_profile(asp))
-        aeng.set_cluster(cluster)
-        aeng.load_pods(pods)
-        aeng.schedule_loaded(0, pods.n_pods, want_chosen=False)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        aev = 0
-        for _ in range(args.steps):
-            aeng.reset_cluster()
-            _, ast = aeng.schedule_loaded(0, pods.n_pods, want_chosen=False)
-            aev += ast.evals
-        torch.cuda.synchronize()
-        adt = time.perf_counter() - t0
-        result["adapt"] = {"mode": "ADAPT (percentageOfNodesToScore 0, K = %d of %d nodes)" %
-                           (_k_adapt(cluster.n_nodes), cluster.n_nodes),
-                           "value": aev / adt, "unit": "evals/s", "pods_per_s": pods.n_pods * args.steps / adt,
-                           "ms_per_step": adt / args.steps * 1e3, "batches": ast.batches,
-                           "perpod_cycles": ast.perpod_cycles}
-        log(f"[rank 0] adapt: {aev / adt:.3e} evals/s")
-    if rank == 0 and world == 1 and not args.no_cpu:
-        log("[rank 0] cpu baseline ...")
-        result["cpu_baseline"] = cpu_baseline(cluster, pods, sp, args.cpu_seconds, cpu_threads_sweep(args.cpu_threads),
-                                              f"config-{cfg}")
-        result["vs_cpu"] = result["value"] / result["cpu_baseline"]["value"]
-    if rank == 0:
-        print(json.dumps(result), file=out, flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return {"kernels": ktab,
+            "roofline": dict(roofline_entry(dominant, achieved, traffic, alg, avg_ms, timing, knodes, by_time, valu),
+                             live_avg_launch_ms=live_ms, live_timing=live_timing)}
 
 
 if __name__ == "__main__":

@@ -13,6 +13,6 @@ for c in ${@:-2 3}; do
     4) args="--config 4 --steps 1 --warmup 1 --pods4 200000" ;;
     5) args="--config 5 --steps 1 --warmup 1 --sweep 64" ;;
   esac
-  timeout -k 10 400 python3 -u bench.py $args --cpu-seconds 5 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || exit $?
+  timeout -k 10 400 python3 -u bench.py --full $args --cpu-seconds 5 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || exit $?
   tail -c 400 "$OUT/bench_$c.json"; echo
 done

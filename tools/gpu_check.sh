@@ -9,7 +9,7 @@ step() { echo "== $*" >&2 ; "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step faile
 if [ -z "$NO_TESTS" ]; then
   step timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1
 fi
-step timeout -k 10 300 python -u bench.py ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err"
+step timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err"
 if [ -z "$NO_PROF" ]; then
   export TMPDIR=/tmp
   step timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu > "$OUT/prof.log" 2>&1

@@ -6,7 +6,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 OUT=$PWD/gpurun_out/${TAG:-r06ab}
 mkdir -p "$OUT"
-ARGS=${ARGS:---no-cpu}
+ARGS=${ARGS:---full --no-cpu}
 for r in $(seq 1 ${REPS:-2}); do
   timeout -k 10 300 python3 -u bench.py $ARGS > $OUT/cur_$r.json 2>$OUT/cur_$r.err || { tail -5 $OUT/cur_$r.err; exit 1; }
   for v in $VARIANTS; do

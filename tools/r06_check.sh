@@ -17,7 +17,7 @@ fi
   tail -1 "$OUT/smoke.txt"
 }
 [ -n "$NODEFAULT" ] || {
-  timeout -k 10 400 python3 -u bench.py ${BENCH_ARGS} > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit $?
+  timeout -k 10 400 python3 -u bench.py --full ${BENCH_ARGS} > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit $?
   tail -c 400 "$OUT/bench_default.json"; echo
 }
 for c in ${BENCH_CONFIGS}; do
@@ -31,7 +31,7 @@ for c in ${BENCH_CONFIGS}; do
     2a) args="--mode adapt --no-adapt --steps 5 --warmup 2" ;;
     fw) args="--mode fw" ;;
   esac
-  timeout -k 10 500 python3 -u bench.py $args > "$OUT/bench_config$c.json" 2> "$OUT/bench_config$c.err" || exit $?
+  timeout -k 10 500 python3 -u bench.py --full $args > "$OUT/bench_config$c.json" 2> "$OUT/bench_config$c.err" || exit $?
   python3 - "$OUT/bench_config$c.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -17,7 +17,7 @@ if [ -z "$NOTEST" ]; then
 fi
 line() {  # label bench-args
   local label=$1; shift
-  timeout -k 10 600 python3 -u bench.py "$@" > "$OUT/bench_$label.json" 2> "$OUT/bench_$label.err" || { tail -5 "$OUT/bench_$label.err"; exit 1; }
+  timeout -k 10 600 python3 -u bench.py --full "$@" > "$OUT/bench_$label.json" 2> "$OUT/bench_$label.err" || { tail -5 "$OUT/bench_$label.err"; exit 1; }
   python3 - "$OUT/bench_$label.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -30,7 +30,7 @@ PY
 prof() {  # label bench-args
   local label=$1; shift
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o "$label" --output-format csv -- \
-    python3 bench.py --no-cpu "$@" > "$OUT/prof_$label.json" 2> "$OUT/prof_$label.err" || { tail -5 "$OUT/prof_$label.err"; exit 1; }
+    python3 bench.py --full --no-cpu "$@" > "$OUT/prof_$label.json" 2> "$OUT/prof_$label.err" || { tail -5 "$OUT/prof_$label.err"; exit 1; }
   cp "$OUT/prof/${label}_kernel_stats.csv" "$OUT/kernel_stats_$label.csv" 2>/dev/null
   rm -f "$OUT/prof/${label}_kernel_trace.csv" "$OUT/prof/${label}_results.db"
 }
