@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define KSIM_ABI_VERSION 11
+#define KSIM_ABI_VERSION 12
 
 /* ---- limits ------------------------------------------------------------ */
 #define KSIM_KEY_NODE_MASK    ((1 << 18) - 1)  /* tie-break key: node field = mask - node (>= 1) */
@@ -647,6 +647,35 @@ int ksim_schedule_batch(ksim_handle* h, const ksim_pod_set* pods, int32_t* chose
  * sequence to 0 (device-side copy; used by sweeps and the bench). */
 int ksim_reset_cluster(ksim_handle* h);
 
+/* Packed policy sweep: the loaded pods [first, first+count) under each of
+ * n_profs profiles that differ from the handle's only in score_weight[], in
+ * one call on the handle's stream.  Row v of chosen ([n_profs][count]) and
+ * stats[v].{pods, scheduled, unschedulable, evals, batches, truncations} are
+ * what ksim_set_profile(&profs[v]); ksim_load_pods(the same set);
+ * ksim_reset_cluster; ksim_schedule_loaded(first, count) would return: every
+ * vector starts from the snapshot given at ksim_set_cluster with
+ * nextStartNodeIndex / pod sequence 0.  stats[v].device_ms is the device time
+ * of the WHOLE call, the same value in every row (the vectors share their
+ * launches); perpod_cycles is 0.  stats may be NULL.
+ * Up to max_lanes vectors run packed in each launch (0: the library's default,
+ * KSIM_SWEEP_DEFAULT_LANES; at most KSIM_SWEEP_MAX_LANES); a lane whose vector
+ * is done takes the next one.  The handle is left as it was: its node state,
+ * nextStartNodeIndex, profile, loaded queue and placements are not touched.
+ * KSIM_E_UNSUPPORTED (ksim_last_error names the condition) unless: the handle
+ * is unsharded, not replicated and keeps every node (percentageOfNodesToScore
+ * 100, no ADAPT window); the range is one run of the deferred-commit FAST
+ * batches under the handle's profile; every vector keeps every pod on that
+ * path and gives the FAST key one shape (default or generic) for all vectors;
+ * the cluster has at most 8192 nodes.  Callers fall back to the four calls
+ * above per vector.  KSIM_E_INVALID: n_profs < 1, a bad range, chosen NULL
+ * with count > 0, max_lanes outside [0, KSIM_SWEEP_MAX_LANES], or a profile
+ * ksim_set_profile would refuse. */
+#define KSIM_SWEEP_MAX_LANES 64
+#define KSIM_SWEEP_DEFAULT_LANES 64
+int ksim_sweep_loaded(ksim_handle* h, int32_t first, int32_t count, const ksim_profile* profs, int32_t n_profs,
+                      int32_t max_lanes, int32_t* chosen /* [n_profs][count] */,
+                      ksim_batch_stats* stats /* [n_profs], may be NULL */);
+
 /* ---- node sharding (multi-GPU) -------------------------------
  * A cluster of n_total nodes (nodeTree order) is split into contiguous shards.
  * A shard handle holds global positions [node_base, node_base + n_nodes) of
@@ -710,7 +739,9 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * overlay-indexed, node-stationary direct / indexed, KEEP default-shape /
  * generic, direct default-shape / generic, indexed default-shape / generic --
  * bits 16..21 k_batch_top -- static-class default-shape KEEP, static-class
- * default-shape, static-class, FAST default-shape, FAST, generic keys);
+ * default-shape, static-class, FAST default-shape, FAST, generic keys --
+ * bits 24..26 the packed sweep's k_sweep_top_commit -- default-shape, generic,
+ * flush);
  * out[26] topology batch pods committed on a zone variant (their batch moved
  * their DoNotSchedule domain verdicts; ksim_tbatch.hip TbVar), cumulative.
  * Returns the number of values written (<= n). */

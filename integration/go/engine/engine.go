@@ -28,7 +28,7 @@ import (
 )
 
 // ABIVersion is the header version this binding was written against.
-const ABIVersion = 11
+const ABIVersion = 12
 
 // Engine owns one device handle (one GPU, or one node shard of a cluster).
 // A handle is not reentrant: the framework's 16 Filter goroutines (nominated
@@ -246,6 +246,29 @@ func (e *Engine) ScheduleLoaded(first, count int, chosen []int32) (C.ksim_batch_
 		p = (*C.int32_t)(unsafe.Pointer(&chosen[0]))
 	}
 	err := e.locked(func() C.int { return C.ksim_schedule_loaded(e.h, C.int32_t(first), C.int32_t(count), p, &st) })
+	return st, err
+}
+
+// SweepLoaded runs the loaded pods [first, first+count) under every profile of
+// profs (the handle's own but for the score weights), up to maxLanes of them
+// per launch (0: the library's default), on the handle's one stream
+// (ksim_sweep_loaded).  chosen holds len(profs) rows of count placements; the
+// returned statistics are one per profile.  The handle's state, profile and
+// queue are left as they were.  An error wrapping KSIM_E_UNSUPPORTED means the
+// packed path does not apply: run the profiles one after another instead.
+func (e *Engine) SweepLoaded(first, count int, profs []C.ksim_profile, maxLanes int, chosen []int32) ([]C.ksim_batch_stats, error) {
+	if len(profs) == 0 || len(chosen) < len(profs)*count {
+		return nil, fmt.Errorf("SweepLoaded: %d profiles, %d placements for %d pods", len(profs), len(chosen), count)
+	}
+	st := make([]C.ksim_batch_stats, len(profs))
+	var p *C.int32_t
+	if len(chosen) > 0 {
+		p = (*C.int32_t)(unsafe.Pointer(&chosen[0]))
+	}
+	err := e.locked(func() C.int {
+		return C.ksim_sweep_loaded(e.h, C.int32_t(first), C.int32_t(count), &profs[0], C.int32_t(len(profs)),
+			C.int32_t(maxLanes), p, &st[0])
+	})
 	return st, err
 }
 

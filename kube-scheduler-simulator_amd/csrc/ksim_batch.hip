@@ -36,10 +36,9 @@
 
 namespace ksim {
 
-// KEEP forms: on node ranges of at most kKeepPerLane * threads nodes every lane
-// keeps all of its keys in registers (no insertion network; top_finish takes
-// them unsorted)
-constexpr int kKeepPerLane = 8;
+// KEEP forms (kKeepPerLane, ksim_internal.h): on node ranges of at most
+// kKeepPerLane * threads nodes every lane keeps all of its keys in registers
+// (no insertion network; top_finish takes them unsorted)
 
 // ---- k_batch_top: evaluation and the pod's top-T in one launch -------------------
 // One block per pod of the batch (kTopThreads threads, kTopWaves waves: two per
@@ -688,19 +687,19 @@ unsigned long long* cp_clock_buffer() { return nullptr; }
 // empty (chain_end = -1), so the next launch commits nothing for it.
 // R: each pod's list is R slice records (the node-stationary evaluation).
 // DEF (FAST pairs): the default profile's key shape compiled in.
-template <bool FAST, bool LAZY = false, bool STAB = false, int R = 1, bool DEF = false>
-__global__ __launch_bounds__(kBatchPods) void k_batch_chain_pairs(DevCluster c, DevPods P,
-                                                                  const ksim_profile* __restrict__ prof_p,
-                                                                  const BatchProg* __restrict__ bp_p,
-                                                                  const DevState* __restrict__ st,
-                                                                  const uint64_t* __restrict__ topk,
-                                                                  const int32_t* __restrict__ topk_cnt,
-                                                                  const int32_t* __restrict__ topk_complete,
-                                                                  uint64_t* __restrict__ gkey,
-                                                                  int32_t* __restrict__ chain_end,
-                                                                  uint64_t* __restrict__ pmax,
-                                                                  const int64_t* __restrict__ pnorm,
-                                                                  int32_t* __restrict__ pinv) {
+// The launch's body (k_batch_chain_pairs, and the packed sweep's
+// k_sweep_chain_pairs with a lane's buffers).
+template <bool FAST, bool LAZY, bool STAB, int R, bool DEF>
+__device__ __forceinline__ void batch_chain_pairs_body(const DevCluster& c, const DevPods& P,
+                                                       const ksim_profile* __restrict__ prof_p,
+                                                       const BatchProg* __restrict__ bp_p,
+                                                       const DevState* __restrict__ st,
+                                                       const uint64_t* __restrict__ topk,
+                                                       const int32_t* __restrict__ topk_cnt,
+                                                       const int32_t* __restrict__ topk_complete,
+                                                       uint64_t* __restrict__ gkey, int32_t* __restrict__ chain_end,
+                                                       uint64_t* __restrict__ pmax, const int64_t* __restrict__ pnorm,
+                                                       int32_t* __restrict__ pinv) {
   __shared__ ChainLds L;
   __shared__ uint64_t s_wmax[kBatchPods / 64];
   __shared__ int32_t s_winv[kBatchPods / 64];
@@ -737,6 +736,23 @@ __global__ __launch_bounds__(kBatchPods) void k_batch_chain_pairs(DevCluster c, 
 #ifdef KSIM_CP_CLOCKS
   if (dbgc && threadIdx.x == 0) atomicAdd(&dbgc[5], (unsigned long long)(__builtin_amdgcn_s_memrealtime() - t_in));
 #endif
+}
+
+template <bool FAST, bool LAZY = false, bool STAB = false, int R = 1, bool DEF = false>
+__global__ __launch_bounds__(kBatchPods) void k_batch_chain_pairs(DevCluster c, DevPods P,
+                                                                  const ksim_profile* __restrict__ prof_p,
+                                                                  const BatchProg* __restrict__ bp_p,
+                                                                  const DevState* __restrict__ st,
+                                                                  const uint64_t* __restrict__ topk,
+                                                                  const int32_t* __restrict__ topk_cnt,
+                                                                  const int32_t* __restrict__ topk_complete,
+                                                                  uint64_t* __restrict__ gkey,
+                                                                  int32_t* __restrict__ chain_end,
+                                                                  uint64_t* __restrict__ pmax,
+                                                                  const int64_t* __restrict__ pnorm,
+                                                                  int32_t* __restrict__ pinv) {
+  batch_chain_pairs_body<FAST, LAZY, STAB, R, DEF>(c, P, prof_p, bp_p, st, topk, topk_cnt, topk_complete, gkey,
+                                                   chain_end, pmax, pnorm, pinv);
 }
 
 __global__ __launch_bounds__(kBatchPods) void k_batch_commit(DevCluster c, DevPods P, DevState* __restrict__ st,
@@ -823,14 +839,16 @@ __device__ __forceinline__ int64_t uni64(int64_t x) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-template <bool FLUSH, bool DIRECT, bool DEF = false, bool KEEP = false, bool NS = false>
-__global__ __launch_bounds__(1024) void k_batch_top_commit(DevCluster c, DevPods P,
-                                                           const ksim_profile* __restrict__ prof_p,
-                                                           const BatchProg* __restrict__ bp_p, LazyStep L,
-                                                           uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,
-                                                           int32_t* __restrict__ topk_complete,
-                                                           int32_t* __restrict__ chosen_out,
-                                                           uint64_t* __restrict__ xsend) {
+// The launch's body (k_batch_top_commit, and the packed sweep's
+// k_sweep_top_commit with a lane's buffers).
+template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS>
+__device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const DevPods& P,
+                                                      const ksim_profile* __restrict__ prof_p,
+                                                      const BatchProg* __restrict__ bp_p, const LazyStep& L,
+                                                      uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,
+                                                      int32_t* __restrict__ topk_complete,
+                                                      int32_t* __restrict__ chosen_out,
+                                                      uint64_t* __restrict__ xsend) {
   constexpr int kThreads = 1024;
   static_assert(kThreads >= kBatchPods, "one thread per batch entry");
   // s_rq: batch i-1's pod requests, then each bound node's delta; entry
@@ -1191,10 +1209,58 @@ __global__ __launch_bounds__(1024) void k_batch_top_commit(DevCluster c, DevPods
   }
 }
 
+template <bool FLUSH, bool DIRECT, bool DEF = false, bool KEEP = false, bool NS = false>
+__global__ __launch_bounds__(1024) void k_batch_top_commit(DevCluster c, DevPods P,
+                                                           const ksim_profile* __restrict__ prof_p,
+                                                           const BatchProg* __restrict__ bp_p, LazyStep L,
+                                                           uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,
+                                                           int32_t* __restrict__ topk_complete,
+                                                           int32_t* __restrict__ chosen_out,
+                                                           uint64_t* __restrict__ xsend) {
+  batch_top_commit_body<FLUSH, DIRECT, DEF, KEEP, NS>(c, P, prof_p, bp_p, L, topk, topk_cnt, topk_complete, chosen_out,
+                                                      xsend);
+}
+
+// ---- packed policy sweep: a lane dimension on the two launches ---------------
+// gridDim.y lanes, each an independent run of the same pod queue over the same
+// static node columns under its own score weights (ksim_sweep_loaded).  A
+// block takes its lane's buffers from the table record tab[blockIdx.y]
+// (wave-uniform loads: the record stays in scalar registers); the host passes
+// the table of the batch's ring phase.  A lane without pods left (st cursor ==
+// end, its slots empty) commits and evaluates nothing.
+__device__ __forceinline__ DevCluster sweep_cols(DevCluster c, const DynCols& d) {
+  c.req_cpu = d.req_cpu;
+  c.req_mem = d.req_mem;
+  c.req_eph = d.req_eph;
+  c.nz_cpu = d.nz_cpu;
+  c.nz_mem = d.nz_mem;
+  c.num_pods = d.num_pods;
+  return c;
+}
+
+template <bool FLUSH, bool DEF>
+__global__ __launch_bounds__(1024) void k_sweep_top_commit(DevCluster c, DevPods P,
+                                                           const SweepLane* __restrict__ tab) {
+  const SweepLane& r = tab[blockIdx.y];
+  const DevCluster cl = sweep_cols(c, r.x_in);
+  batch_top_commit_body<FLUSH, true, DEF, !FLUSH, false>(cl, P, r.prof, r.bp, r.step, r.topk, r.topk_cnt,
+                                                         r.topk_complete, r.chosen, nullptr);
+}
+
+template <bool DEF>
+__global__ __launch_bounds__(kBatchPods) void k_sweep_chain_pairs(DevCluster c, DevPods P,
+                                                                  const SweepLane* __restrict__ tab) {
+  const SweepLane& r = tab[blockIdx.y];
+  const DevCluster cl = sweep_cols(c, r.step.w);
+  batch_chain_pairs_body<true, true, false, 1, DEF>(cl, P, r.prof, r.bp, r.step.st_out, r.topk, r.topk_cnt,
+                                                    r.topk_complete, r.gkey, r.step.e_self, r.pmax, r.pnorm, r.pinv);
+}
+
 // Which instantiations of the evaluation launches a process has launched (or
 // captured into a graph): bits 0..9 k_batch_top_commit (tc_variant), bits
-// 16..21 k_batch_top (launch_eval_top).  ksim_get_diag out[25]; the variant
-// tests assert every bit is reached.
+// 16..21 k_batch_top (launch_eval_top), bits 24..26 k_sweep_top_commit (DEF,
+// generic key shape, flush).  ksim_get_diag out[25]; the variant tests assert
+// every bit is reached.
 static std::atomic<uint64_t> g_variant_reach{0};
 uint64_t batch_variant_reach() { return g_variant_reach.load(std::memory_order_relaxed); }
 static void note_variant(int bit) { g_variant_reach.fetch_or(1ull << bit, std::memory_order_relaxed); }
@@ -1291,6 +1357,27 @@ void launch_lazy_chain_rep(const LazyBatch& z, int32_t world, hipStream_t stream
 }
 
 void launch_lazy_flush(const LazyBatch& z, hipStream_t stream) { launch_top_commit<true>(z, nullptr, stream); }
+
+// Packed sweep (k_sweep_*): one deferred-commit batch of every lane, and the
+// flush.  c: the static node columns (the dynamic ones come from the table).
+void launch_sweep_batch(const DevCluster& c, const DevPods& P, const SweepLane* tab, int32_t lanes, bool def,
+                        hipStream_t stream) {
+  const dim3 grid(kBatchPods, lanes);
+  note_variant(def ? 24 : 25);
+  if (def) {
+    k_sweep_top_commit<false, true><<<grid, 1024, 0, stream>>>(c, P, tab);
+    k_sweep_chain_pairs<true><<<grid, kBatchPods, 0, stream>>>(c, P, tab);
+  } else {
+    k_sweep_top_commit<false, false><<<grid, 1024, 0, stream>>>(c, P, tab);
+    k_sweep_chain_pairs<false><<<grid, kBatchPods, 0, stream>>>(c, P, tab);
+  }
+}
+
+void launch_sweep_flush(const DevCluster& c, const DevPods& P, const SweepLane* tab, int32_t lanes,
+                        hipStream_t stream) {
+  note_variant(26);
+  k_sweep_top_commit<true, false><<<dim3(kBatchPods, lanes), 1024, 0, stream>>>(c, P, tab);
+}
 
 // In-process shard group: M = max over the group's pmax arrays, written back to each.
 __global__ __launch_bounds__(kBatchPods) void k_group_max(GroupPtrs g) {

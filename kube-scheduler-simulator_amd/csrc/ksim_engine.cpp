@@ -294,6 +294,25 @@ struct ksim_handle {
   std::vector<DevBuf> ash_bufs;
   uint64_t *ash_send = nullptr, *ash_recv = nullptr, *ash_gmask = nullptr;
   int32_t ash_world = 0, ash_w = 0;
+  // packed policy sweep (ksim_sweep_loaded, run_sweep): the lanes' buffers as
+  // one slab sized by (dc.n, lanes), the lane table [kLazySlots][kSweepMaxLanes]
+  // (its address is all a sweep graph holds of them), the vectors' profile
+  // copies, the lanes' placement rows, one graph per (lanes, fast_def)
+  struct SweepLaneBufs {
+    DynCols x[2];
+    uint64_t *g, *m;                             // [kLazySlots][kBatchPods]
+    int32_t* e;                                  // [kLazySlots]
+    uint64_t* topk;
+    int32_t *topk_cnt, *topk_complete, *pinv;
+    int64_t* pnorm;
+  };
+  void* sweep_slab = nullptr;
+  int32_t sweep_n = -1, sweep_lanes = 0;
+  std::vector<SweepLaneBufs> sweep_lane;
+  DevState* sweep_st = nullptr;                  // [sweep_lanes][2]
+  SweepLane* sweep_tab = nullptr;
+  DevArena sweep_profs, sweep_rows;
+  std::map<std::pair<int32_t, bool>, hipGraphExec_t> sweep_graphs;
   int64_t graph_captures = 0;                  // graphs captured since ksim_create (ksim_get_diag)
   // node-sharded per-pod cycles (group leader): graphs of kGraphCycles cycles
   // per shape (topology, exchange lengths), valid while every handle of the
@@ -373,6 +392,9 @@ void drop_cycle_graphs(ksim_handle* h) {
 
 void drop_graphs(ksim_handle* h) {
   drop_cycle_graphs(h);
+  for (auto& kv : h->sweep_graphs)               // they hold the static columns and the queue
+    if (kv.second) (void)hipGraphExecDestroy(kv.second);
+  h->sweep_graphs.clear();
   if (h->graph_batch) (void)hipGraphExecDestroy(h->graph_batch);
   if (h->graph_batch_fast) (void)hipGraphExecDestroy(h->graph_batch_fast);
   if (h->graph_batch_stab) (void)hipGraphExecDestroy(h->graph_batch_stab);
@@ -1053,6 +1075,259 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
     i++;
   }
   return lazy_end(h, i - 1);
+}
+
+// ---- packed policy sweep (ksim_sweep_loaded; ksim_internal.h SweepLane) -------
+// The lanes' buffers: one slab, carved at 256-byte steps (k_reset_copy moves
+// 16-byte words), zero-filled; sized by (dc.n, lanes) and kept with the handle.
+int alloc_sweep(ksim_handle* h, int32_t lanes) {
+  if (!h->sweep_tab) {                              // its address is what the sweep graphs hold: allocated once
+    void* t = nullptr;
+    hipError_t e = hipMalloc(&t, sizeof(SweepLane) * kLazySlots * kSweepMaxLanes);
+    if (e != hipSuccess) return hip_fail(h, e, "hipMalloc");
+    h->sweep_tab = (SweepLane*)t;
+  }
+  if (h->sweep_n == h->dc.n && lanes <= h->sweep_lanes) return KSIM_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->sweep_slab) (void)hipFree(h->sweep_slab);
+  h->sweep_slab = nullptr;
+  h->sweep_n = -1;
+  h->sweep_lanes = 0;
+  h->sweep_lane.clear();
+  const size_t n = (size_t)h->dc.n;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  struct Off {
+    size_t col[2][6], g, m, e, topk, cnt, cmp, pnorm, pinv;
+  };
+  std::vector<Off> offs((size_t)lanes);
+  const size_t st_off = take(sizeof(DevState) * 2 * (size_t)lanes);
+  for (auto& o : offs) {
+    for (int p = 0; p < 2; p++)
+      for (int k = 0; k < 6; k++) o.col[p][k] = take(k < 5 ? 8 * n : 4 * n);
+    o.g = take(8 * (size_t)kLazySlots * kBatchPods);
+    o.m = take(8 * (size_t)kLazySlots * kBatchPods);
+    o.e = take(4 * (size_t)kLazySlots);
+    o.topk = take(8 * (size_t)kBatchPods * kTopT);
+    o.cnt = take(4 * (size_t)kBatchPods);
+    o.cmp = take(4 * (size_t)kBatchPods);
+    o.pnorm = take(8 * (size_t)kBatchPods * 4);
+    o.pinv = take(4 * (size_t)kBatchPods);
+  }
+  void* slab = nullptr;
+  hipError_t e = hipMalloc(&slab, off);
+  if (e != hipSuccess) return hip_fail(h, e, "hipMalloc");
+  if ((e = hipMemsetAsync(slab, 0, off, h->stream)) != hipSuccess) {
+    (void)hipFree(slab);
+    return hip_fail(h, e, "hipMemsetAsync");
+  }
+  char* base = (char*)slab;
+  h->sweep_slab = slab;
+  h->sweep_st = (DevState*)(base + st_off);
+  for (const auto& o : offs) {
+    ksim_handle::SweepLaneBufs b{};
+    for (int p = 0; p < 2; p++)
+      b.x[p] = DynCols{(int64_t*)(base + o.col[p][0]), (int64_t*)(base + o.col[p][1]), (int64_t*)(base + o.col[p][2]),
+                       (int64_t*)(base + o.col[p][3]), (int64_t*)(base + o.col[p][4]), (int32_t*)(base + o.col[p][5])};
+    b.g = (uint64_t*)(base + o.g);
+    b.m = (uint64_t*)(base + o.m);
+    b.e = (int32_t*)(base + o.e);
+    b.topk = (uint64_t*)(base + o.topk);
+    b.topk_cnt = (int32_t*)(base + o.cnt);
+    b.topk_complete = (int32_t*)(base + o.cmp);
+    b.pnorm = (int64_t*)(base + o.pnorm);
+    b.pinv = (int32_t*)(base + o.pinv);
+    h->sweep_lane.push_back(b);
+  }
+  h->sweep_n = h->dc.n;
+  h->sweep_lanes = lanes;
+  return KSIM_OK;
+}
+
+// A grow-only device buffer of at least `bytes` (the stream idle: nothing reads the old one).
+int sweep_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
+  if (a.cap >= bytes && a.p) return KSIM_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (a.p) (void)hipFree(a.p);
+  a.p = nullptr;
+  a.cap = 0;
+  const hipError_t e = hipMalloc(&a.p, bytes ? bytes : 16);
+  if (e != hipSuccess) {
+    a.p = nullptr;
+    return hip_fail(h, e, "hipMalloc");
+  }
+  a.cap = bytes ? bytes : 16;
+  return KSIM_OK;
+}
+
+// The table record of lane l at ring phase q (lazy_batch's arithmetic with
+// the lane's buffers).
+SweepLane sweep_record(const ksim_handle* h, int32_t l, int q, int32_t* row, const ksim_profile* prof,
+                       const BatchProg* bp) {
+  const ksim_handle::SweepLaneBufs& b = h->sweep_lane[(size_t)l];
+  const int p = q & 1, q1 = (q + 3) & 3, q2 = (q + 2) & 3;
+  DevState* st[2] = {h->sweep_st + 2 * (size_t)l, h->sweep_st + 2 * (size_t)l + 1};
+  SweepLane r{};
+  r.x_in = b.x[p ^ 1];
+  r.step.w = b.x[p];
+  r.step.st_in = st[p ^ 1];
+  r.step.st_out = st[p];
+  r.step.g1 = b.g + (size_t)q1 * kBatchPods;
+  r.step.m1 = b.m + (size_t)q1 * kBatchPods;
+  r.step.e1 = b.e + q1;
+  r.step.g2 = b.g + (size_t)q2 * kBatchPods;
+  r.step.e2 = b.e + q2;
+  r.step.e_self = b.e + q;
+  r.gkey = b.g + (size_t)q * kBatchPods;
+  r.pmax = b.m + (size_t)q * kBatchPods;
+  r.topk = b.topk;
+  r.topk_cnt = b.topk_cnt;
+  r.topk_complete = b.topk_complete;
+  r.pnorm = b.pnorm;
+  r.pinv = b.pinv;
+  r.chosen = row;
+  r.prof = prof;
+  r.bp = bp;
+  return r;
+}
+
+// Pods [a, b) under every vector, `lanes` vectors per launch (ksim_sweep_loaded
+// has checked the conditions and uploaded the vectors' d_profs / d_bps).  The
+// loop is run_lazy's with a lane dimension: every lane shares the batch index
+// i (the ring phase and the column set), stretches are as long as the slowest
+// live lane needs, each ends with a flush and one copy of the lanes' states.
+// A lane that reached its end there hands out its row and state and takes the
+// next pending vector: both column sets from the uploaded snapshot, both
+// states zero with the run bounds, every ring slot empty, which is a valid
+// start at any ring phase (lazy_begin).  A lane without a vector keeps cursor
+// == end == 0 and empty slots: its blocks commit and evaluate nothing.
+int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lanes, bool def,
+              const ksim_profile* d_profs, const BatchProg* d_bps, int32_t* chosen, ksim_batch_stats* stats) {
+  int rc;
+  if ((rc = alloc_sweep(h, lanes))) return rc;
+  const int32_t np = h->dp.n_pods, count = b - a;
+  if ((rc = sweep_reserve(h, h->sweep_rows, 4 * (size_t)lanes * (size_t)std::max(np, 1)))) return rc;
+  int32_t* rows = (int32_t*)h->sweep_rows.p;
+  LaunchArgs la = make_args(h, h->dp, nullptr);
+  const DevCluster c = la.c;
+  const DevPods P = h->dp;                          // no static-class table: FAST runs do not read it
+  SweepLane* const tab = h->sweep_tab;
+  std::vector<SweepLane> htab((size_t)kLazySlots * kSweepMaxLanes);
+  std::vector<int32_t> vec((size_t)lanes, -1), cur((size_t)lanes, 0);
+  std::vector<DevState> hst(2 * (size_t)lanes);
+  int32_t next_v = 0, live = 0;
+  DevState st0[2] = {}, idle[2] = {};               // a lane's two states: at the run's start, without a vector
+  st0[0].cursor = st0[1].cursor = a;
+  st0[0].end = st0[1].end = b;
+  auto arm = [&](int32_t l, int32_t v) -> int {     // v < 0: the lane idles
+    const ksim_handle::SweepLaneBufs& B = h->sweep_lane[(size_t)l];
+    HIPCHK(h, hipMemcpyAsync(h->sweep_st + 2 * (size_t)l, v >= 0 ? st0 : idle, 2 * sizeof(DevState),
+                             hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(B.e, 0xff, 4 * kLazySlots, h->stream));
+    if (v >= 0) {
+      const size_t n = (size_t)h->dc.n;
+      ResetList L;
+      bool ok = true;
+      for (int p = 0; p < 2; p++) {
+        ok = ok && L.add(B.x[p].req_cpu, h->init.req_cpu, 8 * n) && L.add(B.x[p].req_mem, h->init.req_mem, 8 * n) &&
+             L.add(B.x[p].req_eph, h->init.req_eph, 8 * n) && L.add(B.x[p].nz_cpu, h->init.nz_cpu, 8 * n) &&
+             L.add(B.x[p].nz_mem, h->init.nz_mem, 8 * n) && L.add(B.x[p].num_pods, h->init.num_pods, 4 * n);
+      }
+      if (!ok) return set_err(h, KSIM_E_DEVICE, "packed sweep: snapshot columns not aligned for the reset copy");
+      launch_reset_copy(L, h->stream);
+      HIPCHK(h, hipGetLastError());
+    }
+    for (int q = 0; q < kLazySlots; q++)
+      htab[(size_t)q * kSweepMaxLanes + l] =
+          sweep_record(h, l, q, rows + (size_t)l * np, d_profs + std::max(v, 0), d_bps + std::max(v, 0));
+    vec[(size_t)l] = v;
+    cur[(size_t)l] = a;
+    return KSIM_OK;
+  };
+  for (int32_t l = 0; l < lanes; l++) {
+    const int32_t v = next_v < n_profs ? next_v++ : -1;
+    if ((rc = arm(l, v))) return rc;
+    live += v >= 0;
+  }
+  // st0 / idle / htab are read by the copies above when they are enqueued
+  // (pageable memory: staged before hipMemcpyAsync returns)
+  HIPCHK(h, hipMemcpyAsync(tab, htab.data(), sizeof(SweepLane) * htab.size(), hipMemcpyHostToDevice, h->stream));
+  hipGraphExec_t& graph = h->sweep_graphs[{lanes, def}];
+  if (!graph && count >= kBatchPods * kGraphBatches) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipGraph_t g = nullptr;
+    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    for (int i = 0; i < kGraphBatches; i++)
+      launch_sweep_batch(c, P, tab + (size_t)(i & 3) * kSweepMaxLanes, lanes, def, h->stream);
+    hipError_t e = hipStreamEndCapture(h->stream, &g);
+    if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
+    e = hipGraphInstantiate(&graph, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) {
+      graph = nullptr;
+      return hip_fail(h, e, "hipGraphInstantiate");
+    }
+    h->graph_captures++;
+  }
+  auto phase_tab = [&](int64_t i) { return tab + (size_t)(i & 3) * kSweepMaxLanes; };
+  int64_t i = 0;
+  while (live > 0) {
+    int32_t nb = 0;                                 // batches the slowest live lane still needs at most
+    for (int32_t l = 0; l < lanes; l++)
+      if (vec[(size_t)l] >= 0) nb = std::max(nb, (b - cur[(size_t)l] + kBatchPods - 1) / kBatchPods);
+    const int32_t align = (int32_t)((kLazySlots - (i & 3)) & 3);
+    // one graph per stretch at the most: the lanes are out of step, so some
+    // lane nearly always has a long way to go, and a lane that ends inside a
+    // long stretch would idle until its end instead of taking the next vector
+    nb = std::min(nb, align + kGraphBatches);
+    if (graph && nb >= align + kGraphBatches) {
+      for (int32_t r = 0; r < align; r++, i++, nb--) launch_sweep_batch(c, P, phase_tab(i), lanes, def, h->stream);
+      for (int32_t r = 0; r < nb / kGraphBatches; r++, i += kGraphBatches) HIPCHK(h, hipGraphLaunch(graph, h->stream));
+    } else {
+      for (int32_t r = 0; r < nb; r++, i++) launch_sweep_batch(c, P, phase_tab(i), lanes, def, h->stream);
+    }
+    launch_sweep_flush(c, P, phase_tab(i), lanes, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hst.data(), h->sweep_st, sizeof(DevState) * hst.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    bool progress = false, retab = false;
+    for (int32_t l = 0; l < lanes; l++) {
+      const int32_t v = vec[(size_t)l];
+      if (v < 0) continue;
+      const DevState& st = hst[2 * (size_t)l + (size_t)(i & 1)];
+      progress = progress || st.cursor > cur[(size_t)l];
+      cur[(size_t)l] = st.cursor;
+      if (st.cursor < b) continue;
+      if (count)
+        HIPCHK(h, hipMemcpyAsync(chosen + (size_t)v * count, rows + (size_t)l * np + a, 4 * (size_t)count,
+                                 hipMemcpyDeviceToHost, h->stream));
+      if (stats) {
+        ksim_batch_stats& o = stats[v];
+        o.pods = count;
+        o.scheduled = st.scheduled;
+        o.unschedulable = st.unschedulable;
+        o.evals = st.evals;
+        o.device_ms = 0;
+        o.batches = st.batches;
+        o.truncations = st.truncations;
+        o.perpod_cycles = 0;
+      }
+      const int32_t nv = next_v < n_profs ? next_v++ : -1;
+      if ((rc = arm(l, nv))) return rc;              // stream order: after the row's copy
+      live -= nv < 0;
+      retab = true;
+    }
+    if (!progress) return set_err(h, KSIM_E_DEVICE, "packed sweep made no progress");
+    if (retab)
+      HIPCHK(h, hipMemcpyAsync(tab, htab.data(), sizeof(SweepLane) * htab.size(), hipMemcpyHostToDevice, h->stream));
+    i++;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return KSIM_OK;
 }
 
 // Run pods [a, b) on one path (all of them share the path).
@@ -1807,6 +2082,10 @@ void ksim_destroy(ksim_handle* h) {
   free_bufs(h->scratch_bufs);
   free_bufs(h->ash_bufs);
   free_bufs(h->lazy_bufs);
+  if (h->sweep_slab) (void)hipFree(h->sweep_slab);
+  if (h->sweep_tab) (void)hipFree(h->sweep_tab);
+  if (h->sweep_profs.p) (void)hipFree(h->sweep_profs.p);
+  if (h->sweep_rows.p) (void)hipFree(h->sweep_rows.p);
   free_bufs(h->stab_bufs);
   free_bufs(h->pod_bufs);
   if (h->pod1_arena.p) (void)hipFree(h->pod1_arena.p);
@@ -1834,10 +2113,8 @@ void ksim_destroy(ksim_handle* h) {
 
 const char* ksim_last_error(const ksim_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
-int ksim_set_profile(ksim_handle* h, const ksim_profile* p) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !p) return KSIM_E_INVALID;
-  h->stab_dirty = true;                     // DevPods::stab: the static filter list may change
+// What ksim_set_profile accepts (ksim_sweep_loaded checks every vector the same way).
+static int validate_profile(ksim_handle* h, const ksim_profile* p) {
   if (p->n_filter < 0 || p->n_filter > KSIM_MAX_FILTER || p->n_score < 0 || p->n_score > KSIM_MAX_SCORE)
     return set_err(h, KSIM_E_INVALID, "plugin count out of range");
   for (int i = 0; i < p->n_filter; i++) {
@@ -1872,7 +2149,11 @@ int ksim_set_profile(ksim_handle* h, const ksim_profile* p) {
       (p->preempt_min_pct == 0 && p->preempt_min_abs == 0))
     return set_err(h, KSIM_E_INVALID, "DefaultPreemptionArgs: minCandidateNodesPercentage in [0, 100], "
                                       "minCandidateNodesAbsolute >= 0, not both 0");
-  // the profile compiled for batchable pods (see BatchProg in ksim_device.h)
+  return KSIM_OK;
+}
+
+// The profile compiled for batchable pods (see BatchProg in ksim_device.h).
+static BatchProg compile_batch_prog(const ksim_profile* p) {
   BatchProg bp{};
   // the FAST / cpu-memory keys implement LeastAllocated; the other strategies
   // take the generic keys (fit_score)
@@ -1905,6 +2186,15 @@ int ksim_set_profile(ksim_handle* h, const ksim_profile* p) {
     if (p->score[k] == KSIM_PL_NODE_AFFINITY) bp.w_na += w;
   }
   plan_profile(*p, bp.rank_lo, bp.rank_hi, bp.slot, bp.slot_hi);
+  return bp;
+}
+
+int ksim_set_profile(ksim_handle* h, const ksim_profile* p) {
+  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
+  if (!h || !p) return KSIM_E_INVALID;
+  h->stab_dirty = true;                     // DevPods::stab: the static filter list may change
+  if (const int vrc = validate_profile(h, p)) return vrc;
+  const BatchProg bp = compile_batch_prog(p);
   HIPCHK(h, hipSetDevice(h->device));
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   // the batch graphs read the profile from d_prof / d_bp; only the ADAPT
@@ -3948,6 +4238,86 @@ int ksim_schedule_loaded(ksim_handle* h, int32_t first, int32_t count, int32_t* 
     stats->batches = st.batches;
     stats->truncations = st.truncations;
     stats->perpod_cycles = perpod;
+  }
+  return KSIM_OK;
+}
+
+int ksim_sweep_loaded(ksim_handle* h, int32_t first, int32_t count, const ksim_profile* profs, int32_t n_profs,
+                      int32_t max_lanes, int32_t* chosen, ksim_batch_stats* stats) {
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  if (!profs || n_profs < 1) return set_err(h, KSIM_E_INVALID, "sweep: no profiles");
+  if (!h->dp.pods && count > 0) return set_err(h, KSIM_E_INVALID, "no pods loaded");
+  if (first < 0 || count < 0 || first + count > h->dp.n_pods) return set_err(h, KSIM_E_INVALID, "range out of loaded pods");
+  if (!chosen && count > 0) return set_err(h, KSIM_E_INVALID, "sweep: chosen is null");
+  if (max_lanes < 0 || max_lanes > KSIM_SWEEP_MAX_LANES)
+    return set_err(h, KSIM_E_INVALID, "sweep: max_lanes outside [0, " + std::to_string(KSIM_SWEEP_MAX_LANES) + "]");
+  static_assert(KSIM_SWEEP_MAX_LANES == kSweepMaxLanes && KSIM_SWEEP_DEFAULT_LANES <= kSweepMaxLanes, "sweep lanes");
+  for (int32_t v = 0; v < n_profs; v++)
+    if ((rc = validate_profile(h, &profs[v]))) return rc;
+  // ---- the packed path's conditions -------------------------------------------
+  auto no = [&](const std::string& why) { return set_err(h, KSIM_E_UNSUPPORTED, "packed sweep: " + why); };
+  if (!lazy_enabled()) return no("this library runs the three-launch batches (A/B flavor)");
+  if (is_sharded(h) || h->replicated) return no("the handle is sharded or replicated");
+  if (adapt_mode(h)) return no("the profile scores a window of the nodes (ADAPT); percentageOfNodesToScore must keep every node");
+  if (h->dc.n > kKeepPerLane * 1024)
+    return no("the cluster has more than " + std::to_string(kKeepPerLane * 1024) + " nodes");
+  for (int32_t v = 0; v < n_profs; v++) {
+    ksim_profile q = profs[v];
+    std::memcpy(q.score_weight, h->prof.score_weight, sizeof(q.score_weight));
+    if (std::memcmp(&q, &h->prof, sizeof(q)) != 0)
+      return no("profile " + std::to_string(v) + " differs from the handle's in more than score_weight");
+  }
+  {
+    // one run of the deferred-commit FAST batches under the handle's profile
+    int32_t runs = 0;
+    bool one = true;
+    (void)for_each_run(h, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
+      runs++;
+      LaunchArgs la{};
+      if (batch && !topo) pick_keys(h, a, b, la);
+      one = one && batch && !topo && la.fast && !la.stab && lazy_ok(h, a, b, la.fast, la.stab);
+      return KSIM_OK;
+    });
+    if (runs > 1 || !one) return no("the range is not one run of the deferred-commit FAST batches");
+  }
+  std::vector<BatchProg> bps((size_t)n_profs);
+  for (int32_t v = 0; v < n_profs; v++) {
+    bps[(size_t)v] = compile_batch_prog(&profs[v]);
+    const BatchProg& bp = bps[(size_t)v];
+    // pod_batchable under vector v: the run's pods are class 1 under the
+    // handle's profile (run_fast), so no normalized score of theirs varies
+    // over nodes (a property of the plugin lists and the pods, which the
+    // vectors share), and the class reads the weights in one test only
+    if ((int64_t)kMaxNodeScore * (bp.w_fit + bp.w_ba) >= kKeyTotalLimit)
+      return no("profile " + std::to_string(v) + ": totals past the batch key's range (its pods take the per-pod path)");
+    if (fast_def(bp) != fast_def(bps[0])) return no("the vectors give the FAST key different shapes");
+  }
+  if (count == 0) {
+    if (stats) std::memset(stats, 0, sizeof(ksim_batch_stats) * (size_t)n_profs);
+    return KSIM_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  const int32_t lanes = std::min(max_lanes ? max_lanes : KSIM_SWEEP_DEFAULT_LANES, n_profs);
+  // the vectors' device copies: [n_profs] ksim_profile, then [n_profs] BatchProg
+  const size_t pbytes = (sizeof(ksim_profile) * (size_t)n_profs + 255) & ~(size_t)255;
+  if ((rc = sweep_reserve(h, h->sweep_profs, pbytes + sizeof(BatchProg) * (size_t)n_profs))) return rc;
+  ksim_profile* d_profs = (ksim_profile*)h->sweep_profs.p;
+  BatchProg* d_bps = (BatchProg*)((char*)h->sweep_profs.p + pbytes);
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_profs, profs, sizeof(ksim_profile) * (size_t)n_profs, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_bps, bps.data(), sizeof(BatchProg) * (size_t)n_profs, hipMemcpyHostToDevice, h->stream));
+  if ((rc = run_sweep(h, first, first + count, n_profs, lanes, fast_def(bps[0]), d_profs, d_bps, chosen, stats))) {
+    (void)hipStreamSynchronize(h->stream);         // nothing in flight reads the caller's or this frame's memory
+    return rc;
+  }
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipEventSynchronize(h->ev1));
+  HIPCHK(h, hipGetLastError());
+  if (stats) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    for (int32_t v = 0; v < n_profs; v++) stats[v].device_ms = ms;
   }
   return KSIM_OK;
 }

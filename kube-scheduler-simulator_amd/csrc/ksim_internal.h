@@ -41,6 +41,7 @@ constexpr int kMaxListRecords = 4;            // list records per pod (ksim_batc
 static_assert(kBatchPods % 64 == 0 && kBatchPods <= 1024 && kTopT <= 64, "batch geometry");
 constexpr int kTopThreads = 1024;  // threads per pod of the batch top
 constexpr int kTileCand = 4;       // best keys each lane of the batch top keeps per pod
+constexpr int kKeepPerLane = 8;    // KEEP evaluation forms: keys a lane holds in registers (ksim_batch.hip)
 constexpr int kXRec = kTopT + 1;   // sharded exchange record per pod: T keys + (count | complete << 32)
 #ifndef KSIM_MAX_SHARDS
 #define KSIM_MAX_SHARDS 8
@@ -159,6 +160,29 @@ struct LazyBatch {
   int32_t* abroken;
   int32_t* awin;
 };
+// Packed policy sweep (ksim_sweep_loaded; ksim_batch.hip k_sweep_*): the two
+// launches of a deferred-commit batch with gridDim.y lanes, each lane a run of
+// its own (its two dynamic-column sets, states, ring, lists, placements row)
+// under its own profile copy, over the shared static columns and pod queue.
+// One record per (batch index & 3, lane): what LazyBatch holds for the batch.
+constexpr int kSweepMaxLanes = 64;
+struct SweepLane {
+  DynCols x_in;                                    // X[p ^ 1]
+  LazyStep step;                                   // step.w: X[p]; st_out: st[p]; e_self: batch i's slot
+  uint64_t* gkey;                                  // batch i's slot
+  uint64_t* pmax;
+  uint64_t* topk;
+  int32_t* topk_cnt;
+  int32_t* topk_complete;
+  int64_t* pnorm;
+  int32_t* pinv;
+  int32_t* chosen;                                 // the lane's placements row, by loaded pod index
+  const ksim_profile* prof;                        // the lane's vector
+  const BatchProg* bp;
+};
+void launch_sweep_batch(const DevCluster& c, const DevPods& P, const SweepLane* tab, int32_t lanes, bool def,
+                        hipStream_t stream);
+void launch_sweep_flush(const DevCluster& c, const DevPods& P, const SweepLane* tab, int32_t lanes, hipStream_t stream);
 constexpr int kKernelsPerLazy = 2;
 extern const char* const kLazyKernelNames[kKernelsPerLazy];
 // ADAPT (ksim_adapt.hip): k_adapt_mask_commit (commit of i-1, the S_i bitmaps

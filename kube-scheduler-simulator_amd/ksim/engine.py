@@ -25,7 +25,7 @@ EXPORTS = [
     "ksim_abi_version", "ksim_abi_sizeof", "ksim_create", "ksim_destroy", "ksim_last_error",
     "ksim_set_profile", "ksim_set_cluster", "ksim_get_node_state", "ksim_get_class_count", "ksim_get_nb_alloc", "ksim_get_next_start",
     "ksim_set_next_start", "ksim_set_pod_seq", "ksim_eval_pod", "ksim_assume", "ksim_forget",
-    "ksim_load_pods", "ksim_schedule_loaded", "ksim_schedule_batch", "ksim_reset_cluster",
+    "ksim_load_pods", "ksim_schedule_loaded", "ksim_schedule_batch", "ksim_reset_cluster", "ksim_sweep_loaded",
     "ksim_time_kernels", "ksim_kernel_name", "ksim_time_eval", "ksim_get_diag", "ksim_batch_geometry",
     "ksim_set_shard", "ksim_comm_unique_id", "ksim_comm_init", "ksim_group_schedule_loaded",
     "ksim_emit_cycle_json", "ksim_eval_pod_filter", "ksim_eval_pod_finish",
@@ -117,6 +117,7 @@ def _load(path):
     L.ksim_load_pods.argtypes = [vp, vp]
     L.ksim_schedule_loaded.argtypes = [vp, i32, i32, vp, vp]
     L.ksim_schedule_batch.argtypes = [vp, vp, vp, vp]
+    L.ksim_sweep_loaded.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp]
     L.ksim_reset_cluster.argtypes = [vp]
     L.ksim_time_kernels.argtypes = [vp, i32, i32, vp, vp, i32]
     L.ksim_kernel_name.argtypes = [i32]
@@ -233,6 +234,7 @@ class Engine:
     def set_profile(self, prof: abi.Profile):
         self._chk(self.L.ksim_set_profile(self.h, ctypes.byref(prof)))
         self.n_score = prof.n_score
+        self._profile = prof
 
     def set_cluster(self, cluster):
         nt, vo = cluster.node_table(), cluster.vocab()
@@ -446,6 +448,29 @@ class Engine:
     def schedule_batch(self, pods):
         self.load_pods(pods)
         return self.schedule_loaded(0, pods.n_pods)
+
+    def sweep_loaded(self, profiles, first: int = 0, count: Optional[int] = None, max_lanes: int = 0):
+        """Packed policy sweep (ksim_sweep_loaded): the loaded pods [first,
+        first + count) under every profile of ``profiles`` (the engine's own
+        but for the score weights), up to ``max_lanes`` of them per launch
+        (0: the library's default).  Returns (chosen [V][count] int32, [V]
+        BatchStats); row v is what set_profile(profiles[v]) / load_pods /
+        reset_cluster / schedule_loaded(first, count) returns.  The engine's
+        state, profile and queue are left as they were.  KsimError with
+        E_UNSUPPORTED when the packed path does not apply (sweep.run_sweep
+        falls back to the serial loop)."""
+        profiles = list(profiles)
+        n_loaded = self._keep[0].n_pods if self._keep else 0
+        if count is None:
+            count = n_loaded - first
+        V = len(profiles)
+        arr = (abi.Profile * max(V, 1))(*profiles)
+        # rows for a refused call are never read: the shape only has to be legal
+        chosen = np.zeros((V, max(count, 0)), np.int32)
+        stats = (abi.BatchStats * max(V, 1))()
+        self._chk(self.L.ksim_sweep_loaded(self.h, first, count, arr, V, max_lanes,
+                                           chosen.ctypes.data_as(ctypes.c_void_p), stats))
+        return chosen, [stats[v] for v in range(V)]
 
     def node_state(self) -> dict:
         n = self.n_nodes

@@ -59,6 +59,44 @@ def gather_placements(local: np.ndarray, rank: int, world: int, n_vectors: int, 
     return out
 
 
+def run_sweep(engine, pods, profiles, max_lanes: int = 0):
+    """One queue under many weight vectors on one engine: ``(placements
+    [V][pods] int32, [V] BatchStats, packed)``.  The vectors run packed into
+    shared launches (Engine.sweep_loaded) when the engine can; where it
+    answers E_UNSUPPORTED (and only then) they run one after another, as
+    set_profile / load_pods / reset_cluster / schedule_loaded per vector, after
+    which the engine's own profile and the queue are put back and the cluster
+    is reset.  ``packed`` says which path ran; the matrix is the same either
+    way.  The engine must hold its profile and cluster already."""
+    from . import abi
+    from .engine import KsimError
+    profiles = list(profiles)
+    engine.load_pods(pods)
+    try:
+        chosen, stats = engine.sweep_loaded(profiles, 0, pods.n_pods, max_lanes)
+        return chosen, stats, True
+    except KsimError as e:
+        if e.code != abi.E_UNSUPPORTED:
+            raise
+    own = getattr(engine, "_profile", None)
+    if own is None:
+        raise RuntimeError("run_sweep: the engine's profile is unknown (set it through Engine.set_profile)")
+    rows, stats = [], []
+    try:
+        for pr in profiles:
+            engine.set_profile(pr)
+            engine.load_pods(pods)
+            engine.reset_cluster()
+            chosen, st = engine.schedule_loaded(0, pods.n_pods)
+            rows.append(chosen)
+            stats.append(st)
+    finally:
+        engine.set_profile(own)
+        engine.load_pods(pods)
+        engine.reset_cluster()
+    return (np.stack(rows) if rows else np.zeros((0, pods.n_pods), np.int32)), stats, False
+
+
 def placement_digest(placements: np.ndarray) -> str:
     """A short digest of a placement matrix (reported by bench.py)."""
     import hashlib
