@@ -845,7 +845,9 @@ typedef struct ksim_match_problem {
 
 /* match_bits: [n_sigs][ceil(n_matchers / 32)] (bit m of row s: signature s
  * matches matcher m); counts (may be NULL when n_classes == 0):
- * [n_classes][n_nodes].  Needs no cluster or profile on the handle. */
+ * [n_classes][n_nodes].  The padding bits above n_matchers in the last word
+ * of every row are written as 0, so a caller may read whole words.  Needs no
+ * cluster or profile on the handle. */
 int ksim_match_terms(ksim_handle* h, const ksim_match_problem* mp, uint32_t* match_bits, int32_t* counts);
 
 /* ---- result emission ------------------------------------- */
