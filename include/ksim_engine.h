@@ -776,14 +776,23 @@ typedef struct ksim_preempt_out {
 /* Replace the bound-pod table (copied; the engine orders it per node by
  * importance: priority desc, start time asc). */
 int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b);
+/* The host-port holdings of the bound pods of the last ksim_set_bound_pods
+ * (which drops any earlier ones), as a CSR over its rows in the caller's row
+ * order: adds[off[i] .. off[i + 1]) are row i's count-class contributions
+ * (what a queue pod carries as add_first / add_count), off has n + 1 entries.
+ * Only the classes a preemptor's KSIM_USE_NODE_PORT uses name are read; others
+ * may be present.  Copied.  KSIM_E_INVALID: no table set, offsets not
+ * monotone, a class outside [0, n_classes).  Needed only before a dry run for
+ * a pod with KSIM_USE_NODE_PORT uses under a profile that filters on NodePorts. */
+int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds);
 /* DefaultPreemption's PostFilter for an unschedulable pod of `priority`
  * (default_preemption.go / preemption.go, v1.26) on the current snapshot,
  * without changing it.  It replaces the original plugin's PostFilter that the
  * wrapper calls and records (scheduler/plugin/wrappedplugin.go:518-544,
  * Store.AddPostFilterResult store.go:437):
  *   potential nodes  the nodes whose filter status is Unschedulable, i.e. the
- *                    ones that failed NodeResourcesFit (the plugins before it
- *                    return UnschedulableAndUnresolvable);
+ *                    ones that failed NodeResourcesFit or NodePorts (the other
+ *                    plugins ahead of them return UnschedulableAndUnresolvable);
  *   dry run          SelectVictimsOnNode on each, in nodeTree order from
  *                    offset 0 (upstream draws a random offset), keeping the
  *                    first numCandidates = max(minCandidateNodesPercentage %
@@ -793,7 +802,21 @@ int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b);
  *                    priority, lowest sum of (priority + 2^31), fewest
  *                    victims, latest earliest start among the highest-
  *                    priority victims, then the first candidate (no PDBs).
- * The pod must carry no topology / port / image uses (KSIM_E_UNSUPPORTED). */
+ * The dry run re-runs NodeResourcesFit and NodePorts on each potential node.
+ * The pod's uses, by kind:
+ *   PTS_SOFT, IPA_SCORE, IPA_SCORE_HARD, IMAGE   read by no Filter: ignored;
+ *   NODE_PORT   a node holding a pod of the port class fails NodePorts
+ *               (Unschedulable), is a potential node, and evicting the holders
+ *               frees the port: the dry run keeps the node's count of each
+ *               port class through remove and reprieve, from the bound pods'
+ *               contributions (ksim_set_bound_pod_adds; KSIM_E_INVALID without
+ *               them) and, on a grouped node, the nominated pods' own adds.
+ *               Ignored when the profile's filter list has no NodePorts;
+ *   PTS_HARD, IPA_AFFINITY, IPA_ANTI, IPA_EXISTING_ANTI   their Filter reads a
+ *               domain beyond the node: KSIM_E_UNSUPPORTED (the message names
+ *               the kind).
+ * Also KSIM_E_UNSUPPORTED: shard handles, NetworkBandwidth in the filter list,
+ * KSIM_POD_NODE_NAMES pods. */
 int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                  ksim_preempt_out* out);
 /* ksim_preempt with the PodNominator's pods (replaces the same PostFilter;

@@ -498,6 +498,7 @@ type NativeEncoder struct {
 	boundRows []*v1.Pod          // the bound-pod table rows (DefaultPreemption)
 	boundBufs func()
 	tableOld  bool
+	addsAt    int32 // count classes when the rows' adds were last sent (boundAdds)
 
 	evMu   sync.Mutex
 	events []event
@@ -1047,6 +1048,10 @@ func (n *NativeEncoder) BoundTable(e *Engine) error {
 	n.mu.Lock()
 	defer n.mu.Unlock()
 	if !n.tableOld {
+		// the rows stand; their adds follow the port classes the cycle's pod registered
+		if int32(n.info().n_classes) != n.addsAt {
+			return n.boundAdds(e)
+		}
 		return nil
 	}
 	if n.boundBufs != nil {
@@ -1104,6 +1109,43 @@ func (n *NativeEncoder) BoundTable(e *Engine) error {
 		return err
 	}
 	n.tableOld = false
+	return n.boundAdds(e)
+}
+
+// boundAdds sends the table rows' count-class contributions
+// (ksim_set_bound_pod_adds; ksim/preemption.py bound_table with a
+// TopologyIndex): each row compiled as a queue pod, whose adds are what its
+// bind put on its node, port_adds among them.  The engine reads the port
+// classes only.  The cycle's own set is a copy (Pod), so this compile does not
+// disturb it.  The adds cover the classes registered so far; a cycle whose pod
+// registers a new port class sends them again (addsAt).
+func (n *NativeEncoder) boundAdds(e *Engine) error {
+	off := make([]int32, len(n.boundRows)+1)
+	adds := make([]C.ksim_class_add, 0, len(n.boundRows))
+	if len(n.boundRows) > 0 {
+		if err := n.encodeQueue(n.boundRows); err != nil {
+			return err
+		}
+		ps := n.encodedSet()
+		pods := unsafe.Slice(ps.pods, int(ps.n_pods))
+		var all []C.ksim_class_add
+		if ps.n_adds > 0 {
+			all = unsafe.Slice(ps.adds, int(ps.n_adds))
+		}
+		for i := range n.boundRows {
+			f, c := int(pods[i].add_first), int(pods[i].add_count)
+			adds = append(adds, all[f:f+c]...)
+			off[i+1] = int32(len(adds))
+		}
+	}
+	var ap *C.ksim_class_add
+	if len(adds) > 0 {
+		ap = &adds[0]
+	}
+	if err := e.SetBoundPodAdds(off, ap); err != nil {
+		return err
+	}
+	n.addsAt = int32(n.info().n_classes)
 	return nil
 }
 

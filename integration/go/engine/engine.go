@@ -187,6 +187,15 @@ func (e *Engine) SetBoundPods(b *C.ksim_bound_pods) error {
 	return e.locked(func() C.int { return C.ksim_set_bound_pods(e.h, b) })
 }
 
+// SetBoundPodAdds: the count-class contributions of the last SetBoundPods'
+// rows (CSR: off has one entry per row plus one), the host-port holdings the
+// dry run of a pod with host ports reads.  Copied by the engine.
+func (e *Engine) SetBoundPodAdds(off []int32, adds *C.ksim_class_add) error {
+	return e.locked(func() C.int {
+		return C.ksim_set_bound_pod_adds(e.h, (*C.int32_t)(unsafe.Pointer(&off[0])), adds)
+	})
+}
+
 func (e *Engine) Preempt(ps *C.ksim_pod_set, idx int, priority int32, out *C.ksim_preempt_out) error {
 	return e.locked(func() C.int { return C.ksim_preempt(e.h, ps, C.int32_t(idx), C.int32_t(priority), out) })
 }

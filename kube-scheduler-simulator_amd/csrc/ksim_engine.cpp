@@ -222,6 +222,7 @@ struct ksim_handle {
   // DefaultPreemption: bound pods per node in importance order
   std::vector<DevBuf> pre_bufs;
   std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
+  std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
   DevPreempt pre{};
   std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
   int32_t pre_n = 0;
@@ -2097,6 +2098,7 @@ void ksim_destroy(ksim_handle* h) {
   if (h->pout) (void)hipHostFree(h->pout);
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_nom_bufs);
+  free_bufs(h->pre_add_bufs);
   if (h->d_chosen) (void)hipFree(h->d_chosen);
   if (h->st) (void)hipFree(h->st);
   if (h->d_prof) (void)hipFree(h->d_prof);
@@ -2290,6 +2292,7 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   // extender round trip do not carry over
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_nom_bufs);
+  free_bufs(h->pre_add_bufs);
   h->pre = DevPreempt{};
   h->pre_index.clear();
   h->pre_n = 0;
@@ -4743,6 +4746,7 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   free_bufs(h->pre_bufs);
+  free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
   DevPreempt d{};
   void* p = nullptr;
   if ((rc = upload(h, h->pre_bufs, off.data(), 4 * off.size(), &p))) return rc;
@@ -4767,6 +4771,40 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   h->pre = d;
   h->pre_index = ix;
   h->pre_n = n;
+  return KSIM_OK;
+}
+
+extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: ksim_set_bound_pods first");
+  const int32_t n = h->pre_n;
+  if (!off || off[0] < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: bad offsets");
+  for (int32_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: offsets not monotone");
+  if (off[n] > off[0] && !adds) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: adds missing");
+  for (int32_t e = off[0]; e < off[n]; e++)
+    if (adds[e].cls < 0 || adds[e].cls >= h->dc.n_classes)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: class out of range");
+  // into the table's per-node importance order (CSR position k = caller row pre_index[k])
+  std::vector<int32_t> aoff((size_t)n + 1, 0);
+  std::vector<ksim_class_add> perm;
+  perm.reserve((size_t)(off[n] - off[0]));
+  for (int32_t k = 0; k < n; k++) {
+    const int32_t i = h->pre_index[k];
+    if (off[i + 1] > off[i]) perm.insert(perm.end(), adds + off[i], adds + off[i + 1]);
+    aoff[(size_t)k + 1] = (int32_t)perm.size();
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  free_bufs(h->pre_add_bufs);                   // every dry run ends synchronized: nothing reads them
+  h->pre.aoff = nullptr;
+  h->pre.adds = nullptr;
+  int rc;
+  void *po = nullptr, *pa = nullptr;
+  if ((rc = upload(h, h->pre_add_bufs, aoff.data(), 4 * aoff.size(), &po))) return rc;
+  if ((rc = upload(h, h->pre_add_bufs, perm.data(), sizeof(ksim_class_add) * perm.size(), &pa))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
+  h->pre.aoff = (const int32_t*)po;
+  h->pre.adds = (const ksim_class_add*)pa;
   return KSIM_OK;
 }
 
@@ -4800,22 +4838,53 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
   if (is_sharded(h)) return set_err(h, KSIM_E_UNSUPPORTED, "preemption runs on unsharded handles");
   if (prof_has_filter(h->prof, KSIM_PL_NETWORK_BANDWIDTH))
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption dry runs re-run Fit only, not NetworkBandwidth");
-  if (ps->pods[pod_index].use_count > 0)
-    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with topology / port / image uses");
   if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
   if ((rc = validate_pod(h, ps, pod_index))) return rc;
-  int32_t fit = -1;
-  for (int f = 0; f < h->prof.n_filter; f++)
+  int32_t fit = -1, port = -1;
+  for (int f = 0; f < h->prof.n_filter; f++) {
     if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
+    if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
+  }
+  // The dry run re-runs NodeResourcesFit and NodePorts.  Uses that no Filter
+  // reads (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
+  // ignored; the ones whose Filter reads a domain beyond the node are refused.
+  const ksim_pod& pp = ps->pods[pod_index];
+  const bool topo = pp.use_count > 0;
+  uint32_t port_mask = 0;
+  for (int32_t k = 0; k < pp.use_count; k++) {
+    static const char* const kRefused[] = {"PTS_HARD", nullptr, "IPA_EXISTING_ANTI", "IPA_AFFINITY", "IPA_ANTI"};
+    const uint8_t kind = ps->uses[pp.use_first + k].kind;
+    if (kind <= KSIM_USE_IPA_ANTI && kRefused[kind])
+      return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_") + kRefused[kind] +
+                                                " use (its dry run needs the victims' domains)");
+    if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
+  }
+  if (port_mask && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
+                                      "(after ksim_set_bound_pods)");
   HIPCHK(h, hipSetDevice(h->device));
   DevPods P;
   if ((rc = upload_single(h, ps, pod_index, P))) return rc;
   if ((rc = set_run(h, 0, 1))) return rc;
   const LaunchArgs a = make_args(h, P, nullptr);
   DevPreempt pre = h->pre;
+  // The status pass: the per-pod cycle's filter phase.  For a pod with uses its
+  // PreFilter pass runs first; the domain tables and topology flags it fills
+  // are zero between cycles (k_select / k_bind re-zero them in a whole cycle).
+  auto filter_pass = [&]() -> int {
+    launch_filter_only(a, h->stream, topo);
+    HIPCHK(h, hipGetLastError());
+    if (topo) {
+      if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
+      HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
+    }
+    return KSIM_OK;
+  };
   std::vector<uint8_t> gfail((size_t)std::max(n_groups, 1), KSIM_PASSED);
   std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
+  std::vector<int32_t> goff((size_t)n_groups + 1, 0);    // the groups' class contributions (CSR)
+  std::vector<ksim_class_add> gadds;
   auto bind_group = [&](int32_t k, int sign) -> int {
     for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
       DevPods Q;
@@ -4828,8 +4897,7 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
   };
   for (int32_t k = 0; k < n_groups; k++) {                // pass 1 of each grouped node
     if ((rc = bind_group(k, 1))) return rc;
-    launch_filter_only(a, h->stream);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = filter_pass())) return rc;
     HIPCHK(h, hcopy(h, &gfail[k], h->sc.fail + gnodes[k], 1, hipMemcpyDeviceToHost));
     if ((rc = bind_group(k, -1))) return rc;
     int64_t* q = nreq.data() + (size_t)k * (KSIM_PREEMPT_REQ + 1);
@@ -4839,16 +4907,23 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
       q[1] += x.req_mem;
       q[2] += x.req_eph;
       for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
+      if (port_mask && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
     }
     q[KSIM_PREEMPT_REQ] = count[k];
+    goff[(size_t)k + 1] = (int32_t)gadds.size();
   }
-  launch_filter_only(a, h->stream);                        // every node as is
-  HIPCHK(h, hipGetLastError());
+  if ((rc = filter_pass())) return rc;                     // every node as is
   if (n_groups > 0) {
     free_bufs(h->pre_nom_bufs);
     void* p = nullptr;
     if ((rc = upload(h, h->pre_nom_bufs, nreq.data(), 8 * nreq.size(), &p))) return rc;
     pre.nreq = (const int64_t*)p;
+    if (port_mask) {                                       // the groups' holdings stay on their nodes too
+      if ((rc = upload(h, h->pre_nom_bufs, goff.data(), 4 * goff.size(), &p))) return rc;
+      pre.goff = (const int32_t*)p;
+      if ((rc = upload(h, h->pre_nom_bufs, gadds.data(), sizeof(ksim_class_add) * gadds.size(), &p))) return rc;
+      pre.gadds = (const ksim_class_add*)p;
+    }
     for (int32_t k = 0; k < n_groups; k++) {
       // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
       if (gfail[k] != KSIM_PASSED) {
@@ -4859,7 +4934,7 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
       HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
     }
   }
-  launch_preempt(a, pre, fit, priority, h->stream, false);
+  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask);
   HIPCHK(h, hipGetLastError());
   if (n_groups > 0) {
     static const int32_t kNoGroup = -1;

@@ -256,14 +256,23 @@ struct DevPreempt {
   int32_t* pick;                       // [4] nominated, victims, potential, candidates
   int32_t* nslot;                      // [n] nominated group of the node, -1: none
   const int64_t* nreq;                 // [groups][KSIM_PREEMPT_REQ + 1] requests, pod count
+  // host-port holdings (ksim_set_bound_pod_adds; read only for a preemptor with NodePorts uses)
+  const int32_t* aoff;                 // [n_bound + 1] CSR order: adds[aoff[j] .. aoff[j + 1]) of bound pod j
+  const ksim_class_add* adds;          // the bound pods' count-class contributions
+  const int32_t* goff;                 // [groups + 1] the same per nominated group
+  const ksim_class_add* gadds;
 };
-// filter = false: s.fail already holds the statuses (ksim_preempt_nominated)
+// filter = false: s.fail already holds the statuses (ksim_preempt_nominated).
+// port_index / port_mask: NodePorts' place in the profile's filter list and
+// the preemptor's NodePorts uses (bit i = use i); 0: the dry run re-runs Fit alone.
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio, hipStream_t stream,
-                    bool filter = true);
+                    bool filter = true, int32_t port_index = -1, uint32_t port_mask = 0);
 
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);
-void launch_filter_only(const LaunchArgs& a, hipStream_t stream);
+// topo: the pod carries uses; the PreFilter pass of its cycle runs first (the
+// caller re-zeroes the domain tables and the topology flags afterwards)
+void launch_filter_only(const LaunchArgs& a, hipStream_t stream, bool topo = false);
 // Sharded batch (node shards; the caller exchanges between the phases):
 //   launch_shard_eval    batch top; writes this shard's records to s.xsend
 //   (all-gather s.xsend -> s.xrecv [world][kBatchPods][kXRec])

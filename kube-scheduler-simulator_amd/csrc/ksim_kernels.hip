@@ -1672,10 +1672,12 @@ void launch_fw_normalize(const LaunchArgs& a, int32_t slot, const int32_t* nodes
   k_fw_normalize<<<1, kFinalThreads, 0, stream>>>(a.prof, slot, a.st, a.s, nodes, vals, n, out);
 }
 
-void launch_filter_only(const LaunchArgs& a, hipStream_t stream) {
+void launch_filter_only(const LaunchArgs& a, hipStream_t stream, bool topo) {
   // the variant the cycle launches (launch_cycle_t); the no-window one adds
   // into the window counters, which the caller clears afterwards
   const int blocks = (a.c.n + 255) / 256;
+  if (topo && !a.ptab) k_topo_prefilter<<<blocks, 256, 0, stream>>>(a.c, a.P, a.prof, a.st, a.s);
+  if (topo && !a.fuse_min) k_topo_min<false><<<1, 256, 0, stream>>>(a.c, a.P, a.prof, a.st, a.s);
   const bool nowin = num_feasible_nodes_to_find(a.prof.percentage_of_nodes_to_score, a.c.n) >= a.c.n &&
                      !prof_has_filter(a.prof, KSIM_PL_NETWORK_BANDWIDTH) &&
                      !prof_has_score(a.prof, KSIM_PL_NETWORK_BANDWIDTH);

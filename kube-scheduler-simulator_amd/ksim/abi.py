@@ -422,15 +422,27 @@ class _BoundPodsC(ctypes.Structure):
 
 
 class BoundPods:
-    """ksim_bound_pods over numpy arrays (kept alive by this object)."""
+    """ksim_bound_pods over numpy arrays (kept alive by this object).
+    ``adds_off`` / ``adds`` (optional, outside the C struct): the rows'
+    count-class contributions as a CSR, ``adds`` = [[class, count], ...]
+    (ksim_set_bound_pod_adds; the host-port holdings a dry run for a pod with
+    host ports reads)."""
 
-    def __init__(self, node, priority, start_time, req):
+    def __init__(self, node, priority, start_time, req, adds_off=None, adds=None):
         self.node = np.ascontiguousarray(node, np.int32)
         self.priority = np.ascontiguousarray(priority, np.int32)
         self.start_time = np.ascontiguousarray(start_time, np.int64)
         self.req = np.ascontiguousarray(np.asarray(req, np.int64).reshape(-1, PREEMPT_REQ))
         self.n = int(self.node.size)
         self.c = _BoundPodsC(self.n, 0, _p(self.node), _p(self.priority), _p(self.start_time), _p(self.req))
+        if (adds_off is None) != (adds is None):
+            raise ValueError("adds_off and adds go together")
+        self.adds_off = self.adds = None
+        if adds_off is not None:
+            self.adds_off = np.ascontiguousarray(adds_off, np.int32)
+            self.adds = np.ascontiguousarray(np.asarray(adds, np.int32).reshape(-1, 2))   # ksim_class_add rows
+            if self.adds_off.size != self.n + 1:
+                raise ValueError("adds_off has one entry per row plus one")
 
 
 class _PreemptOutC(ctypes.Structure):

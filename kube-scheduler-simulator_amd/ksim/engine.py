@@ -29,7 +29,7 @@ EXPORTS = [
     "ksim_time_kernels", "ksim_kernel_name", "ksim_time_eval", "ksim_get_diag", "ksim_batch_geometry",
     "ksim_set_shard", "ksim_comm_unique_id", "ksim_comm_init", "ksim_group_schedule_loaded",
     "ksim_emit_cycle_json", "ksim_eval_pod_filter", "ksim_eval_pod_finish",
-    "ksim_set_bound_pods", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
+    "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
@@ -103,6 +103,8 @@ def _load(path):
     L.ksim_eval_pod.argtypes = [vp, vp, i32, vp]
     L.ksim_eval_pod_filter.argtypes = [vp, vp, i32, vp]
     L.ksim_set_bound_pods.argtypes = [vp, vp]
+    if hasattr(L, "ksim_set_bound_pod_adds"):   # an addition within ABI 12: detected by symbol
+        L.ksim_set_bound_pod_adds.argtypes = [vp, vp, vp]
     L.ksim_preempt.argtypes = [vp, vp, i32, i32, vp]
     L.ksim_preempt_nominated.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
@@ -384,6 +386,19 @@ class Engine:
         """The bound-pod table DefaultPreemption may evict (ksim.abi.BoundPods)."""
         self._bound_n = bound.n
         self._chk(self.L.ksim_set_bound_pods(self.h, ctypes.byref(bound.c)))
+        if getattr(bound, "adds_off", None) is not None:
+            self.set_bound_pod_adds(bound.adds_off, bound.adds)
+
+    def set_bound_pod_adds(self, off, adds):
+        """The count-class contributions of the last set_bound_pods' rows (CSR:
+        ``off`` [n + 1], ``adds`` [[class, count], ...]): the host-port holdings
+        a dry run for a pod with host ports reads (ksim_set_bound_pod_adds)."""
+        off = np.ascontiguousarray(off, np.int32)
+        adds = np.ascontiguousarray(np.asarray(adds, np.int32).reshape(-1, 2))
+        if off.size != getattr(self, "_bound_n", -1) + 1:
+            raise ValueError("one offset per bound-pod row plus one")
+        self._chk(self.L.ksim_set_bound_pod_adds(self.h, off.ctypes.data_as(ctypes.c_void_p),
+                                                 adds.ctypes.data_as(ctypes.c_void_p)))
 
     def preempt(self, pods, index: int, priority: int, groups=None) -> tuple:
         """DefaultPreemption PostFilter dry run: (nominated node or -1, victim

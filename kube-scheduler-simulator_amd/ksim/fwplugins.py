@@ -223,7 +223,12 @@ class EnginePlugins:
         indices of the bound-pod table, override): override False is a nil
         result (ModeNoop, the pod keeps its nomination), True with node -1 is
         NominatedNodeName "" (ModeOverride clears it).  ``terminating_lower(node,
-        priority)``: a Terminating pod of lower priority is on the node."""
+        priority)``: a Terminating pod of lower priority is on the node.
+        A pod with host ports needs the bound pods' port holdings: the table
+        set on the engine (or ``bound``) built as ``ksim.preemption.bound_table(
+        cluster, pods, start, cluster.topo)`` after this cycle's pod was
+        compiled.  Pods with DoNotSchedule spread or required pod
+        (anti-)affinity are refused (KsimError, KSIM_E_UNSUPPORTED)."""
         if nominated_node >= 0 and (nominated_status is None or
                                     nominated_status.code != UNSCHEDULABLE_AND_UNRESOLVABLE):
             if terminating_lower is not None and terminating_lower(nominated_node, priority):

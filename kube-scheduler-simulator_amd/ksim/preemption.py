@@ -13,8 +13,12 @@ from .encode import pod_requests
 from .model import Pod
 
 
-def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int]) -> abi.BoundPods:
-    """ksim_bound_pods for ``bound`` (pods whose node is in ``cluster``), in list order."""
+def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None) -> abi.BoundPods:
+    """ksim_bound_pods for ``bound`` (pods whose node is in ``cluster``), in list order.
+    With ``topo`` (the cluster's ksim.topology.TopologyIndex) the table also
+    carries each row's host-port holdings (``topo.port_adds``, over the port
+    classes registered so far: build it after the preemptor is encoded), which
+    the dry run of a pod with host ports reads (ksim_set_bound_pod_adds)."""
     pos = {n: i for i, n in enumerate(cluster.node_names)}
     rows = [p for p in bound if p.node_name in pos]
     node = np.array([pos[p.node_name] for p in rows], np.int32)
@@ -28,4 +32,10 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int]) -> ab
         req[i, 2] = r.get("ephemeral-storage", 0)
         for k, name in enumerate(cluster.scalar_names):
             req[i, 3 + k] = r.get(name, 0)
-    return abi.BoundPods(node, prio, start, req)
+    if topo is None:
+        return abi.BoundPods(node, prio, start, req)
+    off, adds = [0], []
+    for p in rows:
+        adds.extend(sorted(topo.port_adds(p).items()))
+        off.append(len(adds))
+    return abi.BoundPods(node, prio, start, req, np.array(off, np.int32), np.array(adds, np.int32).reshape(-1, 2))

@@ -180,7 +180,10 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     (ksim_eval_pod), then for an unschedulable pod DefaultPreemption's
     PostFilter dry run (ksim_preempt over the bound-pod table set with
     set_bound_pods) when the profile enables it, recorded into ``store``.
-    ``backend`` is an Engine (or the oracle, whose preempt takes ``bound``)."""
+    ``backend`` is an Engine (or the oracle, whose preempt takes ``bound``).
+    For a pod with host ports the table carries the bound pods' port holdings
+    (``ksim.preemption.bound_table(cluster, pods, start, cluster.topo)``, built
+    after ``pods`` was compiled)."""
     res = backend.eval_pod(pods, index) if hasattr(backend, "eval_pod") else backend.cycle(pods, index)
     nominated = -1
     post = [original_name(p.name) for p in prof.plugins["postFilter"].enabled]

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Host wall time of one DefaultPreemption dry run (ksim_preempt) for a
+use-free preemptor: 5,000 nodes of 10 CPUs, four bound pods each of mixed
+priorities and start times filling 9.6 CPUs, a 2-CPU preemptor of priority
+1,000, so every node is a potential node and a candidate.  Each timed call is
+Engine.preempt: the pod's upload, the filter pass, the two preemption kernels
+and the result copies, ending synchronized.
+
+Prints one JSON line: the calls' median, min, max and the 10th / 90th
+percentiles in microseconds, per repeat (a fresh handle each) and over all.
+To compare two builds on one machine run it once per library
+(KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
+
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+for p in (ROOT, os.path.join(ROOT, "kube-scheduler-simulator_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+from ksim import abi, engine, profile  # noqa: E402
+from ksim.encode import encode_cluster, encode_pods  # noqa: E402
+from ksim.model import Container, Node, Pod  # noqa: E402
+
+
+def build(n_nodes: int):
+    rng = np.random.default_rng(7)
+    nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}"},
+                  allocatable={"cpu": "10", "memory": "64Gi", "pods": "110"}) for i in range(n_nodes)]
+    bound, node, prio, start = [], [], [], []
+    for v in range(n_nodes):
+        for k in range(4):
+            bound.append(Pod(f"b{v}-{k}", node_name=nodes[v].name, containers=[Container({"cpu": "2400m"})]))
+            node.append(v)
+            prio.append(int(rng.choice([0, 10, 100, 500])))
+            start.append(int(rng.integers(0, 1000)))
+    cluster, _ = encode_cluster(nodes, bound)
+    assert list(cluster.node_names) == [n.name for n in nodes]
+    req = np.zeros((len(bound), abi.PREEMPT_REQ), np.int64)
+    req[:, 0] = 2400
+    table = abi.BoundPods(node, prio, start, req)
+    enc = encode_pods(cluster, [Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})])])
+    assert int(enc.pods[0]["use_count"]) == 0
+    prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
+    return cluster, table, enc, prof
+
+
+def pct(xs, q):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, int(q * len(xs)))]
+
+
+def summary(us):
+    return dict(median_us=round(statistics.median(us), 1), min_us=round(min(us), 1), max_us=round(max(us), 1),
+                p10_us=round(pct(us, 0.10), 1), p90_us=round(pct(us, 0.90), 1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=5000)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    args = ap.parse_args()
+    cluster, table, enc, prof = build(args.nodes)
+    runs, every, result = [], [], None
+    for _ in range(args.repeats):
+        eng = engine.Engine(0)
+        eng.set_profile(prof)
+        eng.set_cluster(cluster)
+        eng.set_bound_pods(table)
+        for _ in range(args.warmup):
+            result = eng.preempt(enc, 0, 1000)
+        us = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            eng.preempt(enc, 0, 1000)
+            us.append((time.perf_counter() - t0) * 1e6)
+        eng.close()
+        runs.append(summary(us))
+        every += us
+    print(json.dumps(dict(bench="preempt_use_free", library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
+                          bound_pods=table.n, calls=args.calls, repeats=args.repeats,
+                          nominated=result[0], victims=len(result[1]), potential=result[2], candidates=result[3],
+                          runs=runs, **summary(every))))
+
+
+if __name__ == "__main__":
+    main()
