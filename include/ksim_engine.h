@@ -776,14 +776,18 @@ typedef struct ksim_preempt_out {
 /* Replace the bound-pod table (copied; the engine orders it per node by
  * importance: priority desc, start time asc). */
 int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b);
-/* The host-port holdings of the bound pods of the last ksim_set_bound_pods
+/* The class contributions of the bound pods of the last ksim_set_bound_pods
  * (which drops any earlier ones), as a CSR over its rows in the caller's row
  * order: adds[off[i] .. off[i + 1]) are row i's count-class contributions
  * (what a queue pod carries as add_first / add_count), off has n + 1 entries.
- * Only the classes a preemptor's KSIM_USE_NODE_PORT uses name are read; others
- * may be present.  Copied.  KSIM_E_INVALID: no table set, offsets not
- * monotone, a class outside [0, n_classes).  Needed only before a dry run for
- * a pod with KSIM_USE_NODE_PORT uses under a profile that filters on NodePorts. */
+ * The classes read are those of the preemptor's KSIM_USE_NODE_PORT uses (the
+ * rows' host-port holdings) and of its KSIM_USE_IPA_AFFINITY / IPA_ANTI /
+ * IPA_EXISTING_ANTI uses (the selector classes a row matches and the required
+ * anti-affinity terms it carries, each with its multiplicity); others may be
+ * present, and a row must list every one of those it counts into.  Copied.
+ * KSIM_E_INVALID: no table set, offsets not monotone, a class outside
+ * [0, n_classes).  Needed only before a dry run for a pod with such uses under
+ * a profile that filters on NodePorts / InterPodAffinity. */
 int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds);
 /* DefaultPreemption's PostFilter for an unschedulable pod of `priority`
  * (default_preemption.go / preemption.go, v1.26) on the current snapshot,
@@ -791,8 +795,11 @@ int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class
  * wrapper calls and records (scheduler/plugin/wrappedplugin.go:518-544,
  * Store.AddPostFilterResult store.go:437):
  *   potential nodes  the nodes whose filter status is Unschedulable, i.e. the
- *                    ones that failed NodeResourcesFit or NodePorts (the other
- *                    plugins ahead of them return UnschedulableAndUnresolvable);
+ *                    ones that failed NodeResourcesFit, NodePorts, or
+ *                    InterPodAffinity with KSIM_IPA_ANTI_AFFINITY or
+ *                    KSIM_IPA_EXISTING_ANTI (KSIM_IPA_AFFINITY, a missing
+ *                    topology key or no matching pod, and the other plugins
+ *                    ahead of them return UnschedulableAndUnresolvable);
  *   dry run          SelectVictimsOnNode on each, in nodeTree order from
  *                    offset 0 (upstream draws a random offset), keeping the
  *                    first numCandidates = max(minCandidateNodesPercentage %
@@ -802,7 +809,8 @@ int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class
  *                    priority, lowest sum of (priority + 2^31), fewest
  *                    victims, latest earliest start among the highest-
  *                    priority victims, then the first candidate (no PDBs).
- * The dry run re-runs NodeResourcesFit and NodePorts on each potential node.
+ * The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity on each
+ * potential node.
  * The pod's uses, by kind:
  *   PTS_SOFT, IPA_SCORE, IPA_SCORE_HARD, IMAGE   read by no Filter: ignored;
  *   NODE_PORT   a node holding a pod of the port class fails NodePorts
@@ -812,9 +820,20 @@ int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class
  *               contributions (ksim_set_bound_pod_adds; KSIM_E_INVALID without
  *               them) and, on a grouped node, the nominated pods' own adds.
  *               Ignored when the profile's filter list has no NodePorts;
- *   PTS_HARD, IPA_AFFINITY, IPA_ANTI, IPA_EXISTING_ANTI   their Filter reads a
- *               domain beyond the node: KSIM_E_UNSUPPORTED (the message names
- *               the kind).
+ *   IPA_AFFINITY, IPA_ANTI, IPA_EXISTING_ANTI   the dry run of node n starts
+ *               from what the Filter read for n (the domain sum of n's value
+ *               of the use's key, or n's own count for a key unique per node)
+ *               and moves it by count x sign of every add of the use's class
+ *               of each of n's pods it removes or adds back, and of a
+ *               nominated group that stays (only n's own pods move: upstream
+ *               copies the cycle state per node); a use whose key n lacks is
+ *               not read.  The first-pod rule (KSIM_POD_IPA_SELF_AFFINITY)
+ *               sees whether any matching pod is left cluster-wide.  The adds
+ *               come from ksim_set_bound_pod_adds (KSIM_E_INVALID without
+ *               them).  Ignored when the filter list has no InterPodAffinity;
+ *   PTS_HARD    its Filter needs the minimum over every domain after each
+ *               removal: KSIM_E_UNSUPPORTED (the message names PTS_HARD), also
+ *               beside InterPodAffinity uses.
  * Also KSIM_E_UNSUPPORTED: shard handles, NetworkBandwidth in the filter list,
  * KSIM_POD_NODE_NAMES pods. */
 int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
@@ -826,8 +845,11 @@ int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, in
  * `priority`, the preemptor excluded (the caller selects them, as for
  * ksim_fw_filter_nominated; nodes distinct).  A grouped node's status is the
  * two-pass one (pass 1 with the group's pods added; pass 2 as is only if pass
- * 1 passed) and its dry run keeps the group's requests and pod count on the
- * node.  n_groups = 0 is ksim_preempt. */
+ * 1 passed) and its dry run keeps the group's requests, pod count and class
+ * contributions (ports, InterPodAffinity domain counts) on the node: pass 1 of
+ * each trial; pass 2 is not re-run, which for required affinity means a node
+ * whose only matching pod is nominated there can be a candidate.
+ * n_groups = 0 is ksim_preempt. */
 int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                            const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
                            const int32_t* first, const int32_t* count, ksim_preempt_out* out);

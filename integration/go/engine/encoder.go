@@ -1048,7 +1048,7 @@ func (n *NativeEncoder) BoundTable(e *Engine) error {
 	n.mu.Lock()
 	defer n.mu.Unlock()
 	if !n.tableOld {
-		// the rows stand; their adds follow the port classes the cycle's pod registered
+		// the rows stand; their adds follow the classes the cycle's pod registered
 		if int32(n.info().n_classes) != n.addsAt {
 			return n.boundAdds(e)
 		}
@@ -1115,10 +1115,13 @@ func (n *NativeEncoder) BoundTable(e *Engine) error {
 // boundAdds sends the table rows' count-class contributions
 // (ksim_set_bound_pod_adds; ksim/preemption.py bound_table with a
 // TopologyIndex): each row compiled as a queue pod, whose adds are what its
-// bind put on its node, port_adds among them.  The engine reads the port
-// classes only.  The cycle's own set is a copy (Pod), so this compile does not
+// bind put on its node: every class it counts into (bound_table's full_adds
+// form), port_adds among them.  The engine reads the classes of the preemptor's
+// port uses and of its required pod (anti-)affinity and existing-anti-affinity
+// uses.  The cycle's own set is a copy (Pod), so this compile does not
 // disturb it.  The adds cover the classes registered so far; a cycle whose pod
-// registers a new port class sends them again (addsAt).
+// registers a new class (a port, a selector, a carried term) sends them again
+// (addsAt).
 func (n *NativeEncoder) boundAdds(e *Engine) error {
 	off := make([]int32, len(n.boundRows)+1)
 	adds := make([]C.ksim_class_add, 0, len(n.boundRows))

@@ -188,8 +188,10 @@ func (e *Engine) SetBoundPods(b *C.ksim_bound_pods) error {
 }
 
 // SetBoundPodAdds: the count-class contributions of the last SetBoundPods'
-// rows (CSR: off has one entry per row plus one), the host-port holdings the
-// dry run of a pod with host ports reads.  Copied by the engine.
+// rows (CSR: off has one entry per row plus one): the host-port holdings the
+// dry run of a pod with host ports reads, and the selector and carried-term
+// classes the dry run of a pod with required pod (anti-)affinity reads.
+// Copied by the engine.
 func (e *Engine) SetBoundPodAdds(off []int32, adds *C.ksim_class_add) error {
 	return e.locked(func() C.int {
 		return C.ksim_set_bound_pod_adds(e.h, (*C.int32_t)(unsafe.Pointer(&off[0])), adds)

@@ -690,6 +690,9 @@ func (p *postFilter) PostFilter(ctx context.Context, state *framework.CycleState
 	perr := pr.Engine.err(rc) // under the mutex: the handle's last error is this call's
 	pr.Engine.mu.Unlock()
 	if rc == C.KSIM_E_UNSUPPORTED {
+		// a pod with DoNotSchedule spread (KSIM_USE_PTS_HARD): the original answers.
+		// Pods with required pod (anti-)affinity are the engine's: BoundTable sent
+		// every class the bound pods count into, which their dry run moves
 		return p.orig.(framework.PostFilterPlugin).PostFilter(ctx, state, pod, m)
 	}
 	if perr != nil {

@@ -4767,6 +4767,8 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   d.nslot = (int32_t*)p;
   HIPCHK(h, hipMemsetAsync(d.nslot, 0xff, 4 * (size_t)std::max(N, 1), h->stream));   // -1: no group
   d.nreq = nullptr;
+  if ((rc = upload(h, h->pre_bufs, nullptr, 8 * (size_t)KSIM_MAX_USES, &p))) return rc;
+  d.afftot = (int64_t*)p;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->pre = d;
   h->pre_index = ix;
@@ -4841,28 +4843,37 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
   if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
   if ((rc = validate_pod(h, ps, pod_index))) return rc;
-  int32_t fit = -1, port = -1;
+  int32_t fit = -1, port = -1, ipa = -1;
   for (int f = 0; f < h->prof.n_filter; f++) {
     if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
     if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
+    if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) ipa = f;
   }
-  // The dry run re-runs NodeResourcesFit and NodePorts.  Uses that no Filter
-  // reads (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
-  // ignored; the ones whose Filter reads a domain beyond the node are refused.
+  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity.  Uses
+  // that no Filter reads (ScheduleAnyway spread, InterPodAffinity scores,
+  // ImageLocality) are ignored; DoNotSchedule spread, whose Filter needs the
+  // minimum over every domain after each removal, is refused.
   const ksim_pod& pp = ps->pods[pod_index];
   const bool topo = pp.use_count > 0;
-  uint32_t port_mask = 0;
+  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0;
+  for (int32_t k = 0; k < pp.use_count; k++)
+    if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
+      return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
+                                            "victims' domains)");
   for (int32_t k = 0; k < pp.use_count; k++) {
-    static const char* const kRefused[] = {"PTS_HARD", nullptr, "IPA_EXISTING_ANTI", "IPA_AFFINITY", "IPA_ANTI"};
     const uint8_t kind = ps->uses[pp.use_first + k].kind;
-    if (kind <= KSIM_USE_IPA_ANTI && kRefused[kind])
-      return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_") + kRefused[kind] +
-                                                " use (its dry run needs the victims' domains)");
     if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_AFFINITY && ipa >= 0) aff_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_ANTI && ipa >= 0) anti_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_EXISTING_ANTI && ipa >= 0) exist_mask |= 1u << k;
   }
-  if (port_mask && !h->pre.aoff)
+  const bool dom_form = (aff_mask | anti_mask | exist_mask) != 0;   // the domain form of k_preempt_nodes
+  if (port_mask && !dom_form && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
                                       "(after ksim_set_bound_pods)");
+  if (dom_form && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
+                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
   HIPCHK(h, hipSetDevice(h->device));
   DevPods P;
   if ((rc = upload_single(h, ps, pod_index, P))) return rc;
@@ -4872,14 +4883,17 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
   // The status pass: the per-pod cycle's filter phase.  For a pod with uses its
   // PreFilter pass runs first; the domain tables and topology flags it fills
   // are zero between cycles (k_select / k_bind re-zero them in a whole cycle).
-  auto filter_pass = [&]() -> int {
+  // keep: the domain form of k_preempt_nodes reads the last pass's tables, so
+  // the caller re-zeroes them after that kernel.
+  auto rezero = [&]() -> int {
+    if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
+    HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
+    return KSIM_OK;
+  };
+  auto filter_pass = [&](bool keep = false) -> int {
     launch_filter_only(a, h->stream, topo);
     HIPCHK(h, hipGetLastError());
-    if (topo) {
-      if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
-      HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
-    }
-    return KSIM_OK;
+    return topo && !keep ? rezero() : KSIM_OK;
   };
   std::vector<uint8_t> gfail((size_t)std::max(n_groups, 1), KSIM_PASSED);
   std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
@@ -4907,23 +4921,25 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
       q[1] += x.req_mem;
       q[2] += x.req_eph;
       for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
-      if (port_mask && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
+      if ((port_mask || dom_form) && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
     }
     q[KSIM_PREEMPT_REQ] = count[k];
     goff[(size_t)k + 1] = (int32_t)gadds.size();
   }
-  if ((rc = filter_pass())) return rc;                     // every node as is
   if (n_groups > 0) {
     free_bufs(h->pre_nom_bufs);
     void* p = nullptr;
     if ((rc = upload(h, h->pre_nom_bufs, nreq.data(), 8 * nreq.size(), &p))) return rc;
     pre.nreq = (const int64_t*)p;
-    if (port_mask) {                                       // the groups' holdings stay on their nodes too
+    if (port_mask || dom_form) {                           // the groups' holdings stay on their nodes too
       if ((rc = upload(h, h->pre_nom_bufs, goff.data(), 4 * goff.size(), &p))) return rc;
       pre.goff = (const int32_t*)p;
       if ((rc = upload(h, h->pre_nom_bufs, gadds.data(), sizeof(ksim_class_add) * gadds.size(), &p))) return rc;
       pre.gadds = (const ksim_class_add*)p;
     }
+  }
+  if ((rc = filter_pass(dom_form))) return rc;             // every node as is
+  if (n_groups > 0) {
     for (int32_t k = 0; k < n_groups; k++) {
       // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
       if (gfail[k] != KSIM_PASSED) {
@@ -4934,8 +4950,9 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
       HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
     }
   }
-  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask);
+  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask);
   HIPCHK(h, hipGetLastError());
+  if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
   if (n_groups > 0) {
     static const int32_t kNoGroup = -1;
     for (int32_t k = 0; k < n_groups; k++)

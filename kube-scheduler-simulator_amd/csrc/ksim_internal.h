@@ -256,17 +256,23 @@ struct DevPreempt {
   int32_t* pick;                       // [4] nominated, victims, potential, candidates
   int32_t* nslot;                      // [n] nominated group of the node, -1: none
   const int64_t* nreq;                 // [groups][KSIM_PREEMPT_REQ + 1] requests, pod count
-  // host-port holdings (ksim_set_bound_pod_adds; read only for a preemptor with NodePorts uses)
+  // class contributions (ksim_set_bound_pod_adds; read only for a preemptor with NodePorts or
+  // required pod (anti-)affinity uses)
   const int32_t* aoff;                 // [n_bound + 1] CSR order: adds[aoff[j] .. aoff[j + 1]) of bound pod j
   const ksim_class_add* adds;          // the bound pods' count-class contributions
   const int32_t* goff;                 // [groups + 1] the same per nominated group
   const ksim_class_add* gadds;
+  int64_t* afftot;                     // [KSIM_MAX_USES] cluster-wide totals of the preemptor's required-affinity uses
 };
 // filter = false: s.fail already holds the statuses (ksim_preempt_nominated).
 // port_index / port_mask: NodePorts' place in the profile's filter list and
 // the preemptor's NodePorts uses (bit i = use i); 0: the dry run re-runs Fit alone.
+// ipa_index / aff, anti, exist: InterPodAffinity's place and the preemptor's
+// required-affinity, required-anti-affinity and existing-anti-affinity uses
+// (the domain form: s.dom still holds the status pass's domain tables).
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio, hipStream_t stream,
-                    bool filter = true, int32_t port_index = -1, uint32_t port_mask = 0);
+                    bool filter = true, int32_t port_index = -1, uint32_t port_mask = 0, int32_t ipa_index = -1,
+                    uint32_t aff = 0, uint32_t anti = 0, uint32_t exist = 0);
 
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);

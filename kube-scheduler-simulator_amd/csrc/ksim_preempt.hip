@@ -12,7 +12,12 @@
 // and moves it with every pod it removes or adds back, from the bound pods'
 // class contributions (ksim_set_bound_pod_adds).  The bound pods are
 // held per node in importance order (CSR), so the lower-priority pods are a
-// suffix of the node's range.  One block then keeps the first numCandidates
+// suffix of the node's range.  A pod with required pod (anti-)affinity uses
+// takes the domain form: the thread holds the node's TopoRow (the domain sum of
+// the node's topology value, or the node's own count, per use), moves it the
+// same way and re-runs interpodaffinity's Filter on it; a node that failed
+// InterPodAffinity for an anti-affinity reason is a potential node too.  One
+// block then keeps the first numCandidates
 // candidates in nodeTree order (upstream scans from a random offset; offset 0
 // here) and picks one by pickOneNodeForPreemption's criteria.
 #include "ksim_device.h"
@@ -58,13 +63,50 @@ __device__ __forceinline__ bool hold_conflict(const PortHold& h) {
   return hit;
 }
 
+// The preemptor's filter-read uses in the domain form (kernel argument, bit i =
+// use i): its InterPodAffinity uses by role when the profile filters on them,
+// and that filter's place in the profile.  All zero: no domain form.
+struct PreemptDom {
+  uint32_t aff, anti, exist;
+  int32_t ipa_index;
+};
+// NodeInfo.AddPod / RemovePod and PreFilterExtensions.AddPod / RemovePod of one
+// pod (or nominated group) on the node's row: sign x count of every add whose
+// class a filter-read use reads.  A use whose key the node lacks (t.v[i] == 0)
+// moves too, but no Filter reads its count (upstream leaves its maps alone).
+__device__ __forceinline__ void topo_add(TopoRow& t, const int32_t (&cls)[KSIM_MAX_USES],
+                                         const ksim_class_add* __restrict__ adds, int32_t e0, int32_t e1, int sign) {
+  for (int32_t e = e0; e < e1; e++) {
+    const ksim_class_add x = adds[e];
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++)
+      if (cls[i] == x.cls) t.x[i] += (int64_t)sign * x.count;
+  }
+}
+// len(state.affinityCounts) > 0 on the moved row: a matching pod outside the
+// node's domains (outside: the use's cluster-wide total minus the node's domain
+// sum, neither of which another node's dry run changes), or one left inside
+__device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, const TopoRow& t) {
+  bool any = outside;
+#pragma unroll
+  for (int i = 0; i < KSIM_MAX_USES; i++)
+    if (((aff >> i) & 1u) && t.v[i] != 0 && t.x[i] > 0) any = true;
+  return any ? kTopoAffinityNonEmpty : 0u;
+}
+
 // SelectVictimsOnNode of one potential node.  PORTS: the dry run re-runs
 // NodePorts beside NodeResourcesFit (the preemptor has port uses and the
 // profile filters on them); fit: the profile has NodeResourcesFit.
-template <bool PORTS>
-__device__ __forceinline__ void select_victims(const DevCluster& c, const ksim_pod& p, const ksim_topo_use* U,
+// DOM (the domain form): the dry run re-runs NodePorts and InterPodAffinity on
+// the node's TopoRow.  The node failed at Fit, NodePorts or InterPodAffinity;
+// the last is a potential node only for an anti-affinity reason, which the
+// thread re-derives from the row (with the nominated group on it: pass 1).
+template <bool PORTS, bool DOM = false>
+__device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
+                                               const ksim_pod& p, const PodPlan& plan, const ksim_topo_use* U,
                                                const DevPreempt& pre, int32_t node, int32_t prio, bool fit,
-                                               uint32_t port_mask, PreemptNode& out) {
+                                               uint32_t port_mask, const PreemptDom& dm, bool at_ipa,
+                                               PreemptNode& out) {
   const int32_t a = pre.off[node], b = pre.off[node + 1];
   int32_t j0 = a;
   while (j0 < b && pre.prio[j0] >= prio) j0++;       // lower priorities: the suffix [j0, b)
@@ -78,6 +120,29 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const ksim_p
   }
   int32_t cls[KSIM_MAX_USES];
   PortHold h;
+  TopoRow t;
+  UseMasks mm{};                                        // the roles the dry run's filters read
+  bool outside = false;
+  if (DOM) {
+    mm.port = port_mask;
+    mm.aff = dm.aff;
+    mm.anti = dm.anti;
+    mm.exist = dm.exist;
+    const uint32_t read = port_mask | dm.aff | dm.anti | dm.exist;
+    load_topo_row(c, U, p.use_count, plan.m, s, P.ptab, node, t);
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      cls[i] = kNoPortClass;
+      if ((read >> i) & 1u) cls[i] = load_use(U, i).cls;
+      if (((dm.aff >> i) & 1u) && t.v[i] != 0 && pre.afftot[i] - t.x[i] > 0) outside = true;
+    }
+    if (g >= 0) topo_add(t, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
+    if (at_ipa) {                                       // the status pass's InterPodAffinity detail
+      const uint32_t why = ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t);
+      if (why != KSIM_IPA_ANTI_AFFINITY && why != KSIM_IPA_EXISTING_ANTI) return;   // UnschedulableAndUnresolvable
+    }
+    out.potential = 1;
+  }
   if (PORTS) {
 #pragma unroll
     for (int i = 0; i < KSIM_MAX_USES; i++) {
@@ -93,10 +158,12 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const ksim_p
   for (int32_t j = j0; j < b; j++) {
     row_add_req(r, pre.req + (size_t)j * KSIM_PREEMPT_REQ, -1, c.n_scalar);
     if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+    if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
   }
   // the filters the dry run re-runs: 0 = the pod passes
   auto fails = [&]() -> bool {
-    if ((!PORTS || fit) && fits_request(r, p, c.n_scalar, c.fit_ignore) != 0) return true;
+    if ((!(PORTS || DOM) || fit) && fits_request(r, p, c.n_scalar, c.fit_ignore) != 0) return true;
+    if (DOM) return node_port_conflict(mm, t) || ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t) != 0;
     return PORTS && hold_conflict(h);
   };
   if (!fails()) {
@@ -107,11 +174,13 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const ksim_p
       const int64_t* q = pre.req + (size_t)j * KSIM_PREEMPT_REQ;
       row_add_req(r, q, 1, c.n_scalar);
       if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
+      if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
       const bool victim = fails();
       pre.vflag[j] = victim;
       if (victim) {
         row_add_req(r, q, -1, c.n_scalar);
         if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+        if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
         if (nv == 0) high = pre.prio[j];
         sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
         if (pre.prio[j] == high && pre.start[j] < early) early = pre.start[j];   // GetEarliestPodStartTime
@@ -131,27 +200,69 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const ksim_p
 // victim priority, sum of (priority + 2^31), earliest start among the
 // highest-priority victims}; vflag marks the victims (CSR order).  A potential
 // node failed NodeResourcesFit or, for a preemptor with port uses (port_mask),
-// NodePorts: the two filters that return Unschedulable and that the dry run
-// re-runs.
+// NodePorts or, for one with required pod (anti-)affinity uses (dm),
+// InterPodAffinity with an anti-affinity detail: the filters that return
+// Unschedulable and that the dry run re-runs.  DOM: the domain form, a kernel
+// of its own, so a preemptor without such uses runs the code (and keeps the
+// registers) it had before that form existed.
+template <bool DOM>
 __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, const DevState* __restrict__ st,
                                                        DevScratch s, DevPreempt pre, int32_t fit_index,
-                                                       int32_t prio, int32_t port_index, uint32_t port_mask) {
+                                                       int32_t prio, int32_t port_index, uint32_t port_mask,
+                                                       PreemptDom dm) {
   const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= c.n) return;
   PreemptNode out{};
   out.cand = 0;
   const uint8_t f = s.fail[node];
-  const bool potential = (fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index);
-  out.potential = potential;
-  if (potential) {
-    const ksim_pod& p = P.pods[st->cursor];
-    const ksim_topo_use* U = P.uses + p.use_first;
-    if (port_mask)                                     // kernel argument: one uniform branch
-      select_victims<true>(c, p, U, pre, node, prio, fit_index >= 0, port_mask, out);
-    else
-      select_victims<false>(c, p, U, pre, node, prio, true, 0u, out);
+  const ksim_pod& p = P.pods[st->cursor];
+  const ksim_topo_use* U = P.uses + p.use_first;
+  if (DOM) {
+    const bool at_ipa = f == (uint8_t)dm.ipa_index;
+    if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa)
+      select_victims<false, true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
+                                  at_ipa, out);
+  } else {
+    const bool potential = (fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index);
+    out.potential = potential;
+    if (potential) {
+      if (port_mask)                                   // kernel argument: one uniform branch
+        select_victims<true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
+                             false, out);
+      else
+        select_victims<false>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, out);
+    }
   }
   pre.res[node] = out;
+}
+
+// The cluster-wide total of each required-affinity use over the nodes that
+// carry its key (pre.afftot[i]; 0 for every other use): with the node's own
+// domain sum it tells a dry run whether a matching pod exists outside the
+// node's domains (upstream's len(affinityCounts) after RemovePod).
+__global__ __launch_bounds__(256) void k_preempt_totals(DevCluster c, DevPods P, const DevState* __restrict__ st,
+                                                        DevPreempt pre, uint32_t aff) {
+  __shared__ int64_t sh[4];
+  const ksim_pod& p = P.pods[st->cursor];
+  const ksim_topo_use* U = P.uses + p.use_first;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int i = 0; i < KSIM_MAX_USES; i++) {
+    if (!((aff >> i) & 1u)) {                          // block-uniform
+      if (tid == 0) pre.afftot[i] = 0;
+      continue;
+    }
+    const ksim_topo_use u = load_use(U, i);
+    int64_t sum = 0;
+    if (u.col != KSIM_COL_NONE && u.cls >= 0)
+      for (int32_t n = tid; n < c.n; n += blockDim.x)
+        if (c.labels[(size_t)u.col * c.n + n] != 0) sum += c.cnt[(size_t)u.cls * c.n + n];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    __syncthreads();
+    if (lane == 0) sh[w] = sum;
+    __syncthreads();
+    if (tid == 0) pre.afftot[i] = sh[0] + sh[1] + sh[2] + sh[3];
+  }
 }
 
 // pickOneNodeForPreemption order: a is better than b
@@ -249,11 +360,18 @@ __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, Dev
 }
 
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                    hipStream_t stream, bool filter, int32_t port_index, uint32_t port_mask) {
+                    hipStream_t stream, bool filter, int32_t port_index, uint32_t port_mask, int32_t ipa_index,
+                    uint32_t aff, uint32_t anti, uint32_t exist) {
   const int blocks = (a.c.n + 255) / 256;
   if (filter) launch_filter_only(a, stream);             // the filter statuses of every node
   if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
-  k_preempt_nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask);
+  if (ipa_index < 0) aff = anti = exist = 0;             // nor the InterPodAffinity uses without that filter
+  const PreemptDom dm{aff, anti, exist, ipa_index};
+  if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
+  if (aff | anti | exist)
+    k_preempt_nodes<true><<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
+  else
+    k_preempt_nodes<false><<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

@@ -392,7 +392,9 @@ class Engine:
     def set_bound_pod_adds(self, off, adds):
         """The count-class contributions of the last set_bound_pods' rows (CSR:
         ``off`` [n + 1], ``adds`` [[class, count], ...]): the host-port holdings
-        a dry run for a pod with host ports reads (ksim_set_bound_pod_adds)."""
+        a dry run for a pod with host ports reads, and the selector and
+        carried-term classes one for a pod with required pod (anti-)affinity
+        reads (ksim_set_bound_pod_adds)."""
         off = np.ascontiguousarray(off, np.int32)
         adds = np.ascontiguousarray(np.asarray(adds, np.int32).reshape(-1, 2))
         if off.size != getattr(self, "_bound_n", -1) + 1:

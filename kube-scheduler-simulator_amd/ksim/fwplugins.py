@@ -227,8 +227,11 @@ class EnginePlugins:
         A pod with host ports needs the bound pods' port holdings: the table
         set on the engine (or ``bound``) built as ``ksim.preemption.bound_table(
         cluster, pods, start, cluster.topo)`` after this cycle's pod was
-        compiled.  Pods with DoNotSchedule spread or required pod
-        (anti-)affinity are refused (KsimError, KSIM_E_UNSUPPORTED)."""
+        compiled.  A pod with required pod (anti-)affinity, or one that a
+        bound pod's required anti-affinity term matches, needs every class
+        the bound pods count into: the same call with ``full_adds=True``.
+        Pods with DoNotSchedule spread are refused (KsimError,
+        KSIM_E_UNSUPPORTED)."""
         if nominated_node >= 0 and (nominated_status is None or
                                     nominated_status.code != UNSCHEDULABLE_AND_UNRESOLVABLE):
             if terminating_lower is not None and terminating_lower(nominated_node, priority):

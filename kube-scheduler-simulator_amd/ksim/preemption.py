@@ -13,12 +13,16 @@ from .encode import pod_requests
 from .model import Pod
 
 
-def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None) -> abi.BoundPods:
+def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None,
+                full_adds: bool = False) -> abi.BoundPods:
     """ksim_bound_pods for ``bound`` (pods whose node is in ``cluster``), in list order.
     With ``topo`` (the cluster's ksim.topology.TopologyIndex) the table also
     carries each row's host-port holdings (``topo.port_adds``, over the port
     classes registered so far: build it after the preemptor is encoded), which
-    the dry run of a pod with host ports reads (ksim_set_bound_pod_adds)."""
+    the dry run of a pod with host ports reads (ksim_set_bound_pod_adds).
+    ``full_adds``: every class the row counts into instead (``topo.adds``: its
+    carried terms, the selector classes it matches and its ports), which the dry
+    run of a pod with required pod (anti-)affinity reads."""
     pos = {n: i for i, n in enumerate(cluster.node_names)}
     rows = [p for p in bound if p.node_name in pos]
     node = np.array([pos[p.node_name] for p in rows], np.int32)
@@ -36,6 +40,6 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=
         return abi.BoundPods(node, prio, start, req)
     off, adds = [0], []
     for p in rows:
-        adds.extend(sorted(topo.port_adds(p).items()))
+        adds.extend(topo.adds(p) if full_adds else sorted(topo.port_adds(p).items()))
         off.append(len(adds))
     return abi.BoundPods(node, prio, start, req, np.array(off, np.int32), np.array(adds, np.int32).reshape(-1, 2))

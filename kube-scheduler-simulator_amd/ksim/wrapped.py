@@ -183,7 +183,10 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     ``backend`` is an Engine (or the oracle, whose preempt takes ``bound``).
     For a pod with host ports the table carries the bound pods' port holdings
     (``ksim.preemption.bound_table(cluster, pods, start, cluster.topo)``, built
-    after ``pods`` was compiled)."""
+    after ``pods`` was compiled); for a pod with required pod (anti-)affinity,
+    or one a bound pod's required anti-affinity term matches, every class they
+    count into (``full_adds=True``).  A pod with DoNotSchedule spread is refused
+    (KSIM_E_UNSUPPORTED)."""
     res = backend.eval_pod(pods, index) if hasattr(backend, "eval_pod") else backend.cycle(pods, index)
     nominated = -1
     post = [original_name(p.name) for p in prof.plugins["postFilter"].enabled]

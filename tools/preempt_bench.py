@@ -6,12 +6,18 @@ priorities and start times filling 9.6 CPUs, a 2-CPU preemptor of priority
 Engine.preempt: the pod's upload, the filter pass, the two preemption kernels
 and the result copies, ending synchronized.
 
+--anti: the same cluster spread over 50 zones, one pod of app=x in each zone
+(priority 10, on the zone's first node), and a preemptor with a required zone
+anti-affinity term against app=x: every node is a potential node (Fit fails
+first), each runs the domain form of the dry run, and the 50 holders' nodes are
+the candidates.  The table carries every row's class contributions.
+
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti]
 """
 import argparse
 import json
@@ -29,7 +35,9 @@ import numpy as np  # noqa: E402
 
 from ksim import abi, engine, profile  # noqa: E402
 from ksim.encode import encode_cluster, encode_pods  # noqa: E402
-from ksim.model import Container, Node, Pod  # noqa: E402
+from ksim.model import Container, LabelSelector, Node, Pod, PodAffinityTerm  # noqa: E402
+
+ZONE, N_ZONES = "topology.kubernetes.io/zone", 50
 
 
 def build(n_nodes: int):
@@ -54,6 +62,30 @@ def build(n_nodes: int):
     return cluster, table, enc, prof
 
 
+def build_anti(n_nodes: int):
+    """build()'s load on N_ZONES zones, an app=x pod per zone, the anti-affine preemptor."""
+    from ksim.preemption import bound_table
+    rng = np.random.default_rng(7)
+    nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}", ZONE: f"z{i % N_ZONES:02d}"},
+                  allocatable={"cpu": "10", "memory": "64Gi", "pods": "110"}) for i in range(n_nodes)]
+    bound, start = [], {}
+    for v in range(n_nodes):
+        for k in range(4):
+            holder = v < N_ZONES and k == 0
+            bound.append(Pod(f"b{v}-{k}", node_name=nodes[v].name, labels={"app": "x"} if holder else {},
+                             priority=10 if holder else int(rng.choice([0, 10, 100, 500])),
+                             containers=[Container({"cpu": "2400m"})]))
+            start[bound[-1].name] = int(rng.integers(0, 1000))
+    cluster, _ = encode_cluster(nodes, bound)
+    pod = Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})],
+              pod_anti_affinity_required=[PodAffinityTerm(ZONE, LabelSelector({"app": "x"}))])
+    enc = encode_pods(cluster, [pod])
+    assert int(enc.pods[0]["use_count"]) == 1 and int(enc.uses["kind"][0]) == abi.USE_IPA_ANTI
+    table = bound_table(cluster, bound, start, cluster.topo, full_adds=True)
+    prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
+    return cluster, table, enc, prof
+
+
 def pct(xs, q):
     xs = sorted(xs)
     return xs[min(len(xs) - 1, int(q * len(xs)))]
@@ -70,8 +102,9 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
     args = ap.parse_args()
-    cluster, table, enc, prof = build(args.nodes)
+    cluster, table, enc, prof = (build_anti if args.anti else build)(args.nodes)
     runs, every, result = [], [], None
     for _ in range(args.repeats):
         eng = engine.Engine(0)
@@ -88,7 +121,7 @@ def main():
         eng.close()
         runs.append(summary(us))
         every += us
-    print(json.dumps(dict(bench="preempt_use_free", library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
+    print(json.dumps(dict(bench="preempt_zone_anti" if args.anti else "preempt_use_free", library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
                           bound_pods=table.n, calls=args.calls, repeats=args.repeats,
                           nominated=result[0], victims=len(result[1]), potential=result[2], candidates=result[3],
                           runs=runs, **summary(every))))
