@@ -768,9 +768,13 @@ typedef struct ksim_preempt_out {
   int32_t nominated;          /* node position; -1: preemption cannot help */
   int32_t n_victims;          /* victims on the nominated node (may exceed victims_cap) */
   int32_t n_potential;        /* nodesWherePreemptionMightHelp */
-  int32_t n_candidates;       /* candidates the dry run kept (<= numCandidates) */
-  int32_t* victims;           /* [victims_cap] bound-pod indices, reprieve (importance) order */
-  int32_t victims_cap, _pad;
+  int32_t n_candidates;       /* candidates the dry run kept (see the cut below) */
+  int32_t* victims;           /* [victims_cap] bound-pod indices in the dry run's list order: the
+                               * victims violating a PodDisruptionBudget, then the others, each most
+                               * important first (without budgets: the importance order) */
+  int32_t victims_cap;
+  int32_t n_pdb_violations;   /* victims on the nominated node that violate a budget; 0 without a
+                               * node or without budgets.  Always written (it was padding before). */
 } ksim_preempt_out;
 
 /* Replace the bound-pod table (copied; the engine orders it per node by
@@ -789,6 +793,19 @@ int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b);
  * [0, n_classes).  Needed only before a dry run for a pod with such uses under
  * a profile that filters on NodePorts / InterPodAffinity. */
 int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds);
+/* The PodDisruptionBudgets over the bound pods of the last ksim_set_bound_pods
+ * (which drops any earlier ones), as a CSR over its rows in the caller's row
+ * order: ids[off[i] .. off[i + 1]) are the budgets row i matches (the caller
+ * applies the match rule: same namespace, a labelled pod, a non-empty selector
+ * that matches, the pod's name not in status.disruptedPods), off has n + 1
+ * entries and starts at 0, allowed[k] is budget k's status.disruptionsAllowed,
+ * taken as given for any int32.  Copied.  n_pdbs is bounded by int32 alone;
+ * n_pdbs = 0 clears the budgets (the other arguments are not read), which is
+ * the state after ksim_set_bound_pods.
+ * KSIM_E_INVALID: no table set, offsets not monotone or not starting at 0, an
+ * id outside [0, n_pdbs), an id twice in one row. */
+int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
+                            const int32_t* ids);
 /* DefaultPreemption's PostFilter for an unschedulable pod of `priority`
  * (default_preemption.go / preemption.go, v1.26) on the current snapshot,
  * without changing it.  It replaces the original plugin's PostFilter that the
@@ -801,14 +818,28 @@ int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class
  *                    topology key or no matching pod, and the other plugins
  *                    ahead of them return UnschedulableAndUnresolvable);
  *   dry run          SelectVictimsOnNode on each, in nodeTree order from
- *                    offset 0 (upstream draws a random offset), keeping the
- *                    first numCandidates = max(minCandidateNodesPercentage %
- *                    of them, minCandidateNodesAbsolute) candidates (the
- *                    profile's DefaultPreemptionArgs; 10 % and 100 default);
- *   selection        pickOneNodeForPreemption: lowest highest-victim
- *                    priority, lowest sum of (priority + 2^31), fewest
- *                    victims, latest earliest start among the highest-
- *                    priority victims, then the first candidate (no PDBs).
+ *                    offset 0 (upstream draws a random offset).  With budgets
+ *                    set (ksim_set_bound_pod_pdbs) the node's lower-priority
+ *                    pods are split as filterPodsWithPDBViolation does: most
+ *                    important first, from a fresh copy of every budget's
+ *                    disruptionsAllowed per node, each pod decrements every
+ *                    budget it matches and violates when one went below 0
+ *                    (pods of priority >= the preemptor's consume nothing).
+ *                    The violating pods are reprieved first, then the others;
+ *                    the victims list keeps that order and is not re-sorted;
+ *   the cut          numCandidates = max(minCandidateNodesPercentage % of the
+ *                    potential nodes, minCandidateNodesAbsolute) (the
+ *                    profile's DefaultPreemptionArgs; 10 % and 100 default).
+ *                    The scan stops once it holds numCandidates candidates and
+ *                    one without a PDB violation: a candidate is kept unless
+ *                    numCandidates candidates precede it and one of those has
+ *                    no violation.  Without budgets: the first numCandidates;
+ *   selection        pickOneNodeForPreemption over the kept ones: fewest PDB
+ *                    violations among the victims, lowest priority of the
+ *                    first victim of the list (under budgets not always the
+ *                    highest), lowest sum of (priority + 2^31), fewest
+ *                    victims, latest earliest start among the victims of the
+ *                    highest priority, then the first candidate.
  * The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity on each
  * potential node.
  * The pod's uses, by kind:
@@ -849,6 +880,7 @@ int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, in
  * contributions (ports, InterPodAffinity domain counts) on the node: pass 1 of
  * each trial; pass 2 is not re-run, which for required affinity means a node
  * whose only matching pod is nominated there can be a candidate.
+ * Nominated pods are no victims: a group consumes no PodDisruptionBudget.
  * n_groups = 0 is ksim_preempt. */
 int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                            const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,

@@ -1297,6 +1297,9 @@ func (n *NativeEncoder) Position(name string) (int, bool) {
 
 func (n *NativeEncoder) BoundPod(index int) *v1.Pod { return n.boundRows[index] }
 
+// BoundPodCount: the rows of the bound-pod table last sent (BoundTable).
+func (n *NativeEncoder) BoundPodCount() int { return len(n.boundRows) }
+
 // PreFilterNodeNames: NodeAffinity's PreFilterResult.NodeNames (nil: all
 // nodes; empty: conflicting terms), ksim/encode.py prefilter_node_names.
 func (n *NativeEncoder) PreFilterNodeNames(pod *v1.Pod) sets.String {

@@ -198,6 +198,22 @@ func (e *Engine) SetBoundPodAdds(off []int32, adds *C.ksim_class_add) error {
 	})
 }
 
+// SetBoundPodPDBs: the PodDisruptionBudgets over the last SetBoundPods' rows:
+// allowed[k] is budget k's status.disruptionsAllowed, ids[off[i]:off[i+1]] are
+// the budgets row i matches (off has one entry per row plus one and starts at
+// 0).  No budget clears them.  Copied by the engine.
+func (e *Engine) SetBoundPodPDBs(allowed, off, ids []int32) error {
+	ptr := func(s []int32) *C.int32_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.int32_t)(unsafe.Pointer(&s[0]))
+	}
+	return e.locked(func() C.int {
+		return C.ksim_set_bound_pod_pdbs(e.h, C.int32_t(len(allowed)), ptr(allowed), ptr(off), ptr(ids))
+	})
+}
+
 func (e *Engine) Preempt(ps *C.ksim_pod_set, idx int, priority int32, out *C.ksim_preempt_out) error {
 	return e.locked(func() C.int { return C.ksim_preempt(e.h, ps, C.int32_t(idx), C.int32_t(priority), out) })
 }

@@ -75,6 +75,8 @@ import (
 	"unsafe"
 
 	v1 "k8s.io/api/core/v1"
+	metav1 "k8s.io/apimachinery/pkg/apis/meta/v1"
+	"k8s.io/apimachinery/pkg/labels"
 	"k8s.io/apimachinery/pkg/util/sets"
 	utilfeature "k8s.io/apiserver/pkg/util/feature"
 	"k8s.io/client-go/tools/cache"
@@ -112,6 +114,8 @@ type Encoder interface {
 	// Priority and victims bookkeeping for DefaultPreemption: the bound-pod
 	// table row index -> pod (the table follows the snapshot, SetBoundPods).
 	BoundPod(index int) *v1.Pod
+	// BoundPodCount is the number of rows of that table.
+	BoundPodCount() int
 	// Pods encodes a list of pods into a set the caller owns (C memory) until
 	// release: the nominated pods of a first pass / dry run.
 	Pods(pods []*v1.Pod) (ps *C.ksim_pod_set, release func(), err error)
@@ -681,6 +685,44 @@ func (p *postFilter) PostFilter(ctx context.Context, state *framework.CycleState
 	if err := pr.Enc.BoundTable(pr.Engine); err != nil {
 		return nil, framework.AsStatus(err)
 	}
+	// 3) the PodDisruptionBudgets (getPodDisruptionBudgets, then the match rule
+	// of filterPodsWithPDBViolation per table row): a labelled pod, the same
+	// namespace, a non-empty selector that matches, the pod no key of
+	// status.disruptedPods.  The engine splits each node's victims by them,
+	// reprieves the violating ones first and ranks candidates by violations.
+	// Sent every cycle: a budget's status moves without any pod or node event.
+	pdbs, err := p.f.SharedInformerFactory().Policy().V1().PodDisruptionBudgets().Lister().List(labels.Everything())
+	if err != nil {
+		return nil, framework.AsStatus(err)
+	}
+	rows := pr.Enc.BoundPodCount()
+	allowed := make([]int32, len(pdbs))
+	sels := make([]labels.Selector, len(pdbs))
+	for k, b := range pdbs {
+		allowed[k] = b.Status.DisruptionsAllowed
+		if sel, err := metav1.LabelSelectorAsSelector(b.Spec.Selector); err == nil && !sel.Empty() {
+			sels[k] = sel
+		}
+	}
+	poff := make([]int32, rows+1)
+	var pids []int32
+	for i := 0; i < rows; i++ {
+		if q := pr.Enc.BoundPod(i); len(pdbs) > 0 && len(q.Labels) != 0 {
+			for k, b := range pdbs {
+				if b.Namespace != q.Namespace || sels[k] == nil || !sels[k].Matches(labels.Set(q.Labels)) {
+					continue
+				}
+				if _, gone := b.Status.DisruptedPods[q.Name]; gone {
+					continue
+				}
+				pids = append(pids, int32(k))
+			}
+		}
+		poff[i+1] = int32(len(pids))
+	}
+	if err := pr.Engine.SetBoundPodPDBs(allowed, poff, pids); err != nil {
+		return nil, framework.AsStatus(err)
+	}
 	victims := make([]int32, 1024)
 	var out C.ksim_preempt_out
 	out.victims = (*C.int32_t)(unsafe.Pointer(&victims[0]))
@@ -703,8 +745,9 @@ func (p *postFilter) PostFilter(ctx context.Context, state *framework.CycleState
 		return framework.NewPostFilterResultWithNominatedNode(""),
 			framework.NewStatus(framework.Unschedulable, "preemption: no candidate node")
 	}
-	// 5) prepareCandidate (PodDisruptionBudgets are out of the engine's scope,
-	// DESIGN.md §8): reject waiting victims, else patch the DisruptionTarget
+	// 5) prepareCandidate (out.victims is the dry run's list: the victims that
+	// violate a PodDisruptionBudget first, out.n_pdb_violations of them):
+	// reject waiting victims, else patch the DisruptionTarget
 	// condition (PodDisruptionConditions, beta in v1.26; upstream builds the
 	// new status from the preemptor's own status, restated as is) and delete
 	// with the default grace period; then clear the nominations of

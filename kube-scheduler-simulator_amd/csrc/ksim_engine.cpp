@@ -223,6 +223,7 @@ struct ksim_handle {
   std::vector<DevBuf> pre_bufs;
   std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
   std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
+  std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
   DevPreempt pre{};
   std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
   int32_t pre_n = 0;
@@ -2099,6 +2100,7 @@ void ksim_destroy(ksim_handle* h) {
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_nom_bufs);
   free_bufs(h->pre_add_bufs);
+  free_bufs(h->pre_pdb_bufs);
   if (h->d_chosen) (void)hipFree(h->d_chosen);
   if (h->st) (void)hipFree(h->st);
   if (h->d_prof) (void)hipFree(h->d_prof);
@@ -2293,6 +2295,7 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_nom_bufs);
   free_bufs(h->pre_add_bufs);
+  free_bufs(h->pre_pdb_bufs);
   h->pre = DevPreempt{};
   h->pre_index.clear();
   h->pre_n = 0;
@@ -4747,6 +4750,7 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
+  free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
   DevPreempt d{};
   void* p = nullptr;
   if ((rc = upload(h, h->pre_bufs, off.data(), 4 * off.size(), &p))) return rc;
@@ -4761,7 +4765,7 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   d.vflag = (uint8_t*)p;
   if ((rc = upload(h, h->pre_bufs, nullptr, sizeof(PreemptNode) * (size_t)N, &p))) return rc;
   d.res = (PreemptNode*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, 16, &p))) return rc;
+  if ((rc = upload(h, h->pre_bufs, nullptr, 32, &p))) return rc;
   d.pick = (int32_t*)p;
   if ((rc = upload(h, h->pre_bufs, nullptr, 4 * (size_t)std::max(N, 1), &p))) return rc;
   d.nslot = (int32_t*)p;
@@ -4807,6 +4811,51 @@ extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
   h->pre.aoff = (const int32_t*)po;
   h->pre.adds = (const ksim_class_add*)pa;
+  return KSIM_OK;
+}
+
+extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
+                                       const int32_t* ids) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ksim_set_bound_pods first");
+  if (n_pdbs < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: negative budget count");
+  const int32_t n = h->pre_n;
+  std::vector<int32_t> poff((size_t)n + 1, 0), perm;
+  if (n_pdbs > 0) {
+    if (!allowed || !off || off[0] != 0)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: bad offsets (they start at 0)");
+    for (int32_t i = 0; i < n; i++)
+      if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: offsets not monotone");
+    if (off[n] > 0 && !ids) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ids missing");
+    std::vector<int32_t> last((size_t)n_pdbs, -1);   // the last row that named the budget
+    for (int32_t i = 0; i < n; i++)
+      for (int32_t e = off[i]; e < off[i + 1]; e++) {
+        if (ids[e] < 0 || ids[e] >= n_pdbs)
+          return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: budget id out of range");
+        if (last[ids[e]] == i) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: a budget twice in one row");
+        last[ids[e]] = i;
+      }
+    // into the table's per-node importance order (CSR position k = caller row pre_index[k])
+    perm.reserve((size_t)off[n]);
+    for (int32_t k = 0; k < n; k++) {
+      const int32_t i = h->pre_index[k];
+      if (off[i + 1] > off[i]) perm.insert(perm.end(), ids + off[i], ids + off[i + 1]);
+      poff[(size_t)k + 1] = (int32_t)perm.size();
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  free_bufs(h->pre_pdb_bufs);                   // every dry run ends synchronized: nothing reads them
+  h->pre.poff = h->pre.pids = h->pre.pallowed = nullptr;
+  if (n_pdbs == 0) return KSIM_OK;              // cleared: the dry run takes the forms without budgets
+  int rc;
+  void *po = nullptr, *pi = nullptr, *pa = nullptr;
+  if ((rc = upload(h, h->pre_pdb_bufs, poff.data(), 4 * poff.size(), &po))) return rc;
+  if ((rc = upload(h, h->pre_pdb_bufs, perm.data(), 4 * perm.size(), &pi))) return rc;
+  if ((rc = upload(h, h->pre_pdb_bufs, allowed, 4 * (size_t)n_pdbs, &pa))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
+  h->pre.poff = (const int32_t*)po;
+  h->pre.pids = (const int32_t*)pi;
+  h->pre.pallowed = (const int32_t*)pa;
   return KSIM_OK;
 }
 
@@ -4958,22 +5007,25 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
     for (int32_t k = 0; k < n_groups; k++)
       HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &kNoGroup, 4, hipMemcpyHostToDevice, h->stream));
   }
-  int32_t pick[4];
+  int32_t pick[5];
   HIPCHK(h, hipMemcpyAsync(pick, h->pre.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   out->nominated = pick[0];
   out->n_victims = pick[1];
   out->n_potential = pick[2];
   out->n_candidates = pick[3];
+  out->n_pdb_violations = pick[4];
   if (pick[0] >= 0 && out->victims && out->victims_cap > 0) {
     std::vector<int32_t> off(2);
     HIPCHK(h, hcopy(h, off.data(), h->pre.off + pick[0], 8, hipMemcpyDeviceToHost));
     std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
     if (off[1] > off[0])
       HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
+    // the dry run's list order: the victims violating a PDB, then the others, each in CSR order
     int32_t k = 0;
-    for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
-      if (flag[j - off[0]]) out->victims[k++] = h->pre_index[j];
+    for (const uint8_t want : {(uint8_t)(1 | kPreemptViolating), (uint8_t)1})
+      for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
+        if (flag[j - off[0]] == want) out->victims[k++] = h->pre_index[j];
   }
   return KSIM_OK;
 }

@@ -242,18 +242,22 @@ void launch_fw_normalize(const LaunchArgs& a, int32_t slot, const int32_t* nodes
                          int64_t* out, hipStream_t stream);
 // DefaultPreemption dry run (ksim_preempt.hip): the bound pods per node in
 // importance order (CSR over nodes), per-node results, the pick.
+constexpr uint8_t kPreemptViolating = 2;                     // DevPreempt.vflag bit 1 (bit 0: victim)
 struct PreemptNode {
-  int32_t potential, cand, nv, high;   // potential node, candidate, victims, highest victim priority
+  // potential node; candidate (bit 0) and, above it, nviol: the victims that violate a PDB; victims;
+  // victims[0]'s priority
+  int32_t potential, cand, nv, high;
   int64_t sum, early;                  // sum of (priority + 2^31), earliest start of the highest-priority victims
+  __host__ __device__ int32_t nviol() const { return cand >> 1; }
 };
 struct DevPreempt {
   const int32_t* off;                  // [n + 1]
   const int32_t* prio;                 // [n_bound] CSR order
   const int64_t* start;                // [n_bound]
   const int64_t* req;                  // [n_bound][KSIM_PREEMPT_REQ]
-  uint8_t* vflag;                      // [n_bound] victim of its node's dry run
+  uint8_t* vflag;                      // [n_bound] bit 0: victim of its node's dry run, bit 1: violates a PDB there
   PreemptNode* res;                    // [n]
-  int32_t* pick;                       // [4] nominated, victims, potential, candidates
+  int32_t* pick;                       // [5] nominated, victims, potential, candidates kept, the node's PDB violations
   int32_t* nslot;                      // [n] nominated group of the node, -1: none
   const int64_t* nreq;                 // [groups][KSIM_PREEMPT_REQ + 1] requests, pod count
   // class contributions (ksim_set_bound_pod_adds; read only for a preemptor with NodePorts or
@@ -263,6 +267,10 @@ struct DevPreempt {
   const int32_t* goff;                 // [groups + 1] the same per nominated group
   const ksim_class_add* gadds;
   int64_t* afftot;                     // [KSIM_MAX_USES] cluster-wide totals of the preemptor's required-affinity uses
+  // PodDisruptionBudgets (ksim_set_bound_pod_pdbs; null: none, the dry run takes the forms without them)
+  const int32_t* poff;                 // [n_bound + 1] CSR order: pids[poff[j] .. poff[j + 1]) the budgets bound pod j matches
+  const int32_t* pids;
+  const int32_t* pallowed;             // [n_pdbs] status.disruptionsAllowed
 };
 // filter = false: s.fail already holds the statuses (ksim_preempt_nominated).
 // port_index / port_mask: NodePorts' place in the profile's filter list and

@@ -16,10 +16,13 @@
 // takes the domain form: the thread holds the node's TopoRow (the domain sum of
 // the node's topology value, or the node's own count, per use), moves it the
 // same way and re-runs interpodaffinity's Filter on it; a node that failed
-// InterPodAffinity for an anti-affinity reason is a potential node too.  One
-// block then keeps the first numCandidates
-// candidates in nodeTree order (upstream scans from a random offset; offset 0
-// here) and picks one by pickOneNodeForPreemption's criteria.
+// InterPodAffinity for an anti-affinity reason is a potential node too.  With
+// PodDisruptionBudgets on the table (ksim_set_bound_pod_pdbs) the thread first
+// splits the lower-priority pods as filterPodsWithPDBViolation does (the PDB
+// form, kernels of their own) and reprieves the violating ones first.  One
+// block then keeps candidates in nodeTree order (upstream scans from a random
+// offset; offset 0 here) until numCandidates were found and one of them has
+// no PDB violation, and picks one by pickOneNodeForPreemption's criteria.
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
@@ -101,7 +104,16 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
 // the node's TopoRow.  The node failed at Fit, NodePorts or InterPodAffinity;
 // the last is a potential node only for an anti-affinity reason, which the
 // thread re-derives from the row (with the nominated group on it: pass 1).
-template <bool PORTS, bool DOM = false>
+// PDB (the PDB form): the table carries budgets (pre.poff / pids / pallowed).
+// filterPodsWithPDBViolation walks the suffix most important first with a
+// fresh copy of every budget and decrements each budget a pod matches; the pod
+// violates when one of them went below zero, i.e. when the rows of [j0, j]
+// that carry the budget outnumber its disruptionsAllowed.  That count is taken
+// directly (quadratic in the node's victims, no per-thread array, no cap on
+// the number of budgets).  The violating rows are reprieved first, then the
+// others, so the victims list need not be sorted by priority: `high` is the
+// first victim appended, `early` follows the true maximum priority.
+template <bool PORTS, bool DOM = false, bool PDB = false>
 __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
                                                const ksim_pod& p, const PodPlan& plan, const ksim_topo_use* U,
                                                const DevPreempt& pre, int32_t node, int32_t prio, bool fit,
@@ -168,26 +180,56 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
   };
   if (!fails()) {
     out.cand = 1;
-    int32_t nv = 0, high = 0;
+    if (PDB) {                                          // filterPodsWithPDBViolation
+      for (int32_t j = j0; j < b; j++) {
+        bool viol = false;
+        for (int32_t e = pre.poff[j]; e < pre.poff[j + 1]; e++) {
+          const int32_t id = pre.pids[e];
+          int32_t used = 0;                             // rows of [j0, j] in budget id (j itself among them)
+          for (int32_t e2 = pre.poff[j0]; e2 < pre.poff[j + 1]; e2++) used += pre.pids[e2] == id;
+          if (used > pre.pallowed[id]) viol = true;
+        }
+        pre.vflag[j] = viol ? kPreemptViolating : 0;
+      }
+    }
+    int32_t nv = 0, nviol = 0, high = 0, top = INT32_MIN;
     int64_t sum = 0, early = INT64_MAX;
-    for (int32_t j = j0; j < b; j++) {                 // reprievePod, most important first
-      const int64_t* q = pre.req + (size_t)j * KSIM_PREEMPT_REQ;
-      row_add_req(r, q, 1, c.n_scalar);
-      if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
-      if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
-      const bool victim = fails();
-      pre.vflag[j] = victim;
-      if (victim) {
-        row_add_req(r, q, -1, c.n_scalar);
-        if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
-        if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
-        if (nv == 0) high = pre.prio[j];
-        sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
-        if (pre.prio[j] == high && pre.start[j] < early) early = pre.start[j];   // GetEarliestPodStartTime
-        nv++;
+    for (int pass = PDB ? 0 : 1; pass < 2; pass++) {     // the violating rows first, then the others
+      for (int32_t j = j0; j < b; j++) {                 // reprievePod, most important first
+        uint8_t mark = 0;
+        if (PDB) {
+          mark = pre.vflag[j] & kPreemptViolating;
+          if ((mark != 0) != (pass == 0)) continue;
+        }
+        const int64_t* q = pre.req + (size_t)j * KSIM_PREEMPT_REQ;
+        row_add_req(r, q, 1, c.n_scalar);
+        if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
+        if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
+        const bool victim = fails();
+        pre.vflag[j] = (uint8_t)victim | mark;
+        if (victim) {
+          row_add_req(r, q, -1, c.n_scalar);
+          if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+          if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+          if (nv == 0) high = pre.prio[j];
+          sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
+          if (PDB) {                                     // GetEarliestPodStartTime on an unsorted list
+            if (pre.prio[j] > top || nv == 0) {
+              top = pre.prio[j];
+              early = pre.start[j];
+            } else if (pre.prio[j] == top && pre.start[j] < early) {
+              early = pre.start[j];
+            }
+            if (mark) nviol++;
+          } else if (pre.prio[j] == high && pre.start[j] < early) {
+            early = pre.start[j];                        // sorted list: the first victim is the highest
+          }
+          nv++;
+        }
       }
     }
     out.nv = nv;
+    if (PDB) out.cand |= nviol << 1;
     out.high = nv ? high : INT32_MIN;
     out.sum = sum;
     out.early = early;
@@ -196,16 +238,19 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
   }
 }
 
-// Per node: SelectVictimsOnNode.  res[node] = {candidate, victims, highest
-// victim priority, sum of (priority + 2^31), earliest start among the
-// highest-priority victims}; vflag marks the victims (CSR order).  A potential
+// Per node: SelectVictimsOnNode.  res[node] = {potential, candidate (with the
+// PDB violations among the victims above bit 0), victims, the first victim's
+// priority, sum of (priority + 2^31), earliest start among the
+// highest-priority victims}; vflag marks the victims (bit 0) and, in the PDB
+// form, the violating rows (bit 1), in CSR order.  A potential
 // node failed NodeResourcesFit or, for a preemptor with port uses (port_mask),
 // NodePorts or, for one with required pod (anti-)affinity uses (dm),
 // InterPodAffinity with an anti-affinity detail: the filters that return
 // Unschedulable and that the dry run re-runs.  DOM: the domain form, a kernel
 // of its own, so a preemptor without such uses runs the code (and keeps the
-// registers) it had before that form existed.
-template <bool DOM>
+// registers) it had before that form existed.  PDB: the PDB form, likewise
+// kernels of their own, launched only when the table carries budgets.
+template <bool DOM, bool PDB>
 __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, const DevState* __restrict__ st,
                                                        DevScratch s, DevPreempt pre, int32_t fit_index,
                                                        int32_t prio, int32_t port_index, uint32_t port_mask,
@@ -220,17 +265,17 @@ __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, 
   if (DOM) {
     const bool at_ipa = f == (uint8_t)dm.ipa_index;
     if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa)
-      select_victims<false, true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
+      select_victims<false, true, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
                                   at_ipa, out);
   } else {
     const bool potential = (fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index);
     out.potential = potential;
     if (potential) {
       if (port_mask)                                   // kernel argument: one uniform branch
-        select_victims<true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
+        select_victims<true, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
                              false, out);
       else
-        select_victims<false>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, out);
+        select_victims<false, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, out);
     }
   }
   pre.res[node] = out;
@@ -269,6 +314,7 @@ __global__ __launch_bounds__(256) void k_preempt_totals(DevCluster c, DevPods P,
 __device__ __forceinline__ bool better(const PreemptNode& a, int32_t na, const PreemptNode& b, int32_t nb) {
   if (nb < 0) return na >= 0;
   if (na < 0) return false;
+  if (a.cand != b.cand) return a.cand < b.cand;         // fewest PDB violations (both are candidates)
   if (a.high != b.high) return a.high < b.high;
   if (a.sum != b.sum) return a.sum < b.sum;
   if (a.nv != b.nv) return a.nv < b.nv;
@@ -281,64 +327,71 @@ constexpr int kPickThreads = 1024;
 // min_pct / min_abs: DefaultPreemptionArgs (calculateNumCandidates)
 __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, DevPreempt pre, int32_t min_pct,
                                                                int32_t min_abs) {
-  __shared__ int32_t sh[kPickThreads / 64];
+  __shared__ int32_t sh[3][kPickThreads / 64];
   __shared__ PreemptNode s_best[kPickThreads];
   __shared__ int32_t s_node[kPickThreads];
+  __shared__ int32_t s_first;                            // rank of the first candidate without a PDB violation
   const int tid = threadIdx.x;
   const int32_t N = c.n, chunk = (N + kPickThreads - 1) / kPickThreads;
   const int32_t lo = min(N, tid * chunk), hi = min(N, lo + chunk);
-  int32_t npot = 0, ncand = 0;
+  int32_t npot = 0, ncand = 0, nclean = 0;
   for (int32_t x = lo; x < hi; x++) {
+    const int32_t cand = pre.res[x].cand;
     npot += pre.res[x].potential;
-    ncand += pre.res[x].cand;
+    ncand += cand & 1;
+    nclean += cand == 1;                                 // a candidate without a PDB violation
   }
-  // GetOffsetAndNumCandidates over the potential nodes; candidates are kept
-  // in nodeTree order until that many were found
-  int32_t total_pot, cexcl, total_cand;
+  if (tid == 0) s_first = -1;
+  // GetOffsetAndNumCandidates over the potential nodes; dryRunPreemption keeps
+  // candidates in nodeTree order until numCandidates were found and one of
+  // them has no PDB violation: candidate x is cut when at least `want`
+  // candidates precede it and one of those is clean.  Without PDBs every
+  // candidate is clean and the rule is rank < want.  One block scan of the
+  // three counts: the candidates and the clean ones before this thread's
+  // chunk, and the totals.
+  int32_t total_pot = 0, cexcl = 0, total_cand = 0, kexcl = 0;
   {
     const int lane = tid & 63, w = tid >> 6;
-    int32_t x = npot, y = ncand;
+    int32_t x = npot, y = ncand, z = nclean;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-      const int32_t a = __shfl_up(x, d, 64), b = __shfl_up(y, d, 64);
+      const int32_t a = __shfl_up(x, d, 64), b = __shfl_up(y, d, 64), e = __shfl_up(z, d, 64);
       if (lane >= d) {
         x += a;
         y += b;
+        z += e;
       }
     }
-    __syncthreads();
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    int32_t base = 0, tot = 0;
-    for (int i = 0; i < kPickThreads / 64; i++) {
-      if (i < w) base += sh[i];
-      tot += sh[i];
+    if (lane == 63) {
+      sh[0][w] = x;
+      sh[1][w] = y;
+      sh[2][w] = z;
     }
-    total_pot = tot;
     __syncthreads();
-    if (lane == 63) sh[w] = y;
-    __syncthreads();
-    base = 0;
-    tot = 0;
     for (int i = 0; i < kPickThreads / 64; i++) {
-      if (i < w) base += sh[i];
-      tot += sh[i];
+      total_pot += sh[0][i];
+      total_cand += sh[1][i];
+      if (i < w) {
+        cexcl += sh[1][i];
+        kexcl += sh[2][i];
+      }
     }
-    cexcl = base + y - ncand;
-    total_cand = tot;
+    cexcl += y - ncand;
+    kexcl += z - nclean;
   }
   int32_t want = total_pot * min_pct / 100;
   if (want < min_abs) want = min_abs;
   if (want > total_pot) want = total_pot;
   PreemptNode best{};
-  int32_t best_node = -1, rank = cexcl;
+  int32_t best_node = -1, rank = cexcl, clean = kexcl;
   for (int32_t x = lo; x < hi; x++) {
     const PreemptNode& r = pre.res[x];
     if (!r.cand) continue;
-    if (rank < want && better(r, x, best, best_node)) {
+    if ((rank < want || (want > 0 && clean == 0)) && better(r, x, best, best_node)) {
       best = r;
       best_node = x;
     }
+    if (r.cand == 1 && clean++ == 0) s_first = rank;    // one thread holds the first clean candidate
     rank++;
   }
   s_best[tid] = best;
@@ -352,10 +405,16 @@ __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, Dev
     __syncthreads();
   }
   if (tid == 0) {
+    // kept: the first `want` candidates, or up to the first clean one when that comes later
+    // (all of them when none is clean)
+    const int32_t upto = s_first < 0 ? total_cand : s_first + 1;
+    int32_t kept = want > upto ? want : upto;
+    if (kept > total_cand) kept = total_cand;
     pre.pick[0] = s_node[0];
     pre.pick[1] = s_node[0] >= 0 ? s_best[0].nv : 0;
     pre.pick[2] = total_pot;
-    pre.pick[3] = total_cand < want ? total_cand : want;
+    pre.pick[3] = want > 0 ? kept : 0;
+    pre.pick[4] = s_node[0] >= 0 ? s_best[0].nviol() : 0;
   }
 }
 
@@ -367,11 +426,11 @@ void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_inde
   if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
   if (ipa_index < 0) aff = anti = exist = 0;             // nor the InterPodAffinity uses without that filter
   const PreemptDom dm{aff, anti, exist, ipa_index};
+  const bool dom = (aff | anti | exist) != 0, pdb = pre.poff != nullptr;
   if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
-  if (aff | anti | exist)
-    k_preempt_nodes<true><<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
-  else
-    k_preempt_nodes<false><<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
+  auto nodes = dom ? (pdb ? k_preempt_nodes<true, true> : k_preempt_nodes<true, false>)
+                   : (pdb ? k_preempt_nodes<false, true> : k_preempt_nodes<false, false>);
+  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

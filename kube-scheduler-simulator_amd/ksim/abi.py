@@ -426,9 +426,12 @@ class BoundPods:
     ``adds_off`` / ``adds`` (optional, outside the C struct): the rows'
     count-class contributions as a CSR, ``adds`` = [[class, count], ...]
     (ksim_set_bound_pod_adds; the host-port holdings a dry run for a pod with
-    host ports reads)."""
+    host ports reads).  ``pdb_allowed`` / ``pdb_off`` / ``pdb_ids`` (optional,
+    likewise): the PodDisruptionBudgets' disruptionsAllowed and, as a CSR over
+    the rows, the budgets each row matches (ksim_set_bound_pod_pdbs)."""
 
-    def __init__(self, node, priority, start_time, req, adds_off=None, adds=None):
+    def __init__(self, node, priority, start_time, req, adds_off=None, adds=None, pdb_allowed=None, pdb_off=None,
+                 pdb_ids=None):
         self.node = np.ascontiguousarray(node, np.int32)
         self.priority = np.ascontiguousarray(priority, np.int32)
         self.start_time = np.ascontiguousarray(start_time, np.int64)
@@ -443,12 +446,21 @@ class BoundPods:
             self.adds = np.ascontiguousarray(np.asarray(adds, np.int32).reshape(-1, 2))   # ksim_class_add rows
             if self.adds_off.size != self.n + 1:
                 raise ValueError("adds_off has one entry per row plus one")
+        if len({pdb_allowed is None, pdb_off is None, pdb_ids is None}) != 1:
+            raise ValueError("pdb_allowed, pdb_off and pdb_ids go together")
+        self.pdb_allowed = self.pdb_off = self.pdb_ids = None
+        if pdb_allowed is not None:
+            self.pdb_allowed = np.ascontiguousarray(pdb_allowed, np.int32)
+            self.pdb_off = np.ascontiguousarray(pdb_off, np.int32)
+            self.pdb_ids = np.ascontiguousarray(pdb_ids, np.int32)
+            if self.pdb_off.size != self.n + 1:
+                raise ValueError("pdb_off has one entry per row plus one")
 
 
 class _PreemptOutC(ctypes.Structure):
     _fields_ = [("nominated", ctypes.c_int32), ("n_victims", ctypes.c_int32), ("n_potential", ctypes.c_int32),
                 ("n_candidates", ctypes.c_int32), ("victims", ctypes.c_void_p), ("victims_cap", ctypes.c_int32),
-                ("_pad", ctypes.c_int32)]
+                ("n_pdb_violations", ctypes.c_int32)]
 
 
 class PreemptOut:
@@ -459,6 +471,9 @@ class PreemptOut:
     def result(self) -> tuple:
         n = min(self.c.n_victims, self.c.victims_cap)
         return self.c.nominated, [int(v) for v in self.victims[:n]], self.c.n_potential, self.c.n_candidates
+
+    def result_with_pdb(self) -> tuple:
+        return self.result() + (self.c.n_pdb_violations,)
 
 
 def repo_root() -> str:

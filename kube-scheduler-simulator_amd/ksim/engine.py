@@ -29,7 +29,7 @@ EXPORTS = [
     "ksim_time_kernels", "ksim_kernel_name", "ksim_time_eval", "ksim_get_diag", "ksim_batch_geometry",
     "ksim_set_shard", "ksim_comm_unique_id", "ksim_comm_init", "ksim_group_schedule_loaded",
     "ksim_emit_cycle_json", "ksim_eval_pod_filter", "ksim_eval_pod_finish",
-    "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
+    "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_set_bound_pod_pdbs", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
@@ -105,6 +105,8 @@ def _load(path):
     L.ksim_set_bound_pods.argtypes = [vp, vp]
     if hasattr(L, "ksim_set_bound_pod_adds"):   # an addition within ABI 12: detected by symbol
         L.ksim_set_bound_pod_adds.argtypes = [vp, vp, vp]
+    if hasattr(L, "ksim_set_bound_pod_pdbs"):   # likewise
+        L.ksim_set_bound_pod_pdbs.argtypes = [vp, i32, vp, vp, vp]
     L.ksim_preempt.argtypes = [vp, vp, i32, i32, vp]
     L.ksim_preempt_nominated.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
@@ -388,6 +390,8 @@ class Engine:
         self._chk(self.L.ksim_set_bound_pods(self.h, ctypes.byref(bound.c)))
         if getattr(bound, "adds_off", None) is not None:
             self.set_bound_pod_adds(bound.adds_off, bound.adds)
+        if getattr(bound, "pdb_off", None) is not None:
+            self.set_bound_pod_pdbs(bound.pdb_allowed, bound.pdb_off, bound.pdb_ids)
 
     def set_bound_pod_adds(self, off, adds):
         """The count-class contributions of the last set_bound_pods' rows (CSR:
@@ -402,18 +406,35 @@ class Engine:
         self._chk(self.L.ksim_set_bound_pod_adds(self.h, off.ctypes.data_as(ctypes.c_void_p),
                                                  adds.ctypes.data_as(ctypes.c_void_p)))
 
-    def preempt(self, pods, index: int, priority: int, groups=None) -> tuple:
+    def set_bound_pod_pdbs(self, allowed, off, ids):
+        """The PodDisruptionBudgets over the last set_bound_pods' rows:
+        ``allowed`` [n_pdbs] disruptionsAllowed, and as a CSR (``off`` [n + 1],
+        ``ids``) the budgets each row matches (ksim_set_bound_pod_pdbs).  No
+        budget (``allowed`` empty) clears them."""
+        allowed = np.ascontiguousarray(allowed, np.int32)
+        off = np.ascontiguousarray(off, np.int32)
+        ids = np.ascontiguousarray(ids, np.int32)
+        n = getattr(self, "_bound_n", None)         # None: no table yet, the library refuses the call
+        if allowed.size and n is not None and off.size != n + 1:
+            raise ValueError("one offset per bound-pod row plus one")
+        self._chk(self.L.ksim_set_bound_pod_pdbs(self.h, int(allowed.size), *(a.ctypes.data_as(ctypes.c_void_p)
+                                                                              for a in (allowed, off, ids))))
+
+    def preempt(self, pods, index: int, priority: int, groups=None, with_pdb: bool = False) -> tuple:
         """DefaultPreemption PostFilter dry run: (nominated node or -1, victim
-        indices into the bound-pod table, potential nodes, candidates).
+        indices into the bound-pod table in the dry run's list order, potential
+        nodes, candidates kept); ``with_pdb`` appends the nominated node's
+        victims that violate a PodDisruptionBudget (n_pdb_violations).
         ``groups`` = [(node, [indices of ``pods``]), ...]: the PodNominator's
         pods of priority >= ``priority`` per node (ksim_preempt_nominated)."""
         self._sync()
         self._ran = True
         out = abi.PreemptOut(max(getattr(self, "_bound_n", 1), 1))
+        result = out.result_with_pdb if with_pdb else out.result
         ps = pods.pod_set()
         if not groups:
             self._chk(self.L.ksim_preempt(self.h, ctypes.byref(ps), index, priority, ctypes.byref(out.c)))
-            return out.result()
+            return result()
         nodes, first, count, order = _nominated_groups(groups)
         sub = pods.subset_indices(order)      # kept alive: the pod set points into it
         nps = sub.pod_set()
@@ -421,7 +442,7 @@ class Engine:
                                                 len(nodes), *(a.ctypes.data_as(ctypes.c_void_p)
                                                               for a in (nodes, first, count)),
                                                 ctypes.byref(out.c)))
-        return out.result()
+        return result()
 
     def match_terms(self, mp: abi.MatchProblem, n_words: int, counts: Optional[np.ndarray]) -> np.ndarray:
         """ksim_match_terms: [n_sigs][n_words] matcher bits; ``counts``

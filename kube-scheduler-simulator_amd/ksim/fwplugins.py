@@ -216,7 +216,7 @@ class EnginePlugins:
             self.b.forget(a[0], a[1], a[2])
 
     def post_filter(self, priority: int, bound=None, nominated_node: int = -1, nominated_status=None,
-                    terminating_lower=None) -> Tuple[Status, int, List[int], bool]:
+                    terminating_lower=None, pdbs=None) -> Tuple[Status, int, List[int], bool]:
         """DefaultPreemption.PostFilter (default_preemption.go v1.26):
         PodEligibleToPreemptOthers, then the dry run over this cycle's
         nominated groups.  Returns (status, nominated node or -1, victim
@@ -231,12 +231,16 @@ class EnginePlugins:
         bound pod's required anti-affinity term matches, needs every class
         the bound pods count into: the same call with ``full_adds=True``.
         Pods with DoNotSchedule spread are refused (KsimError,
-        KSIM_E_UNSUPPORTED)."""
+        KSIM_E_UNSUPPORTED).  ``pdbs``: (allowed, off, ids), the
+        PodDisruptionBudgets over the table's rows, set on the engine before
+        the dry run (Engine.set_bound_pod_pdbs)."""
         if nominated_node >= 0 and (nominated_status is None or
                                     nominated_status.code != UNSCHEDULABLE_AND_UNRESOLVABLE):
             if terminating_lower is not None and terminating_lower(nominated_node, priority):
                 return (Status(UNSCHEDULABLE, "preemption: not eligible due to a terminating pod on the "
                                               "nominated node."), -1, [], False)
+        if pdbs is not None:
+            self.b.set_bound_pod_pdbs(*pdbs)
         if bound is None:
             node, victims = self.b.preempt(self._pods, self._idx, priority, groups=self._groups)[:2]
         else:

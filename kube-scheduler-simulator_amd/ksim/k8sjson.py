@@ -7,7 +7,8 @@ reference's scheduler reads (golden vectors item 4).
 """
 from typing import Dict, List, Optional
 
-from .model import (Container, LabelSelector, Node, NodeSelectorTerm, Pod, PodAffinityTerm, Requirement,
+from .model import (Container, LabelSelector, Node, NodeSelectorTerm, Pod, PodAffinityTerm, PodDisruptionBudget,
+                    Requirement,
                     TopologySpreadConstraint, WeightedPodAffinityTerm)
 
 
@@ -164,3 +165,17 @@ def nodes_to_list(nodes: List[Node]) -> List[dict]:
 
 def pods_to_list(pods: List[Pod]) -> List[dict]:
     return [pod_to_dict(p) for p in pods]
+
+
+def pdb_from_dict(d: dict) -> PodDisruptionBudget:
+    """A policy/v1 PodDisruptionBudget document: metadata, spec.selector (absent
+    or null: nil) and status.disruptionsAllowed / disruptedPods (absent: 0 and
+    none, as with no disruption controller running)."""
+    md, spec, status = d.get("metadata") or {}, d.get("spec") or {}, d.get("status") or {}
+    sel = spec.get("selector")
+    if sel is not None:
+        sel = LabelSelector(dict(sel.get("matchLabels") or {}),
+                            [Requirement(r["key"], r["operator"], list(r.get("values") or []))
+                             for r in (sel.get("matchExpressions") or [])])
+    return PodDisruptionBudget(md.get("name", ""), md.get("namespace", "default") or "default", sel,
+                               int(status.get("disruptionsAllowed") or 0), tuple(status.get("disruptedPods") or {}))

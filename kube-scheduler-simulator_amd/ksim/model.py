@@ -455,6 +455,18 @@ class Controller:
     selector: object = None
 
 
+@dataclass
+class PodDisruptionBudget:
+    """policy/v1 PodDisruptionBudget as DefaultPreemption reads it
+    (filterPodsWithPDBViolation): the selector (nil or empty matches no pod
+    there), status.disruptionsAllowed and the keys of status.disruptedPods."""
+    name: str
+    namespace: str = "default"
+    selector: Optional[LabelSelector] = None
+    disruptions_allowed: int = 0
+    disrupted_pods: Tuple[str, ...] = ()
+
+
 def service_from_dict(d: dict) -> Service:
     md, spec = d.get("metadata", {}) or {}, d.get("spec", {}) or {}
     sel = spec.get("selector")

@@ -4,17 +4,35 @@ in a snapshot.  Requests follow NodeInfo's Requested (the same
 computePodResourceRequest the encoder uses)."""
 from __future__ import annotations
 
-from typing import Dict, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from . import abi
 from .encode import pod_requests
-from .model import Pod
+from .model import Pod, PodDisruptionBudget
+
+
+def pdb_matches(rows: Sequence[Pod], pdbs: Sequence[PodDisruptionBudget]) -> List[List[int]]:
+    """Per pod of ``rows`` the positions in ``pdbs`` of the budgets that match it,
+    ascending (filterPodsWithPDBViolation, v1.26): the pod has at least one
+    label, the namespaces are equal, the selector is non-nil, non-empty and
+    matches the labels, and the pod's name is no key of status.disruptedPods."""
+    out = []
+    for p in rows:
+        hit = []
+        if p.labels:
+            for k, b in enumerate(pdbs):
+                if b.namespace != p.namespace or b.selector is None or b.selector.empty():
+                    continue
+                if b.selector.matches(p.labels) and p.name not in b.disrupted_pods:
+                    hit.append(k)
+        out.append(hit)
+    return out
 
 
 def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None,
-                full_adds: bool = False) -> abi.BoundPods:
+                full_adds: bool = False, pdbs: Optional[Sequence[PodDisruptionBudget]] = None) -> abi.BoundPods:
     """ksim_bound_pods for ``bound`` (pods whose node is in ``cluster``), in list order.
     With ``topo`` (the cluster's ksim.topology.TopologyIndex) the table also
     carries each row's host-port holdings (``topo.port_adds``, over the port
@@ -22,7 +40,10 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=
     the dry run of a pod with host ports reads (ksim_set_bound_pod_adds).
     ``full_adds``: every class the row counts into instead (``topo.adds``: its
     carried terms, the selector classes it matches and its ports), which the dry
-    run of a pod with required pod (anti-)affinity reads."""
+    run of a pod with required pod (anti-)affinity reads.
+    ``pdbs``: the cluster's PodDisruptionBudgets; the table then carries their
+    disruptionsAllowed and the budgets each row matches (``pdb_matches``;
+    ksim_set_bound_pod_pdbs).  None or empty: no budgets."""
     pos = {n: i for i, n in enumerate(cluster.node_names)}
     rows = [p for p in bound if p.node_name in pos]
     node = np.array([pos[p.node_name] for p in rows], np.int32)
@@ -36,10 +57,17 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=
         req[i, 2] = r.get("ephemeral-storage", 0)
         for k, name in enumerate(cluster.scalar_names):
             req[i, 3 + k] = r.get(name, 0)
+    budgets = {}
+    if pdbs:
+        hits = pdb_matches(rows, pdbs)
+        budgets = dict(pdb_allowed=np.array([b.disruptions_allowed for b in pdbs], np.int32),
+                       pdb_off=np.cumsum([0] + [len(h) for h in hits]).astype(np.int32),
+                       pdb_ids=np.array([k for h in hits for k in h], np.int32))
     if topo is None:
-        return abi.BoundPods(node, prio, start, req)
+        return abi.BoundPods(node, prio, start, req, **budgets)
     off, adds = [0], []
     for p in rows:
         adds.extend(topo.adds(p) if full_adds else sorted(topo.port_adds(p).items()))
         off.append(len(adds))
-    return abi.BoundPods(node, prio, start, req, np.array(off, np.int32), np.array(adds, np.int32).reshape(-1, 2))
+    return abi.BoundPods(node, prio, start, req, np.array(off, np.int32), np.array(adds, np.int32).reshape(-1, 2),
+                         **budgets)

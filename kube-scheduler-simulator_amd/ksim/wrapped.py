@@ -175,7 +175,7 @@ def record_cycle(store: Store, cluster: EncodedCluster, prof: SchedulerProfile, 
 
 
 def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: SchedulerProfile, pods, index: int,
-                 priority: int = 0, bound=None) -> Dict:
+                 priority: int = 0, bound=None, pdbs=None) -> Dict:
     """One deterministic compat cycle as the wrapped plugins see it: the cycle
     (ksim_eval_pod), then for an unschedulable pod DefaultPreemption's
     PostFilter dry run (ksim_preempt over the bound-pod table set with
@@ -193,6 +193,8 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     if res["status"] == abi.STATUS_UNSCHEDULABLE and "DefaultPreemption" in post and pods.rejection(index) is None:
         names = pods.prefilter_names[index] if pods.prefilter_names else None
         if not (names is not None and len(names) == 0):
+            if pdbs is not None:
+                backend.set_bound_pod_pdbs(*pdbs)
             out = backend.preempt(pods, index, priority) if bound is None else \
                 backend.preempt(pods, index, priority, bound)
             nominated = int(out[0])

@@ -12,12 +12,17 @@ anti-affinity term against app=x: every node is a potential node (Fit fails
 first), each runs the domain form of the dry run, and the 50 holders' nodes are
 the candidates.  The table carries every row's class contributions.
 
+--pdbs K: K PodDisruptionBudgets with disruptionsAllowed 1 over the table,
+the bound pods of node v in budget v % K (ksim_set_bound_pod_pdbs), so all but
+the most important lower-priority pod of a node violate: the call takes the
+PDB form of the kernels.  With --anti too.
+
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti] [--pdbs K]
 """
 import argparse
 import json
@@ -103,16 +108,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
+    ap.add_argument("--pdbs", type=int, default=0, help="this many budgets (disruptionsAllowed 1), each bound pod in one")
     args = ap.parse_args()
     cluster, table, enc, prof = (build_anti if args.anti else build)(args.nodes)
+    budgets = None
+    if args.pdbs > 0:
+        budgets = (np.ones(args.pdbs, np.int32), np.arange(table.n + 1, dtype=np.int32),
+                   (np.asarray(table.node) % args.pdbs).astype(np.int32))
     runs, every, result = [], [], None
     for _ in range(args.repeats):
         eng = engine.Engine(0)
         eng.set_profile(prof)
         eng.set_cluster(cluster)
         eng.set_bound_pods(table)
+        if budgets is not None:
+            eng.set_bound_pod_pdbs(*budgets)
         for _ in range(args.warmup):
-            result = eng.preempt(enc, 0, 1000)
+            result = eng.preempt(enc, 0, 1000, with_pdb=True) if budgets is not None else eng.preempt(enc, 0, 1000)
         us = []
         for _ in range(args.calls):
             t0 = time.perf_counter()
@@ -121,10 +133,12 @@ def main():
         eng.close()
         runs.append(summary(us))
         every += us
-    print(json.dumps(dict(bench="preempt_zone_anti" if args.anti else "preempt_use_free", library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
+    name = ("preempt_zone_anti" if args.anti else "preempt_use_free") + ("_pdb" if budgets is not None else "")
+    extra = dict(pdbs=args.pdbs, pdb_violations=result[4]) if budgets is not None else {}
+    print(json.dumps(dict(bench=name, library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
                           bound_pods=table.n, calls=args.calls, repeats=args.repeats,
                           nominated=result[0], victims=len(result[1]), potential=result[2], candidates=result[3],
-                          runs=runs, **summary(every))))
+                          runs=runs, **extra, **summary(every))))
 
 
 if __name__ == "__main__":
