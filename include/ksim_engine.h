@@ -741,9 +741,14 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * bits 16..21 k_batch_top -- static-class default-shape KEEP, static-class
  * default-shape, static-class, FAST default-shape, FAST, generic keys --
  * bits 24..26 the packed sweep's k_sweep_top_commit -- default-shape, generic,
+ * flush -- bits 27..28 k_batch_top_commit with the request-class table and its
  * flush);
  * out[26] topology batch pods committed on a zone variant (their batch moved
- * their DoNotSchedule domain verdicts; ksim_tbatch.hip TbVar), cumulative.
+ * their DoNotSchedule domain verdicts; ksim_tbatch.hip TbVar), cumulative;
+ * out[27] batch runs of this handle that took the request-class table (the
+ * pods of a loaded queue that share their resource requests share a class,
+ * and a long enough P100 run reads each class's verdict and scores per node
+ * from a table instead of computing them per pod), since ksim_create.
  * Returns the number of values written (<= n). */
 int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n);
 /* Batch-path geometry compiled into the library: out[0] pods per batch (B),

@@ -813,11 +813,6 @@ __device__ __forceinline__ uint32_t lazy_hash(int32_t node) {
   return ((uint32_t)node * 2654435761u) >> (32 - kLazyHashBits);
 }
 
-// the request fields a FAST pod's key reads
-struct PodReq {
-  int64_t cpu, mem, eph, nzc, nzm;
-};
-
 // DEF: the FAST key with the default profile's shape compiled in (fast_def).
 // KEEP: the local node range is at most kKeepPerLane * 1024 nodes, so every
 // lane keeps all of its keys (no insertion network; top_finish unsorted).
@@ -839,18 +834,41 @@ __device__ __forceinline__ int64_t uni64(int64_t x) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// RT upkeep: a row the block materializes, whole (S_i's dynamic columns and
+// the node's static ones), for the threads that key every class on it
+struct UpRow {
+  ResCols s;
+  int64_t alloc_cpu, alloc_mem, alloc_eph;
+  double inv_cpu, inv_mem;
+  int32_t alloc_pods, node;                        // node -1: no row
+};
+
 // The launch's body (k_batch_top_commit, and the packed sweep's
 // k_sweep_top_commit with a lane's buffers).
-template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS>
+// RT (KEEP, DEF, DIRECT; ksim_internal.h ReqTab): the block's pod takes its
+// verdicts and scores from its request class's row of T[p ^ 1], one 2-byte
+// load per node, and only the tie-break hash is computed per pair.  The nodes
+// batch i-1 bound are stale there (their binds are in the overlay alone):
+// thread t keys entry t's node for the block's class with the full arithmetic
+// into s_patch[t], and the main pass selects by s_ent.  Where the block
+// writes S_i's rows into X[p] it writes every class's entry of them into T[p].
+template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS, bool RT = false>
 __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const DevPods& P,
                                                       const ksim_profile* __restrict__ prof_p,
                                                       const BatchProg* __restrict__ bp_p, const LazyStep& L,
                                                       uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,
                                                       int32_t* __restrict__ topk_complete,
                                                       int32_t* __restrict__ chosen_out,
-                                                      uint64_t* __restrict__ xsend) {
+                                                      uint64_t* __restrict__ xsend, const ReqTab& rt = ReqTab{}) {
   constexpr int kThreads = 1024;
   static_assert(kThreads >= kBatchPods, "one thread per batch entry");
+  static_assert(!RT || (DIRECT && !NS && (FLUSH || (DEF && KEEP))), "the table form is the KEEP / DEF / DIRECT launch");
+  static_assert(2 * kReqMaxClasses <= kThreads, "upkeep: one thread per (class, row)");
+  // RT: the candidate pods' classes (as s_pc), the patch entries (as s_rq) and
+  // the two rows the block materializes (upkeep)
+  __shared__ uint16_t s_cls[RT ? kBatchPods + 1 : 1];
+  __shared__ uint16_t s_patch[RT ? kBatchPods + 1 : 1];   // (entry kBatchPods: never selected)
+  __shared__ UpRow s_up[RT ? 2 : 1];
   // s_rq: batch i-1's pod requests, then each bound node's delta; entry
   // kBatchPods stays zero (DIRECT: the entry of every node batch i-1 did not bind)
   __shared__ ResCols s_rq[kBatchPods + 1];
@@ -893,6 +911,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
         rq = ResCols{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem, 1};
       } else {
         s_pc[x - kBatchPods] = PodReq{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem};
+        if constexpr (RT && !FLUSH) s_cls[x - kBatchPods] = rt.rcls[q];
       }
     }
   }
@@ -912,6 +931,30 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     s_sched = 0;
     s_unsched = 0;
     s_rq[kBatchPods] = ResCols{0, 0, 0, 0, 0, 0};
+  }
+  // RT: the row of this thread's entry of batch i-1 (patched below if it is
+  // bound) and the class request of this thread's upkeep; neither depends on
+  // the cut.  Issued once g1 is here, with clamped indices and no lane
+  // predicate, so that the waits further down count them exactly and they
+  // stay in flight across the cut's barriers.
+  NodeRow prow{};
+  double pic = 0, pim = 0;
+  PodReq creq{0, 0, 0, 0, 0};
+  if constexpr (RT) {
+    if constexpr (!FLUSH) {
+      // m1 is waited for here, before the branch: past it the wait could no
+      // longer leave the row loads in flight (a wait after a branch counts the
+      // path that issued fewest)
+      asm volatile("" : : "v"(m1), "v"(g1));
+      if (tid < kBatchPods) {                       // whole waves
+        const int32_t gn = (tid < e1 && g1) ? key_node(g1) - c.base : 0;   // tid < e1: the slot holds batch i-1's guesses
+        prow = load_res_row_off(c, gn);
+        pic = ld_off(c.inv_cpu, (uint32_t)gn << 3);
+        pim = ld_off(c.inv_mem, (uint32_t)gn << 3);
+      }
+    }
+    const int32_t t = tid < 64 ? 0 : tid - 64;      // upkeep thread 64 + t: row t / C, class t % C
+    creq = rt.rreq[t < 2 * rt.n_cls ? (t < rt.n_cls ? t : t - rt.n_cls) : 0];
   }
   lds_barrier();
 #ifdef KSIM_TC_CLOCKS
@@ -935,6 +978,17 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   tp[2] = __builtin_amdgcn_s_memrealtime();
 #endif
   const int32_t inode = s_inode;
+  // RT: the lane's entries of its class's row, all loaded before the first use
+  uint32_t te[kKeepPerLane];
+  if constexpr (RT && !FLUSH) {
+    const int32_t cls = live ? (int32_t)s_cls[committed] : 0;
+    const uint16_t* __restrict__ trow = rt.t_in + (size_t)cls * (size_t)c.n;
+#pragma unroll
+    for (int q = 0; q < kKeepPerLane; q++) {
+      const int32_t node = c.eval_lo + tid + q * kThreads;
+      te[q] = trow[node < c.eval_hi ? node : c.eval_lo];   // clamped, not predicated (a past-the-end lane's is unused)
+    }
+  }
   // entry tid < i*: its guessed node takes pod tid, and pod i* when i* chose it
   const int32_t gnode = (tid < istar && g1) ? key_node(g1) - c.base : -1;
   if (gnode >= 0) {
@@ -949,6 +1003,24 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
       d.pods += 1;
     }
     s_rq[tid] = d;
+    if constexpr (RT && !FLUSH) {
+      if (live) {                                 // the bound node's entry for the block's class
+        const PodReq x = s_pc[committed];
+        ksim_pod pq;
+        pq.req_cpu = x.cpu;
+        pq.req_mem = x.mem;
+        pq.req_eph = x.eph;
+        pq.nz_cpu = x.nzc;
+        pq.nz_mem = x.nzm;
+        prow.req_cpu += d.cpu;
+        prow.req_mem += d.mem;
+        prow.req_eph += d.eph;
+        prow.nz_cpu += d.nzc;
+        prow.nz_mem += d.nzm;
+        prow.num_pods += d.pods;
+        s_patch[tid] = (uint16_t)req_entry(fast_prog(*bp_p), pq, prow, pic, pim);
+      }
+    }
     if constexpr (DIRECT) {
       s_ent[gnode] = (int16_t)tid;                // guessed nodes are distinct
     } else {
@@ -965,11 +1037,26 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   // this block's two rows to materialize, loaded ahead of the node loop
   int32_t mn0 = -1, mn1 = -1;
   ResCols mr0{0, 0, 0, 0, 0, 0}, mr1{0, 0, 0, 0, 0, 0};
+  UpRow ms[RT ? 2 : 1];
   if (tid == b) {
     if (b < nchain && g1) mn0 = key_node(g1) - c.base;
     if (b < e2 && g2) mn1 = key_node(g2) - c.base;   // thread b holds g2[b]
     if (mn0 >= 0) mr0 = ResCols{c.req_cpu[mn0], c.req_mem[mn0], c.req_eph[mn0], c.nz_cpu[mn0], c.nz_mem[mn0], c.num_pods[mn0]};
     if (mn1 >= 0) mr1 = ResCols{c.req_cpu[mn1], c.req_mem[mn1], c.req_eph[mn1], c.nz_cpu[mn1], c.nz_mem[mn1], c.num_pods[mn1]};
+    if constexpr (RT) {                            // their static columns too (in registers until materialize())
+      const int32_t mn[2] = {mn0, mn1};
+#pragma unroll
+      for (int w = 0; w < 2; w++) {
+        const int32_t n = mn[w] >= 0 ? mn[w] : 0;
+        ms[w].alloc_cpu = c.alloc_cpu[n];
+        ms[w].alloc_mem = c.alloc_mem[n];
+        ms[w].alloc_eph = c.alloc_eph[n];
+        ms[w].inv_cpu = c.inv_cpu[n];
+        ms[w].inv_mem = c.inv_mem[n];
+        ms[w].alloc_pods = c.alloc_pods[n];
+        ms[w].node = mn[w];
+      }
+    }
   }
   lds_barrier();
   // st[p] = st[p ^ 1] with the commit's updates, written whole by one thread
@@ -1015,29 +1102,65 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
       return d;
     }
   };
+  auto write_row = [&](int32_t mn, const ResCols& mr, int which) {
+    ResCols s = mr;
+    if (mn >= 0) {
+      const ResCols d = delta(mn);
+      s = ResCols{mr.cpu + d.cpu, mr.mem + d.mem, mr.eph + d.eph, mr.nzc + d.nzc, mr.nzm + d.nzm, mr.pods + d.pods};
+      L.w.req_cpu[mn] = s.cpu;
+      L.w.req_mem[mn] = s.mem;
+      L.w.req_eph[mn] = s.eph;
+      L.w.nz_cpu[mn] = s.nzc;
+      L.w.nz_mem[mn] = s.nzm;
+      L.w.num_pods[mn] = s.pods;
+    }
+    if constexpr (RT) {
+      ms[which].s = s;
+      s_up[which] = ms[which];
+    }
+  };
   auto materialize = [&]() {
     if (tid != b) return;
-    if (mn0 >= 0) {
-      const ResCols d = delta(mn0);
-      L.w.req_cpu[mn0] = mr0.cpu + d.cpu;
-      L.w.req_mem[mn0] = mr0.mem + d.mem;
-      L.w.req_eph[mn0] = mr0.eph + d.eph;
-      L.w.nz_cpu[mn0] = mr0.nzc + d.nzc;
-      L.w.nz_mem[mn0] = mr0.nzm + d.nzm;
-      L.w.num_pods[mn0] = mr0.pods + d.pods;
-    }
-    if (mn1 >= 0) {
-      const ResCols d = delta(mn1);
-      L.w.req_cpu[mn1] = mr1.cpu + d.cpu;
-      L.w.req_mem[mn1] = mr1.mem + d.mem;
-      L.w.req_eph[mn1] = mr1.eph + d.eph;
-      L.w.nz_cpu[mn1] = mr1.nzc + d.nzc;
-      L.w.nz_mem[mn1] = mr1.nzm + d.nzm;
-      L.w.num_pods[mn1] = mr1.pods + d.pods;
+    write_row(mn0, mr0, 0);
+    write_row(mn1, mr1, 1);
+  };
+  // RT, after a barrier that follows materialize(): every class's entry of the
+  // two rows into T[p].  Thread 64 + t keys row t / C for class t % C (wave 0
+  // is left to the top-T merge); rows that are equal carry equal entries.
+  auto upkeep = [&]() {
+    if constexpr (RT) {
+      const int32_t t = tid - 64;
+      if (t < 0 || t >= 2 * rt.n_cls) return;
+      const UpRow& u = s_up[t < rt.n_cls ? 0 : 1];
+      const int32_t mn = u.node;
+      if (mn < 0) return;
+      NodeRow r;
+      r.alloc_cpu = u.alloc_cpu;
+      r.alloc_mem = u.alloc_mem;
+      r.alloc_eph = u.alloc_eph;
+      r.alloc_pods = u.alloc_pods;
+      r.req_cpu = u.s.cpu;
+      r.req_mem = u.s.mem;
+      r.req_eph = u.s.eph;
+      r.nz_cpu = u.s.nzc;
+      r.nz_mem = u.s.nzm;
+      r.num_pods = u.s.pods;
+      ksim_pod pq;
+      pq.req_cpu = creq.cpu;
+      pq.req_mem = creq.mem;
+      pq.req_eph = creq.eph;
+      pq.nz_cpu = creq.nzc;
+      pq.nz_mem = creq.nzm;
+      const int32_t k = t < rt.n_cls ? t : t - rt.n_cls;
+      rt.t_out[(size_t)k * (size_t)c.n + mn] = (uint16_t)req_entry(fast_prog(*bp_p), pq, r, u.inv_cpu, u.inv_mem);
     }
   };
   if (!live) {
     materialize();
+    if constexpr (RT) {
+      lds_barrier();
+      upkeep();
+    }
     if (st_writer) update_state();
     return;
   }
@@ -1160,7 +1283,16 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     for (int q = 0; q < kKeepPerLane; q++) {
       if (c.eval_lo + q * kThreads >= c.eval_hi) break;   // block-uniform
       const int32_t node = c.eval_lo + tid + q * kThreads;
-      const uint64_t k = node < c.eval_hi ? key_of(node) : 0;
+      uint64_t k = 0;
+      if constexpr (RT) {
+        if (node < c.eval_hi) {
+          const int32_t ent = s_ent[node];
+          const uint32_t e = ent == kBatchPods ? te[q] : (uint32_t)s_patch[ent];
+          k = req_entry_key(bq, e, hseed, c.base + node);
+        }
+      } else {
+        k = node < c.eval_hi ? key_of(node) : 0;
+      }
       nfeas += k != 0;
       ak[q] = k;
     }
@@ -1205,20 +1337,21 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   else
     top_finish<kThreads>(a, nfeas, b, topk, topk_cnt, topk_complete, xsend);
 #endif
+  upkeep();                                   // (top_finish's barriers follow materialize())
   if (st_writer) update_state();              // waves past the first return from the merge early
   }
 }
 
-template <bool FLUSH, bool DIRECT, bool DEF = false, bool KEEP = false, bool NS = false>
+template <bool FLUSH, bool DIRECT, bool DEF = false, bool KEEP = false, bool NS = false, bool RT = false>
 __global__ __launch_bounds__(1024) void k_batch_top_commit(DevCluster c, DevPods P,
                                                            const ksim_profile* __restrict__ prof_p,
                                                            const BatchProg* __restrict__ bp_p, LazyStep L,
                                                            uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,
                                                            int32_t* __restrict__ topk_complete,
                                                            int32_t* __restrict__ chosen_out,
-                                                           uint64_t* __restrict__ xsend) {
-  batch_top_commit_body<FLUSH, DIRECT, DEF, KEEP, NS>(c, P, prof_p, bp_p, L, topk, topk_cnt, topk_complete, chosen_out,
-                                                      xsend);
+                                                           uint64_t* __restrict__ xsend, ReqTab rt) {
+  batch_top_commit_body<FLUSH, DIRECT, DEF, KEEP, NS, RT>(c, P, prof_p, bp_p, L, topk, topk_cnt, topk_complete,
+                                                          chosen_out, xsend, rt);
 }
 
 // ---- packed policy sweep: a lane dimension on the two launches ---------------
@@ -1259,7 +1392,8 @@ __global__ __launch_bounds__(kBatchPods) void k_sweep_chain_pairs(DevCluster c, 
 // Which instantiations of the evaluation launches a process has launched (or
 // captured into a graph): bits 0..9 k_batch_top_commit (tc_variant), bits
 // 16..21 k_batch_top (launch_eval_top), bits 24..26 k_sweep_top_commit (DEF,
-// generic key shape, flush).  ksim_get_diag out[25]; the variant tests assert
+// generic key shape, flush), bits 27..28 k_batch_top_commit with the
+// request-class table and its flush.  ksim_get_diag out[25]; the variant tests assert
 // every bit is reached.
 static std::atomic<uint64_t> g_variant_reach{0};
 uint64_t batch_variant_reach() { return g_variant_reach.load(std::memory_order_relaxed); }
@@ -1276,12 +1410,13 @@ constexpr int tc_variant() {
 
 // the evaluation launch of a deferred-commit batch (DIRECT overlay when the
 // local node range fits kLazyDirect; DEF / KEEP as k_batch_top_commit says)
-template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS = false>
+// RT: the request-class table form (bits 27, and 28 its flush)
+template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS = false, bool RT = false>
 static void launch_tc(const LazyBatch& z, uint64_t* xsend, hipStream_t stream) {
   const LaunchArgs& a = z.a;
-  note_variant(tc_variant<FLUSH, DIRECT, DEF, KEEP, NS>());
-  k_batch_top_commit<FLUSH, DIRECT, DEF, KEEP, NS><<<kBatchPods, 1024, 0, stream>>>(
-      a.c, a.P, a.dprof, a.dbp, z.step, a.s.topk, a.s.topk_cnt, a.s.topk_complete, a.chosen, xsend);
+  note_variant(RT ? (FLUSH ? 28 : 27) : tc_variant<FLUSH, DIRECT, DEF, KEEP, NS>());
+  k_batch_top_commit<FLUSH, DIRECT, DEF, KEEP, NS, RT><<<kBatchPods, 1024, 0, stream>>>(
+      a.c, a.P, a.dprof, a.dbp, z.step, a.s.topk, a.s.topk_cnt, a.s.topk_complete, a.chosen, xsend, z.rt);
 }
 // the node-stationary form (its records are merged by chain_block<kNsSlices>):
 // unsharded launches of the default profile's shape past the KEEP range
@@ -1293,8 +1428,11 @@ template <bool FLUSH>
 static void launch_top_commit(const LazyBatch& z, uint64_t* xsend, hipStream_t stream) {
   const LaunchArgs& a = z.a;
   const bool direct = a.c.n <= kLazyDirect;
+  // the host gives a table only to unsharded KEEP / DEF runs (ksim_engine.cpp reqtab_ok)
+  const bool rt = z.rt.n_cls > 0 && !xsend && direct;
   if constexpr (FLUSH) {
-    if (direct) launch_tc<FLUSH, true, false, false>(z, xsend, stream);
+    if (rt) launch_tc<FLUSH, true, false, false, false, true>(z, xsend, stream);
+    else if (direct) launch_tc<FLUSH, true, false, false>(z, xsend, stream);
     else launch_tc<FLUSH, false, false, false>(z, xsend, stream);
   } else {
     const bool def = fast_def(a.bp);
@@ -1303,7 +1441,8 @@ static void launch_top_commit(const LazyBatch& z, uint64_t* xsend, hipStream_t s
       if (direct) launch_tc<FLUSH, true, true, false, true>(z, xsend, stream);
       else launch_tc<FLUSH, false, true, false, true>(z, xsend, stream);
     } else if (keep) {
-      if (def) launch_tc<FLUSH, true, true, true>(z, xsend, stream);
+      if (def && rt) launch_tc<FLUSH, true, true, true, false, true>(z, xsend, stream);
+      else if (def) launch_tc<FLUSH, true, true, true>(z, xsend, stream);
       else launch_tc<FLUSH, true, false, true>(z, xsend, stream);
     } else if (direct) {
       if (def) launch_tc<FLUSH, true, true, false>(z, xsend, stream);
@@ -1313,6 +1452,31 @@ static void launch_top_commit(const LazyBatch& z, uint64_t* xsend, hipStream_t s
       else launch_tc<FLUSH, false, false, false>(z, xsend, stream);
     }
   }
+}
+
+// Both halves of the request-class table from the snapshot c (a run's start:
+// X[0] == X[1]): one thread per (node, class).
+__global__ __launch_bounds__(256) void k_req_table(DevCluster c, const BatchProg* __restrict__ bp_p, ReqTab rt,
+                                                   uint16_t* __restrict__ t0, uint16_t* __restrict__ t1) {
+  const int32_t node = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+  if (node >= c.n) return;
+  const PodReq x = rt.rreq[k];
+  ksim_pod pq;
+  pq.req_cpu = x.cpu;
+  pq.req_mem = x.mem;
+  pq.req_eph = x.eph;
+  pq.nz_cpu = x.nzc;
+  pq.nz_mem = x.nzm;
+  const NodeRow r = load_res_row_off(c, node);
+  const uint16_t e = (uint16_t)req_entry(fast_prog(*bp_p), pq, r, ld_off(c.inv_cpu, (uint32_t)node << 3),
+                                         ld_off(c.inv_mem, (uint32_t)node << 3));
+  const size_t at = (size_t)k * (size_t)c.n + node;
+  t0[at] = e;
+  t1[at] = e;
+}
+
+void launch_req_table(const LaunchArgs& a, const ReqTab& rt, uint16_t* t0, uint16_t* t1, hipStream_t stream) {
+  k_req_table<<<dim3((a.c.n + 255) / 256, rt.n_cls), 256, 0, stream>>>(a.c, a.dbp, rt, t0, t1);
 }
 
 const char* const kLazyKernelNames[kKernelsPerLazy] = {"k_batch_top_commit", "k_batch_chain_pairs"};

@@ -86,6 +86,11 @@ constexpr uint32_t kClusterNarrow = 8u;          // every allocatable cpu / memo
 
 struct PodPlan;
 
+// the request fields a FAST pod's key reads (and a request class's, ReqTab::rreq)
+struct PodReq {
+  int64_t cpu, mem, eph, nzc, nzm;
+};
+
 struct DevPods {
   const ksim_pod* pods;
   const ksim_label_expr* exprs;
@@ -1844,6 +1849,31 @@ __device__ __forceinline__ int32_t fast_balanced_allocation(const FastProg& q, c
   return (hc && hm) ? b : kMaxNodeScore;
 }
 
+// The FAST key's pieces (dyn_key_fast_t, and the request-class table's req_entry).
+template <bool DEF>
+__device__ __forceinline__ bool fast_fit_ok(const FastProg& q, const ksim_pod& p, const NodeRow& r) {
+  // the Fit filter with non-short-circuit operators: one select, no branches
+  // (the request's zero test is uniform across the wave)
+  const bool any = (p.req_cpu | p.req_mem | p.req_eph) != 0;
+  const bool fits = (p.req_cpu <= r.alloc_cpu - r.req_cpu) & (p.req_mem <= r.alloc_mem - r.req_mem) &
+                    (p.req_eph <= r.alloc_eph - r.req_eph);
+  return !(DEF || q.fit) | ((r.num_pods < r.alloc_pods) & (!any | fits));
+}
+
+// The DEF total of the two scores.  The masks change no value (weights < 2^14,
+// scores in [0, 100]); they let the compiler prove both factors narrow and
+// pick v_mul_u32_u24.
+__device__ __forceinline__ int32_t fast_def_total(const FastProg& q, uint32_t la, uint32_t ba) {
+  return (int32_t)(((uint32_t)q.w_fit & 0x3fffu) * (la & 0xffffu) + ((uint32_t)q.w_ba & 0x3fffu) * (ba & 0xffffu));
+}
+
+// The key of a verdict and a total: the pod's tie-break hash of the node below them.
+__device__ __forceinline__ uint64_t fast_key_pack(bool ok, int32_t tot, uint64_t hseed, int32_t gnode) {
+  const uint64_t h = splitmix64(hseed ^ (uint64_t)(uint32_t)gnode) >> 38;
+  const uint64_t key = ((uint64_t)(uint32_t)tot << 44) | (h << 18) | (uint64_t)(KSIM_KEY_NODE_MASK - gnode);
+  return ok ? key : 0;
+}
+
 // DEF (fast_def(bp) on the host): a Fit filter, equal LeastAllocated weights,
 // at least one score plugin and both score weights below 2^14, so the key's
 // shape is compiled in: no uniform branches in the node loop, and the weights
@@ -1851,27 +1881,36 @@ __device__ __forceinline__ int32_t fast_balanced_allocation(const FastProg& q, c
 template <bool DEF>
 __device__ __forceinline__ uint64_t dyn_key_fast_t(const FastProg& q, const ksim_pod& p, const NodeRow& r,
                                                    double inv_c, double inv_m, uint64_t hseed, int32_t gnode) {
-  // the Fit filter with non-short-circuit operators: one select, no branches
-  // (the request's zero test is uniform across the wave)
-  const bool any = (p.req_cpu | p.req_mem | p.req_eph) != 0;
-  const bool fits = (p.req_cpu <= r.alloc_cpu - r.req_cpu) & (p.req_mem <= r.alloc_mem - r.req_mem) &
-                    (p.req_eph <= r.alloc_eph - r.req_eph);
-  const bool ok = !(DEF || q.fit) | ((r.num_pods < r.alloc_pods) & (!any | fits));
+  const bool ok = fast_fit_ok<DEF>(q, p, r);
   int32_t tot = 0;
   if constexpr (DEF) {
-    // the masks change no value (weights < 2^14, scores in [0, 100]); they let
-    // the compiler prove both factors narrow and pick v_mul_u32_u24
-    const uint32_t la = (uint32_t)fast_least_allocated<true>(q, p, r, inv_c, inv_m) & 0xffffu;
-    const uint32_t ba = (uint32_t)fast_balanced_allocation<true>(q, p, r, inv_c, inv_m) & 0xffffu;
-    tot = (int32_t)(((uint32_t)q.w_fit & 0x3fffu) * la + ((uint32_t)q.w_ba & 0x3fffu) * ba);
+    const uint32_t la = (uint32_t)fast_least_allocated<true>(q, p, r, inv_c, inv_m);
+    const uint32_t ba = (uint32_t)fast_balanced_allocation<true>(q, p, r, inv_c, inv_m);
+    tot = fast_def_total(q, la, ba);
   } else {
     if (q.w_fit) tot += q.w_fit * fast_least_allocated(q, p, r, inv_c, inv_m);
     if (q.w_ba) tot += q.w_ba * fast_balanced_allocation(q, p, r, inv_c, inv_m);
     if (q.no_score) tot = 1;
   }
-  const uint64_t h = splitmix64(hseed ^ (uint64_t)(uint32_t)gnode) >> 38;
-  const uint64_t key = ((uint64_t)(uint32_t)tot << 44) | (h << 18) | (uint64_t)(KSIM_KEY_NODE_MASK - gnode);
-  return ok ? key : 0;
+  return fast_key_pack(ok, tot, hseed, gnode);
+}
+
+// Request-class table entries (ksim_batch.hip k_req_table, ksim_internal.h ReqTab): the
+// part of the DEF key that depends on the pod's five request fields and the
+// node's row only, ok << 15 | la << 7 | ba.  Both scores lie in [0, 100]
+// whenever ok holds (Fit passed on a kClusterNarrow row), and a key that is
+// not ok is 0 whatever its scores; the weights stay with the profile, so an
+// entry outlives a weight change.  req_entry_key rebuilds dyn_key_fast_t<true>'s
+// key from an entry, bit for bit.
+__device__ __forceinline__ uint32_t req_entry(const FastProg& q, const ksim_pod& p, const NodeRow& r, double inv_c,
+                                              double inv_m) {
+  const uint32_t ok = fast_fit_ok<true>(q, p, r) ? 1u : 0u;
+  const uint32_t la = (uint32_t)fast_least_allocated<true>(q, p, r, inv_c, inv_m) & 0x7fu;
+  const uint32_t ba = (uint32_t)fast_balanced_allocation<true>(q, p, r, inv_c, inv_m) & 0x7fu;
+  return (ok << 15) | (la << 7) | ba;
+}
+__device__ __forceinline__ uint64_t req_entry_key(const FastProg& q, uint32_t e, uint64_t hseed, int32_t gnode) {
+  return fast_key_pack((e >> 15) != 0, fast_def_total(q, (e >> 7) & 0x7fu, e & 0x7fu), hseed, gnode);
 }
 
 __device__ __forceinline__ uint64_t dyn_key_fast(const FastProg& q, const ksim_pod& p, const NodeRow& r,

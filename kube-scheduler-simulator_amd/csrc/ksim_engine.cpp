@@ -12,6 +12,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -291,6 +292,19 @@ struct ksim_handle {
   int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
   hipGraphExec_t graph_lazy = nullptr;
   hipGraphExec_t graph_lazy_adapt = nullptr;
+  // request classes of the loaded queue (ksim_internal.h ReqTab): per loaded
+  // pod its class (0xffff: none), the classes' requests, and the table's two
+  // halves [2][rq_ncls][dc.n] (ensure_rtab; a reallocation drops graph_lazy_rt,
+  // the deferred-commit graph of the runs that take the table)
+  std::vector<uint16_t> rq_cls;
+  uint16_t* d_rcls = nullptr;
+  PodReq* d_rreq = nullptr;
+  int32_t rq_ncls = 0;                             // > kReqMaxClasses: too many, no table
+  std::vector<DevBuf> rtab_bufs;
+  size_t rtab_bytes = 0;
+  hipGraphExec_t graph_lazy_rt = nullptr;
+  int64_t rtab_runs = 0;                           // runs that took the table (ksim_get_diag out[27])
+  int32_t rt_graph_ncls = 0;                       // the class count graph_lazy_rt was captured with
   // node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and
   // the global bitmap (allocated at the first such run)
   std::vector<DevBuf> ash_bufs;
@@ -405,6 +419,8 @@ void drop_graphs(ksim_handle* h) {
   if (h->graph_lazy) (void)hipGraphExecDestroy(h->graph_lazy);
   if (h->graph_lazy_adapt) (void)hipGraphExecDestroy(h->graph_lazy_adapt);
   h->graph_lazy_adapt = nullptr;
+  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
+  h->graph_lazy_rt = nullptr;
   h->graph_batch_fast = nullptr;
   h->graph_batch = nullptr;
   h->graph_tbatch = nullptr;
@@ -911,7 +927,8 @@ int alloc_lazy(ksim_handle* h) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (h->graph_lazy) (void)hipGraphExecDestroy(h->graph_lazy);
   if (h->graph_lazy_adapt) (void)hipGraphExecDestroy(h->graph_lazy_adapt);
-  h->graph_lazy = h->graph_lazy_adapt = nullptr;
+  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
+  h->graph_lazy = h->graph_lazy_adapt = h->graph_lazy_rt = nullptr;
   free_bufs(h->lazy_bufs);
   h->lazy_n = -1;
   const size_t n = (size_t)h->dc.n;
@@ -955,8 +972,48 @@ DevCluster with_cols(DevCluster c, const DynCols& d) {
   return c;
 }
 
-// The launch arguments of deferred-commit batch i of a run.
-LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i) {
+// ---- request classes (ksim_internal.h ReqTab) ----------------------------------
+// The "ab" flavor: every pod x node pair keyed (today's KEEP / DEF kernel).
+bool reqtab_enabled() {
+  constexpr bool off = ab(kAbReqTab);
+  return !off;
+}
+
+// A deferred-commit P100 run [a, b) (lazy_ok holds) takes the table where
+// k_batch_top_commit<false, true, true, true> runs (fast_def, the KEEP range),
+// with every pod in a request class, at most kReqMaxClasses of them, and at
+// least 8 pods per class: the build keys C x N pairs and every batch's upkeep
+// up to 2 B C more, so a run not much longer than C gains nothing.
+bool reqtab_ok(const ksim_handle* h, int32_t a, int32_t b) {
+  if (!reqtab_enabled() || adapt_mode(h) || !fast_def(h->bp)) return false;
+  if (h->dc.n > kKeepPerLane * 1024) return false;   // the KEEP range (within the direct overlay's)
+  const int32_t C = h->rq_ncls;
+  if (C <= 0 || C > kReqMaxClasses || (int64_t)(b - a) < 8 * (int64_t)C || !h->d_rcls) return false;
+  for (int32_t i = a; i < b; i++)
+    if (h->rq_cls[(size_t)i] == 0xffff) return false;
+  return true;
+}
+
+// The table's two halves for the handle's cluster; a reallocation drops the
+// graph that holds their addresses (ensure_stab's rule).
+int ensure_rtab(ksim_handle* h) {
+  const size_t need = 2 * sizeof(uint16_t) * (size_t)h->rq_ncls * (size_t)h->dc.n;
+  if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
+  h->graph_lazy_rt = nullptr;
+  free_bufs(h->rtab_bufs);
+  h->rtab_bytes = 0;
+  void* p = nullptr;
+  int rc;
+  if ((rc = upload(h, h->rtab_bufs, nullptr, need, &p))) return rc;
+  h->rtab_bytes = need;
+  return KSIM_OK;
+}
+
+// The launch arguments of deferred-commit batch i of a run (rt: with the
+// request-class table, ensure_rtab done).
+LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool rt = false) {
   const int p = (int)(i & 1), q = (int)(i & 3), q1 = (int)((i + 3) & 3), q2 = (int)((i + 2) & 3);
   const DynCols x[2] = {dyn_cols(h->dc), h->lazy_x1};
   DevState* st[2] = {h->st, h->lazy_st1};
@@ -981,6 +1038,15 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i) {
   z.w1 = h->lazy_aw + (size_t)q1 * 2 * kBatchPods;
   z.abroken = h->lazy_ab + (size_t)q * kBatchPods;
   z.awin = h->lazy_aw + (size_t)q * 2 * kBatchPods;
+  if (rt) {
+    uint16_t* const t = (uint16_t*)h->rtab_bufs[0].p;
+    const size_t half = (size_t)h->rq_ncls * (size_t)h->dc.n;
+    z.rt.t_in = t + (size_t)(p ^ 1) * half;
+    z.rt.t_out = t + (size_t)p * half;
+    z.rt.rreq = h->d_rreq;
+    z.rt.rcls = h->d_rcls;
+    z.rt.n_cls = h->rq_ncls;
+  }
   return z;
 }
 
@@ -1037,15 +1103,37 @@ void lazy_flush(const ksim_handle* h, const LazyBatch& z, hipStream_t stream) {
   else launch_lazy_flush(z, stream);
 }
 
+// Both halves of the table from the run's starting snapshot (lazy_begin done).
+int reqtab_begin(ksim_handle* h, const LaunchArgs& la) {
+  int rc;
+  if ((rc = ensure_rtab(h))) return rc;
+  const LazyBatch z0 = lazy_batch(h, la, 0, true);
+  launch_req_table(la, z0.rt, z0.rt.t_out, const_cast<uint16_t*>(z0.rt.t_in), h->stream);
+  return KSIM_OK;
+}
+
 int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
   int rc;
   if ((rc = lazy_begin(h))) return rc;
-  hipGraphExec_t& graph = adapt_mode(h) ? h->graph_lazy_adapt : h->graph_lazy;
+  // the request-class table, rebuilt from the run's starting snapshot in
+  // stream order: anything may have moved X since the last run
+  const bool rt = reqtab_ok(h, a, b);
+  if (rt) {
+    h->rtab_runs++;
+    if ((rc = reqtab_begin(h, la))) return rc;
+  }
+  if (rt && h->graph_lazy_rt && h->rt_graph_ncls != h->rq_ncls) {   // a reloaded queue with other classes
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    (void)hipGraphExecDestroy(h->graph_lazy_rt);
+    h->graph_lazy_rt = nullptr;
+  }
+  hipGraphExec_t& graph = adapt_mode(h) ? h->graph_lazy_adapt : rt ? h->graph_lazy_rt : h->graph_lazy;
   if (!graph) {
+    if (rt) h->rt_graph_ncls = h->rq_ncls;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     hipGraph_t g = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kGraphBatches; i++) lazy_launch(h, lazy_batch(h, la, i), h->stream);
+    for (int i = 0; i < kGraphBatches; i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
     hipError_t e = hipStreamEndCapture(h->stream, &g);
     if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
     e = hipGraphInstantiate(&graph, g, nullptr, nullptr, 0);
@@ -1063,12 +1151,12 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
     int32_t nb = (b - cursor + kBatchPods - 1) / kBatchPods;
     const int32_t align = (int32_t)((kLazySlots - (i & 3)) & 3);
     if (nb >= align + kGraphBatches) {
-      for (int32_t r = 0; r < align; r++, i++, nb--) lazy_launch(h, lazy_batch(h, la, i), h->stream);
+      for (int32_t r = 0; r < align; r++, i++, nb--) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
       for (int32_t r = 0; r < nb / kGraphBatches; r++, i += kGraphBatches) HIPCHK(h, hipGraphLaunch(graph, h->stream));
     } else {
-      for (int32_t r = 0; r < nb; r++, i++) lazy_launch(h, lazy_batch(h, la, i), h->stream);
+      for (int32_t r = 0; r < nb; r++, i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
     }
-    lazy_flush(h, lazy_batch(h, la, i), h->stream);
+    lazy_flush(h, lazy_batch(h, la, i, rt), h->stream);
     HIPCHK(h, hipGetLastError());
     DevState st;
     if ((rc = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return rc;
@@ -2089,6 +2177,7 @@ void ksim_destroy(ksim_handle* h) {
   if (h->sweep_profs.p) (void)hipFree(h->sweep_profs.p);
   if (h->sweep_rows.p) (void)hipFree(h->sweep_rows.p);
   free_bufs(h->stab_bufs);
+  free_bufs(h->rtab_bufs);
   free_bufs(h->pod_bufs);
   if (h->pod1_arena.p) (void)hipFree(h->pod1_arena.p);
   if (h->nom_arena.p) (void)hipFree(h->nom_arena.p);
@@ -4034,7 +4123,7 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
                                      sizeof(ksim_topo_use) * (size_t)ps->n_uses,
                                      sizeof(PodPlan) * (size_t)ps->n_pods,
                                      sizeof(ksim_class_add) * (size_t)ps->n_adds,
-                                     4 * np1, 4 * np1};
+                                     4 * np1, 4 * np1, 2 * np1, sizeof(PodReq) * ((size_t)kReqMaxClasses + 1)};
   const bool reuse = h->d_chosen && h->pod_buf_bytes == bytes;
   auto drop_queue = [&](int code) {
     drop_graphs(h);
@@ -4114,6 +4203,27 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
       scls[(size_t)i] = it->second;
     }
   }
+  // request classes (ReqTab): the pods run_fast accepts, by their five request
+  // fields (such pods request no scalar resources)
+  std::vector<uint16_t> rcls(np1, 0xffff);
+  std::vector<PodReq> rreq;
+  {
+    std::map<std::array<int64_t, 5>, int32_t> ids;
+    for (int32_t i = 0; i < ps->n_pods; i++) {
+      const ksim_pod& q = ps->pods[i];
+      if (!h->trivial[i] || batchable[i] != 1 || (q.flags & KSIM_POD_HAS_SCALAR)) continue;
+      const std::array<int64_t, 5> key = {q.req_cpu, q.req_mem, q.req_eph, q.nz_cpu, q.nz_mem};
+      auto it = ids.find(key);
+      if (it == ids.end()) {
+        if ((int32_t)ids.size() > kReqMaxClasses) break;   // too many: no table for this queue
+        it = ids.emplace(key, (int32_t)ids.size()).first;
+        rreq.push_back(PodReq{key[0], key[1], key[2], key[3], key[4]});
+      }
+      rcls[(size_t)i] = (uint16_t)it->second;
+    }
+  }
+  const int32_t n_rcls = (int32_t)rreq.size();       // kReqMaxClasses + 1: too many
+  rreq.resize((size_t)kReqMaxClasses + 1, PodReq{0, 0, 0, 0, 0});
   std::vector<PodPlan> plans((size_t)ps->n_pods);
   for (int32_t i = 0; i < ps->n_pods; i++) {
     plans[i] = make_plan(h, ps->pods[i], uses.data() + std::max(ps->pods[i].use_first, 0));
@@ -4168,6 +4278,15 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
   h->stab_ncls = ncls;
   h->sclass.assign(scls.begin(), scls.begin() + ps->n_pods);
   h->stab_dirty = true;
+  h->d_rcls = nullptr;
+  h->rq_ncls = 0;
+  if ((rc = put(rcls.data(), 2 * np1, &p))) return drop_queue(rc);
+  uint16_t* const d_rcls = (uint16_t*)p;
+  if ((rc = put(rreq.data(), sizeof(PodReq) * rreq.size(), &p))) return drop_queue(rc);
+  h->d_rreq = (PodReq*)p;
+  h->d_rcls = d_rcls;
+  h->rq_cls.assign(rcls.begin(), rcls.begin() + ps->n_pods);
+  h->rq_ncls = n_rcls;
   if ((rc = put(R.ent.data(), sizeof(int4) * R.ent.size(), &p))) return drop_queue(rc);
   P.ptab_ent = (const int4*)p;
   if ((rc = put(R.cfirst.data(), 4 * R.cfirst.size(), &p))) return drop_queue(rc);
@@ -4514,9 +4633,13 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
     // (idempotent: it reads X[0], st[0] and slot 0, and writes X[1], st[1],
     // the lists and batch 0's placements); the handle's own buffers keep
     // their contents
+    // (with the request-class table when the run from `first` to the queue's
+    // end takes it: the launch the timing stands for)
     if ((rc = lazy_begin(h))) return rc;
-    launch_batch_lazy(lazy_batch(h, a, 0), h->stream);
-    const LazyBatch z = lazy_batch(h, a, 1);
+    const bool rt = reqtab_ok(h, first, h->dp.n_pods);
+    if (rt && (rc = reqtab_begin(h, a))) return rc;
+    launch_batch_lazy(lazy_batch(h, a, 0, rt), h->stream);
+    const LazyBatch z = lazy_batch(h, a, 1, rt);
     launch_lazy_top(z, h->stream);
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     for (int32_t i = 0; i < reps; i++) launch_lazy_top(z, h->stream);
@@ -4606,6 +4729,8 @@ int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_
                         (adapt ? kKernelsPerLazy : 0);
       HIPCHK(h, hipMemsetAsync(&h->st->batches, 0, 4, h->stream));
       if ((r = lazy_begin(h))) return r;
+      const bool rt = reqtab_ok(h, lo, hi);
+      if (rt && (r = reqtab_begin(h, a))) return r;
       int64_t i = 0;
       int32_t cursor = lo, done_batches = 0;
       while (cursor < hi) {
@@ -4614,8 +4739,8 @@ int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_
         for (auto& e : evs) HIPCHK(h, hipEventCreate(&e));
         uint32_t launched = 0;
         for (int32_t t = 0; t < iters; t++, i++)
-          launched = lazy_launch(h, lazy_batch(h, a, i), h->stream, &evs[(size_t)t * (lper + 1)]);
-        lazy_flush(h, lazy_batch(h, a, i), h->stream);
+          launched = lazy_launch(h, lazy_batch(h, a, i, rt), h->stream, &evs[(size_t)t * (lper + 1)]);
+        lazy_flush(h, lazy_batch(h, a, i, rt), h->stream);
         HIPCHK(h, hipGetLastError());
         DevState st;
         if ((r = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return r;
@@ -4693,7 +4818,7 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   DevState st;
   int rc = read_state(h, st);
   if (rc) return rc;
-  int64_t v[3 + 16 + 2 + 4 + 2] = {st.batches, st.truncations, st.cuts};
+  int64_t v[3 + 16 + 2 + 4 + 3] = {st.batches, st.truncations, st.cuts};
   if (h->has_cluster) HIPCHK(h, hcopy(h, v + 3, h->sc.dbg, 8 * 16, hipMemcpyDeviceToHost));
   if (unsigned long long* cp = cp_clock_buffer())   // KSIM_CP_CLOCKS builds: the chain + pairs phase clocks
     HIPCHK(h, hcopy(h, v + 3, cp, 8 * 8, hipMemcpyDeviceToHost));
@@ -4704,7 +4829,8 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   for (int k = 0; k < 4; k++) v[21 + k] = h->fw_counts[k];
   v[25] = (int64_t)batch_variant_reach();
   if (h->has_cluster && h->sc.tb_vpods) HIPCHK(h, hcopy(h, v + 26, h->sc.tb_vpods, 8, hipMemcpyDeviceToHost));
-  const int32_t m = n < 27 ? n : 27;
+  v[27] = h->rtab_runs;
+  const int32_t m = n < 28 ? n : 28;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
 }

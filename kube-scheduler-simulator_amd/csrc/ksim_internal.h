@@ -10,7 +10,7 @@ namespace ksim {
 // libksim_engine_ab.so, every alternative form on; tests/test_gpu_ab_switches.py
 // runs it against the oracle).  The product library has none of them.
 // KSIM_AB_FORMS is a bitmask of the alternative forms (csrc/Makefile "ab":
-// 127, every one on; "abforms": one form each, checked against the product's
+// 255, every one on; "abforms": one form each, checked against the product's
 // other forms):
 constexpr unsigned kAbStab = 1;      // per-node static plugins (no static-class table)
 constexpr unsigned kAbLazy = 2;      // three-launch batches (commit as its own launch)
@@ -19,6 +19,7 @@ constexpr unsigned kAbTbatch = 8;    // topology pods on the per-pod path
 constexpr unsigned kAbShardGraph = 16;   // eager shard cycles (no shard-group graphs)
 constexpr unsigned kAbPtab = 32;     // per-cycle PreFilter domain sums (no persistent tables)
 constexpr unsigned kAbTbVar = 64;    // topology batches end at a zone-keyed class conflict (no zone variants)
+constexpr unsigned kAbReqTab = 128;  // KEEP/DEF deferred-commit batches key every pod x node pair (no request-class table)
 #ifdef KSIM_AB_FORMS
 constexpr unsigned kAbMask = KSIM_AB_FORMS;
 #else
@@ -138,6 +139,21 @@ struct DynCols {
   int64_t *req_cpu, *req_mem, *req_eph, *nz_cpu, *nz_mem;
   int32_t* num_pods;
 };
+// Request classes (ReqTab): the pods of a loaded queue that share their five
+// request fields share a class, and T[2][C][N] holds each class's verdict and
+// scores on each node (req_entry), double-buffered with X: batch i reads
+// T[p ^ 1] (S_{i-1}; the nodes batch i-1 bound patched from the overlay) and
+// writes S_i's entries into T[p] for the nodes batches i-1 and i-2 guessed,
+// exactly where it writes X[p].  k_req_table fills both halves from X at the
+// start of a run.  n_cls = 0: no table (every other launch form).
+constexpr int kReqMaxClasses = 256;
+struct ReqTab {
+  const uint16_t* t_in = nullptr;                  // T[p ^ 1], [n_cls][n]
+  uint16_t* t_out = nullptr;                       // T[p]
+  const PodReq* rreq = nullptr;                    // [n_cls] the classes' requests
+  const uint16_t* rcls = nullptr;                  // [n_pods] class of each loaded pod
+  int32_t n_cls = 0, _pad = 0;
+};
 struct LazyStep {
   DynCols w;                                       // X[p]: receives S_i
   const DevState* st_in;                           // st[p ^ 1]: the state batch i-1 started from
@@ -150,6 +166,7 @@ struct LazyBatch {
   LaunchArgs a;        // a.c: static columns + X[p ^ 1]
   DevCluster cw;       // static columns + X[p]
   LazyStep step;
+  ReqTab rt;           // the request-class table halves of the batch (run_lazy's runs that take it)
   DevState* st;        // st[p]
   uint64_t* gkey;      // batch i's slot
   uint64_t* pmax;
@@ -199,6 +216,8 @@ void launch_adapt_lazy_flush(const LazyBatch& z, hipStream_t stream);
 // DevPods::stab rows of classes [0, n_cls) (ksim_batch.hip k_static_table)
 void launch_static_table(const LaunchArgs& a, const int32_t* rep, int32_t n_cls, uint64_t* stab, hipStream_t stream);
 uint32_t launch_batch_lazy(const LazyBatch& z, hipStream_t stream, hipEvent_t* evs = nullptr);
+// both halves of the request-class table from the snapshot a.c (k_req_table)
+void launch_req_table(const LaunchArgs& a, const ReqTab& rt, uint16_t* t0, uint16_t* t1, hipStream_t stream);
 void launch_lazy_flush(const LazyBatch& z, hipStream_t stream);
 // the evaluation-launch instantiations launched so far (ksim_get_diag out[25])
 uint64_t batch_variant_reach();
