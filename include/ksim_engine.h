@@ -742,7 +742,8 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * default-shape, static-class, FAST default-shape, FAST, generic keys --
  * bits 24..26 the packed sweep's k_sweep_top_commit -- default-shape, generic,
  * flush -- bits 27..28 k_batch_top_commit with the request-class table and its
- * flush);
+ * flush -- bit 29 the k_batch_chain_pairs that writes the table's patch
+ * entries for the next evaluation launch);
  * out[26] topology batch pods committed on a zone variant (their batch moved
  * their DoNotSchedule domain verdicts; ksim_tbatch.hip TbVar), cumulative;
  * out[27] batch runs of this handle that took the request-class table (the

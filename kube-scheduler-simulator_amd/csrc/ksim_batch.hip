@@ -17,7 +17,11 @@
 //   k_batch_commit       one block: validates the chain and commits
 //
 // or, on FAST runs of an unsharded handle, the deferred-commit form
-// (k_batch_top_commit: batch i-1's commit inside batch i's top launch).
+// (k_batch_top_commit: batch i-1's commit inside batch i's top launch).  With
+// the request-class table (ksim_internal.h ReqTab) that launch reads a 2-byte
+// entry per (class, node) instead of keying the pair, and the pairs launch,
+// which holds every guessed node's row with its pod bound, also writes those
+// rows' entries for every class: the next launch's patches of the table.
 //
 // Exactness: pods 0..i-1 took their guesses (distinct nodes), so before pod i
 // only those nodes differ from S0.  Pod i's guess is the best node still at
@@ -564,28 +568,37 @@ __global__ __launch_bounds__(256) void k_batch_gmerge(const DevState* __restrict
 // held one of its normalization maxima (kPodNormVaries) has left its feasible
 // set: the maximum, and so its S0 keys, no longer hold, and the batch commits
 // only the pods before it.
-template <bool FAST, bool STAB = false, bool DEF = false>
+// PATCH (FAST, DEF, no static classes; ksim_internal.h ReqTab): a block that
+// owns a request class (pe_out: the class's row of the ring's patch entries,
+// creq: its request; both null elsewhere) also keys that class on every guess
+// of the chain with the guessing pod bound there, the row thread k < j holds
+// for its pair key anyway.  The other lanes of the block load theirs in the
+// same round trip, and a block past the chain's end stays for it.
+template <bool FAST, bool STAB = false, bool DEF = false, bool PATCH = false>
 __device__ __forceinline__ void pairs_block(const DevCluster& c, const DevPods& P, const ksim_profile& prof,
                                             const BatchProg& bp, const DevState* __restrict__ st, uint64_t gk,
                                             int32_t nchain, uint64_t* s_wmax, uint64_t* __restrict__ pmax,
                                             const ksim_pod* pj = nullptr, const ksim_pod* pk = nullptr,
                                             const int64_t* __restrict__ pnorm = nullptr,
-                                            int32_t* __restrict__ pinv = nullptr, int32_t* s_winv = nullptr) {
+                                            int32_t* __restrict__ pinv = nullptr, int32_t* s_winv = nullptr,
+                                            const ksim_pod* creq = nullptr, uint16_t* __restrict__ pe_out = nullptr) {
+  static_assert(!PATCH || (FAST && !STAB && DEF), "patch entries: the FAST default-shape pairs");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = blockIdx.x, k = tid;
   const int32_t base = st->cursor;
   const int64_t seq0 = st->pod_seq;
   constexpr bool kInv = !FAST || STAB;               // pinv flags (kPodNormVaries pods)
+  const bool owns = PATCH && pe_out != nullptr;      // block-uniform
   if (j >= nchain) {                                 // block-uniform
     if (tid == 0) {
       pmax[j] = 0;
       if (kInv) pinv[j] = 0;
     }
-    return;
+    if (!owns) return;
   }
   uint64_t v = 0;
   bool lost_t = false, lost_a = false;               // guess k held a maximum of pod j and left its feasible set
-  if (k < j) {
+  if (k < j || owns) {                               // (gk = 0 from the chain's end on)
     const int32_t local = gk ? key_node(gk) - c.base : -1;
     if (local >= 0 && local < c.n) {
       const ksim_pod& p = P.pods[base + j];
@@ -613,8 +626,13 @@ __device__ __forceinline__ void pairs_block(const DevCluster& c, const DevPods& 
       } else if constexpr (FAST) {
         NodeRow r = load_res_row(c, local);
         row_add_pod(r, pk ? *pk : P.pods[base + k], 1);
-        v = dyn_key_fast_t<DEF>(fast_prog(bp), pj ? *pj : p, r, c.inv_cpu[local], c.inv_mem[local],
-                         prof.tiebreak_seed ^ ((uint64_t)(seq0 + j) << 20), c.base + local);
+        const double ic = c.inv_cpu[local], im = c.inv_mem[local];
+        if (!PATCH || (k < j && j < nchain))
+          v = dyn_key_fast_t<DEF>(fast_prog(bp), pj ? *pj : p, r, ic, im,
+                                  prof.tiebreak_seed ^ ((uint64_t)(seq0 + j) << 20), c.base + local);
+        if constexpr (PATCH) {
+          if (owns) pe_out[k] = (uint16_t)req_entry(fast_prog(bp), *creq, r, ic, im);
+        }
       } else {
         const int32_t bf = P.bflags[base + j];
         const bool normv = (bf & kPodNormVaries) != 0;
@@ -644,6 +662,7 @@ __device__ __forceinline__ void pairs_block(const DevCluster& c, const DevPods& 
       }
     }
   }
+  if (PATCH && j >= nchain) return;                  // stayed for its class only (pmax[j] = 0 above)
   v = wave_max_u64_dpp(v);
   if (lane == 0) s_wmax[wave] = v;
   if (kInv) {                                        // holders lost per wave: TaintToleration | NodeAffinity << 16
@@ -689,7 +708,9 @@ unsigned long long* cp_clock_buffer() { return nullptr; }
 // DEF (FAST pairs): the default profile's key shape compiled in.
 // The launch's body (k_batch_chain_pairs, and the packed sweep's
 // k_sweep_chain_pairs with a lane's buffers).
-template <bool FAST, bool LAZY, bool STAB, int R, bool DEF>
+// PATCH (the request-class table's runs, rt.n_cls > 0): block kBatchPods - 1 -
+// c writes class c's patch entries of the batch into rt.p_out (pairs_block).
+template <bool FAST, bool LAZY, bool STAB, int R, bool DEF, bool PATCH = false>
 __device__ __forceinline__ void batch_chain_pairs_body(const DevCluster& c, const DevPods& P,
                                                        const ksim_profile* __restrict__ prof_p,
                                                        const BatchProg* __restrict__ bp_p,
@@ -699,7 +720,7 @@ __device__ __forceinline__ void batch_chain_pairs_body(const DevCluster& c, cons
                                                        const int32_t* __restrict__ topk_complete,
                                                        uint64_t* __restrict__ gkey, int32_t* __restrict__ chain_end,
                                                        uint64_t* __restrict__ pmax, const int64_t* __restrict__ pnorm,
-                                                       int32_t* __restrict__ pinv) {
+                                                       int32_t* __restrict__ pinv, const ReqTab& rt = ReqTab{}) {
   __shared__ ChainLds L;
   __shared__ uint64_t s_wmax[kBatchPods / 64];
   __shared__ int32_t s_winv[kBatchPods / 64];
@@ -710,6 +731,21 @@ __device__ __forceinline__ void batch_chain_pairs_body(const DevCluster& c, cons
     const int32_t j = blockIdx.x, k = threadIdx.x;
     if (j < nb) pj = fast_pod_fields(P.pods[base + j]);
     if (k < nb) pk = fast_pod_fields(P.pods[base + k]);
+  }
+  // PATCH: the block's class and its request (block-uniform), likewise
+  ksim_pod creq;
+  uint16_t* pe_out = nullptr;
+  if constexpr (PATCH) {
+    const int32_t cls = kBatchPods - 1 - (int32_t)blockIdx.x;
+    if (cls < rt.n_cls) {
+      const PodReq x = rt.rreq[cls];
+      creq.req_cpu = x.cpu;
+      creq.req_mem = x.mem;
+      creq.req_eph = x.eph;
+      creq.nz_cpu = x.nzc;
+      creq.nz_mem = x.nzm;
+      pe_out = rt.p_out + (size_t)cls * kBatchPods;
+    }
   }
   uint64_t gk;
   int32_t nchain;
@@ -731,14 +767,14 @@ __device__ __forceinline__ void batch_chain_pairs_body(const DevCluster& c, cons
     if ((int)threadIdx.x < nb) gkey[threadIdx.x] = gk;
     if (threadIdx.x == 0) *chain_end = nchain;
   }
-  pairs_block<FAST, STAB, DEF>(c, P, *prof_p, *bp_p, st, gk, nchain, s_wmax, pmax, FAST ? &pj : nullptr,
-                          FAST ? &pk : nullptr, pnorm, pinv, s_winv);
+  pairs_block<FAST, STAB, DEF, PATCH>(c, P, *prof_p, *bp_p, st, gk, nchain, s_wmax, pmax, FAST ? &pj : nullptr,
+                                      FAST ? &pk : nullptr, pnorm, pinv, s_winv, &creq, pe_out);
 #ifdef KSIM_CP_CLOCKS
   if (dbgc && threadIdx.x == 0) atomicAdd(&dbgc[5], (unsigned long long)(__builtin_amdgcn_s_memrealtime() - t_in));
 #endif
 }
 
-template <bool FAST, bool LAZY = false, bool STAB = false, int R = 1, bool DEF = false>
+template <bool FAST, bool LAZY = false, bool STAB = false, int R = 1, bool DEF = false, bool PATCH = false>
 __global__ __launch_bounds__(kBatchPods) void k_batch_chain_pairs(DevCluster c, DevPods P,
                                                                   const ksim_profile* __restrict__ prof_p,
                                                                   const BatchProg* __restrict__ bp_p,
@@ -750,9 +786,9 @@ __global__ __launch_bounds__(kBatchPods) void k_batch_chain_pairs(DevCluster c, 
                                                                   int32_t* __restrict__ chain_end,
                                                                   uint64_t* __restrict__ pmax,
                                                                   const int64_t* __restrict__ pnorm,
-                                                                  int32_t* __restrict__ pinv) {
-  batch_chain_pairs_body<FAST, LAZY, STAB, R, DEF>(c, P, prof_p, bp_p, st, topk, topk_cnt, topk_complete, gkey,
-                                                   chain_end, pmax, pnorm, pinv);
+                                                                  int32_t* __restrict__ pinv, ReqTab rt) {
+  batch_chain_pairs_body<FAST, LAZY, STAB, R, DEF, PATCH>(c, P, prof_p, bp_p, st, topk, topk_cnt, topk_complete,
+                                                          gkey, chain_end, pmax, pnorm, pinv, rt);
 }
 
 __global__ __launch_bounds__(kBatchPods) void k_batch_commit(DevCluster c, DevPods P, DevState* __restrict__ st,
@@ -849,9 +885,12 @@ struct UpRow {
 // verdicts and scores from its request class's row of T[p ^ 1], one 2-byte
 // load per node, and only the tie-break hash is computed per pair.  The nodes
 // batch i-1 bound are stale there (their binds are in the overlay alone):
-// thread t keys entry t's node for the block's class with the full arithmetic
-// into s_patch[t], and the main pass selects by s_ent.  Where the block
-// writes S_i's rows into X[p] it writes every class's entry of them into T[p].
+// thread t < i* takes entry t's node for the block's class from the patch
+// entries batch i-1's pairs launch wrote (that launch held the row with pod t
+// bound for its pair keys; one coalesced 2-byte load) into s_patch[t], and the
+// main pass selects by s_ent.  Only the node that takes pod i* too is keyed
+// here, by one lane.  Where the block writes S_i's rows into X[p] it writes
+// every class's entry of them into T[p].
 template <bool FLUSH, bool DIRECT, bool DEF, bool KEEP, bool NS, bool RT = false>
 __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const DevPods& P,
                                                       const ksim_profile* __restrict__ prof_p,
@@ -932,27 +971,9 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     s_unsched = 0;
     s_rq[kBatchPods] = ResCols{0, 0, 0, 0, 0, 0};
   }
-  // RT: the row of this thread's entry of batch i-1 (patched below if it is
-  // bound) and the class request of this thread's upkeep; neither depends on
-  // the cut.  Issued once g1 is here, with clamped indices and no lane
-  // predicate, so that the waits further down count them exactly and they
-  // stay in flight across the cut's barriers.
-  NodeRow prow{};
-  double pic = 0, pim = 0;
+  // RT: the class request of this thread's upkeep (it does not depend on the cut)
   PodReq creq{0, 0, 0, 0, 0};
   if constexpr (RT) {
-    if constexpr (!FLUSH) {
-      // m1 is waited for here, before the branch: past it the wait could no
-      // longer leave the row loads in flight (a wait after a branch counts the
-      // path that issued fewest)
-      asm volatile("" : : "v"(m1), "v"(g1));
-      if (tid < kBatchPods) {                       // whole waves
-        const int32_t gn = (tid < e1 && g1) ? key_node(g1) - c.base : 0;   // tid < e1: the slot holds batch i-1's guesses
-        prow = load_res_row_off(c, gn);
-        pic = ld_off(c.inv_cpu, (uint32_t)gn << 3);
-        pim = ld_off(c.inv_mem, (uint32_t)gn << 3);
-      }
-    }
     const int32_t t = tid < 64 ? 0 : tid - 64;      // upkeep thread 64 + t: row t / C, class t % C
     creq = rt.rreq[t < 2 * rt.n_cls ? (t < rt.n_cls ? t : t - rt.n_cls) : 0];
   }
@@ -978,10 +999,27 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   tp[2] = __builtin_amdgcn_s_memrealtime();
 #endif
   const int32_t inode = s_inode;
-  // RT: the lane's entries of its class's row, all loaded before the first use
+  // entry tid < i*: its guessed node takes pod tid, and pod i* when i* chose it
+  const int32_t gnode = (tid < istar && g1) ? key_node(g1) - c.base : -1;
+  // RT: the entry of this thread's node for the block's class with pod tid
+  // bound there, as batch i-1's pairs launch keyed it (ReqTab::p_in; tid < i*
+  // <= e1: the slot holds that batch's), and the lane's entries of its class's
+  // row, all in one round trip and all loaded before the first use.  The node
+  // that takes pod i* as well is keyed here: its one lane loads the row.  The
+  // patch loads come first, so waiting for them leaves te[] in flight.
   uint32_t te[kKeepPerLane];
+  uint32_t pe = 0;
+  NodeRow prow{};
+  double pic = 0, pim = 0;
+  const bool twice = RT && !FLUSH && live && gnode >= 0 && gnode == inode;
   if constexpr (RT && !FLUSH) {
     const int32_t cls = live ? (int32_t)s_cls[committed] : 0;
+    if (live && gnode >= 0) pe = rt.p_in[(size_t)cls * kBatchPods + tid];
+    if (twice) {
+      prow = load_res_row_off(c, gnode);
+      pic = ld_off(c.inv_cpu, (uint32_t)gnode << 3);
+      pim = ld_off(c.inv_mem, (uint32_t)gnode << 3);
+    }
     const uint16_t* __restrict__ trow = rt.t_in + (size_t)cls * (size_t)c.n;
 #pragma unroll
     for (int q = 0; q < kKeepPerLane; q++) {
@@ -989,8 +1027,6 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
       te[q] = trow[node < c.eval_hi ? node : c.eval_lo];   // clamped, not predicated (a past-the-end lane's is unused)
     }
   }
-  // entry tid < i*: its guessed node takes pod tid, and pod i* when i* chose it
-  const int32_t gnode = (tid < istar && g1) ? key_node(g1) - c.base : -1;
   if (gnode >= 0) {
     ResCols d = rq;
     if (gnode == inode) {
@@ -1004,7 +1040,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     }
     s_rq[tid] = d;
     if constexpr (RT && !FLUSH) {
-      if (live) {                                 // the bound node's entry for the block's class
+      if (twice) {                                // S_{i-1} + pod tid + pod i* for the block's class
         const PodReq x = s_pc[committed];
         ksim_pod pq;
         pq.req_cpu = x.cpu;
@@ -1018,8 +1054,9 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
         prow.nz_cpu += d.nzc;
         prow.nz_mem += d.nzm;
         prow.num_pods += d.pods;
-        s_patch[tid] = (uint16_t)req_entry(fast_prog(*bp_p), pq, prow, pic, pim);
+        pe = req_entry(fast_prog(*bp_p), pq, prow, pic, pim);
       }
+      if (live) s_patch[tid] = (uint16_t)pe;
     }
     if constexpr (DIRECT) {
       s_ent[gnode] = (int16_t)tid;                // guessed nodes are distinct
@@ -1393,8 +1430,9 @@ __global__ __launch_bounds__(kBatchPods) void k_sweep_chain_pairs(DevCluster c, 
 // captured into a graph): bits 0..9 k_batch_top_commit (tc_variant), bits
 // 16..21 k_batch_top (launch_eval_top), bits 24..26 k_sweep_top_commit (DEF,
 // generic key shape, flush), bits 27..28 k_batch_top_commit with the
-// request-class table and its flush.  ksim_get_diag out[25]; the variant tests assert
-// every bit is reached.
+// request-class table and its flush, bit 29 the k_batch_chain_pairs that
+// writes the table's patch entries.  ksim_get_diag out[25]; the variant tests
+// assert every bit is reached.
 static std::atomic<uint64_t> g_variant_reach{0};
 uint64_t batch_variant_reach() { return g_variant_reach.load(std::memory_order_relaxed); }
 static void note_variant(int bit) { g_variant_reach.fetch_or(1ull << bit, std::memory_order_relaxed); }
@@ -1424,6 +1462,14 @@ static bool ns_eval(const LaunchArgs& a, const uint64_t* xsend) {
   const int32_t len = a.c.eval_hi - a.c.eval_lo;
   return !xsend && fast_def(a.bp) && len > kKeepPerLane * 1024;
 }
+// the request-class table form of a batch (the KEEP / DEF / DIRECT launch with
+// a table): its evaluation launch reads the patch entries the pairs launch of
+// the batch before it wrote, so both take the form by this one rule
+static bool rt_eval(const LazyBatch& z, const uint64_t* xsend) {
+  const LaunchArgs& a = z.a;
+  return z.rt.n_cls > 0 && !xsend && a.c.n <= kLazyDirect && a.c.eval_hi - a.c.eval_lo <= kKeepPerLane * 1024 &&
+         fast_def(a.bp);
+}
 template <bool FLUSH>
 static void launch_top_commit(const LazyBatch& z, uint64_t* xsend, hipStream_t stream) {
   const LaunchArgs& a = z.a;
@@ -1441,7 +1487,7 @@ static void launch_top_commit(const LazyBatch& z, uint64_t* xsend, hipStream_t s
       if (direct) launch_tc<FLUSH, true, true, false, true>(z, xsend, stream);
       else launch_tc<FLUSH, false, true, false, true>(z, xsend, stream);
     } else if (keep) {
-      if (def && rt) launch_tc<FLUSH, true, true, true, false, true>(z, xsend, stream);
+      if (rt_eval(z, xsend)) launch_tc<FLUSH, true, true, true, false, true>(z, xsend, stream);
       else if (def) launch_tc<FLUSH, true, true, true>(z, xsend, stream);
       else launch_tc<FLUSH, true, false, true>(z, xsend, stream);
     } else if (direct) {
@@ -1489,15 +1535,20 @@ uint32_t launch_batch_lazy(const LazyBatch& z, hipStream_t stream, hipEvent_t* e
   if (ns_eval(a, nullptr))                     // the slice records merged as the chain loads them
     k_batch_chain_pairs<true, true, false, kNsSlices, true><<<kBatchPods, kBatchPods, 0, stream>>>(
         z.cw, a.P, a.dprof, a.dbp, z.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, z.gkey, z.cend, z.pmax,
-        a.s.pnorm, a.s.pinv);
-  else if (fast_def(a.bp))
+        a.s.pnorm, a.s.pinv, ReqTab{});
+  else if (fast_def(a.bp) && rt_eval(z, nullptr)) {   // ... and the next evaluation launch's patch entries
+    note_variant(29);
+    k_batch_chain_pairs<true, true, false, 1, true, true><<<kBatchPods, kBatchPods, 0, stream>>>(
+        z.cw, a.P, a.dprof, a.dbp, z.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, z.gkey, z.cend, z.pmax,
+        a.s.pnorm, a.s.pinv, z.rt);
+  } else if (fast_def(a.bp))
     k_batch_chain_pairs<true, true, false, 1, true><<<kBatchPods, kBatchPods, 0, stream>>>(
         z.cw, a.P, a.dprof, a.dbp, z.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, z.gkey, z.cend, z.pmax,
-        a.s.pnorm, a.s.pinv);
+        a.s.pnorm, a.s.pinv, ReqTab{});
   else
     k_batch_chain_pairs<true, true><<<kBatchPods, kBatchPods, 0, stream>>>(
         z.cw, a.P, a.dprof, a.dbp, z.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, z.gkey, z.cend, z.pmax,
-        a.s.pnorm, a.s.pinv);
+        a.s.pnorm, a.s.pinv, ReqTab{});
   if (evs) (void)hipEventRecord(evs[2], stream);
   return 0x3u;
 }
@@ -1517,7 +1568,7 @@ void launch_lazy_chain_rep(const LazyBatch& z, int32_t world, hipStream_t stream
                                                      a.s.topk_complete);
   k_batch_chain_pairs<true, true><<<kBatchPods, kBatchPods, 0, stream>>>(z.cw, a.P, a.dprof, a.dbp, z.st, a.s.topk,
                                                                             a.s.topk_cnt, a.s.topk_complete, z.gkey,
-                                                                            z.cend, z.pmax, a.s.pnorm, a.s.pinv);
+                                                                            z.cend, z.pmax, a.s.pnorm, a.s.pinv, ReqTab{});
 }
 
 void launch_lazy_flush(const LazyBatch& z, hipStream_t stream) { launch_top_commit<true>(z, nullptr, stream); }
@@ -1583,19 +1634,19 @@ static void launch_chain_pairs(const LaunchArgs& a, hipStream_t stream) {
   if (a.stab && fast_def(a.bp))
     k_batch_chain_pairs<true, false, true, 1, true><<<kBatchPods, kBatchPods, 0, stream>>>(
         a.c, a.P, a.dprof, a.dbp, a.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, a.s.gkey, a.s.chain_end, a.s.pmax,
-        a.s.pnorm, a.s.pinv);
+        a.s.pnorm, a.s.pinv, ReqTab{});
   else if (a.stab)
     k_batch_chain_pairs<true, false, true><<<kBatchPods, kBatchPods, 0, stream>>>(
         a.c, a.P, a.dprof, a.dbp, a.st, a.s.topk, a.s.topk_cnt, a.s.topk_complete, a.s.gkey, a.s.chain_end, a.s.pmax,
-        a.s.pnorm, a.s.pinv);
+        a.s.pnorm, a.s.pinv, ReqTab{});
   else if (a.fast)
     k_batch_chain_pairs<true><<<kBatchPods, kBatchPods, 0, stream>>>(a.c, a.P, a.dprof, a.dbp, a.st, a.s.topk,
                                                                      a.s.topk_cnt, a.s.topk_complete, a.s.gkey,
-                                                                     a.s.chain_end, a.s.pmax, a.s.pnorm, a.s.pinv);
+                                                                     a.s.chain_end, a.s.pmax, a.s.pnorm, a.s.pinv, ReqTab{});
   else
     k_batch_chain_pairs<false><<<kBatchPods, kBatchPods, 0, stream>>>(a.c, a.P, a.dprof, a.dbp, a.st, a.s.topk,
                                                                       a.s.topk_cnt, a.s.topk_complete, a.s.gkey,
-                                                                      a.s.chain_end, a.s.pmax, a.s.pnorm, a.s.pinv);
+                                                                      a.s.chain_end, a.s.pmax, a.s.pnorm, a.s.pinv, ReqTab{});
 }
 
 uint32_t launch_batch(const LaunchArgs& a, hipStream_t stream, hipEvent_t* evs) {

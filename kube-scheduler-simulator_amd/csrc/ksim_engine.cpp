@@ -294,8 +294,9 @@ struct ksim_handle {
   hipGraphExec_t graph_lazy_adapt = nullptr;
   // request classes of the loaded queue (ksim_internal.h ReqTab): per loaded
   // pod its class (0xffff: none), the classes' requests, and the table's two
-  // halves [2][rq_ncls][dc.n] (ensure_rtab; a reallocation drops graph_lazy_rt,
-  // the deferred-commit graph of the runs that take the table)
+  // halves [2][rq_ncls][dc.n] with the ring's patch entries
+  // [kLazySlots][rq_ncls][kBatchPods] behind them (ensure_rtab; a reallocation
+  // drops graph_lazy_rt, the deferred-commit graph of the runs that take the table)
   std::vector<uint16_t> rq_cls;
   uint16_t* d_rcls = nullptr;
   PodReq* d_rreq = nullptr;
@@ -994,10 +995,15 @@ bool reqtab_ok(const ksim_handle* h, int32_t a, int32_t b) {
   return true;
 }
 
-// The table's two halves for the handle's cluster; a reallocation drops the
-// graph that holds their addresses (ensure_stab's rule).
+// The table's two halves for the handle's cluster, then (at a 256-byte step)
+// the ring's patch entries P[kLazySlots][C][kBatchPods]; a reallocation drops
+// the graph that holds their addresses (ensure_stab's rule).
+size_t rtab_halves_bytes(const ksim_handle* h) {
+  const size_t t = 2 * sizeof(uint16_t) * (size_t)h->rq_ncls * (size_t)h->dc.n;
+  return (t + 255) & ~(size_t)255;
+}
 int ensure_rtab(ksim_handle* h) {
-  const size_t need = 2 * sizeof(uint16_t) * (size_t)h->rq_ncls * (size_t)h->dc.n;
+  const size_t need = rtab_halves_bytes(h) + sizeof(uint16_t) * kLazySlots * (size_t)h->rq_ncls * kBatchPods;
   if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
@@ -1046,6 +1052,12 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool
     z.rt.rreq = h->d_rreq;
     z.rt.rcls = h->d_rcls;
     z.rt.n_cls = h->rq_ncls;
+    // the patch entries: batch i's pairs launch writes slot q, batch i's
+    // evaluation launch reads batch i-1's
+    uint16_t* const pe = (uint16_t*)((char*)h->rtab_bufs[0].p + rtab_halves_bytes(h));
+    const size_t slot = (size_t)h->rq_ncls * kBatchPods;
+    z.rt.p_in = pe + (size_t)q1 * slot;
+    z.rt.p_out = pe + (size_t)q * slot;
   }
   return z;
 }

@@ -142,16 +142,25 @@ struct DynCols {
 // Request classes (ReqTab): the pods of a loaded queue that share their five
 // request fields share a class, and T[2][C][N] holds each class's verdict and
 // scores on each node (req_entry), double-buffered with X: batch i reads
-// T[p ^ 1] (S_{i-1}; the nodes batch i-1 bound patched from the overlay) and
+// T[p ^ 1] (S_{i-1}; the nodes batch i-1 bound patched from P, below) and
 // writes S_i's entries into T[p] for the nodes batches i-1 and i-2 guessed,
 // exactly where it writes X[p].  k_req_table fills both halves from X at the
 // start of a run.  n_cls = 0: no table (every other launch form).
+// The patch entries P[kLazySlots][C][kBatchPods] ride the ring: batch i's
+// pairs launch, whose thread k holds S_i[node(g_k)] + pod k for its pair key,
+// writes every class's entry of that row into slot i & 3 (block B - 1 - c keys
+// class c for every k of the chain: one 512-byte row per class), and batch
+// i + 1's evaluation launch reads its class's row of that slot, entry t under
+// t < i* <= chain_end only, so a stale slot or a stale tail is never selected.
+// Only the node that takes two pods at a cut is keyed in the evaluation launch.
 constexpr int kReqMaxClasses = 256;
 struct ReqTab {
   const uint16_t* t_in = nullptr;                  // T[p ^ 1], [n_cls][n]
   uint16_t* t_out = nullptr;                       // T[p]
   const PodReq* rreq = nullptr;                    // [n_cls] the classes' requests
   const uint16_t* rcls = nullptr;                  // [n_pods] class of each loaded pod
+  const uint16_t* p_in = nullptr;                  // P[(i - 1) & 3], [n_cls][kBatchPods]: batch i-1's patch entries
+  uint16_t* p_out = nullptr;                       // P[i & 3]: batch i's, written by its pairs launch
   int32_t n_cls = 0, _pad = 0;
 };
 struct LazyStep {
