@@ -1783,8 +1783,10 @@ __device__ __forceinline__ double div_rn(double n, double d, double y) {
 // tie-break hash.
 // An integer in [0, 2^52) as a double, exactly: the bits of 2^52 + x minus
 // 2^52 (one OR and one add, where the general int64 conversion takes two
-// conversions, a scale and an add).  Every value the FAST keys convert is
-// below 2^46 (kClusterNarrow allocatables; sums bounded by them, see callers).
+// conversions, a scale and an add).  Every value whose conversion the FAST
+// keys use is below 2^46 (kClusterNarrow allocatables; sums bounded by them,
+// see callers); a larger or negative x converts to garbage the callers never
+// select (x = 2^52 to 0: bit 52 is one of the bits the OR sets).
 __device__ __forceinline__ double u52_to_f64(int64_t x) {
   return __longlong_as_double(x | 0x4330000000000000LL) - 4503599627370496.0;
 }
@@ -1833,18 +1835,27 @@ __device__ __forceinline__ int32_t fast_least_allocated(const FastProg& q, const
 }
 
 // balancedResourceScorer over {cpu, memory}: the float64 quotients Go computes.
-// With a Fit filter in the profile it passed, so requested + request <=
-// allocatable < 2^46 and the short conversion is exact (without one the sums
-// are unbounded and take the general conversion).  With one resource missing
-// the standard deviation is 0 (score 100), as with both present and equal.
+// A fraction above 1 counts as 1, and that is decided on the integers: a sum
+// above the allocatable gives a quotient above 1 in float64 too (the
+// conversion is monotone and allocatable + 1 < 2^46 is exact), and one at or
+// below it is below 2^46, where the short conversion is exact and the
+// correctly rounded quotient is at most 1.  A passed Fit filter does not bound
+// the sums: a pod that requests nothing passes it on a node whose requested
+// column is past its allocatable, or past 2^52, where the short conversion
+// would drop the high bits (tests/test_gpu_fast_edges.py, zero_and_overdrawn).
+// Without a Fit filter the sums take the general conversion as before.  With
+// one resource missing the standard deviation is 0 (score 100), as with both
+// present and equal.
 template <bool DEF>
 __device__ __forceinline__ int32_t fast_balanced_allocation(const FastProg& q, const ksim_pod& p, const NodeRow& r,
                                                             double inv_c, double inv_m) {
   const bool hc = r.alloc_cpu != 0, hm = r.alloc_mem != 0;
   const int64_t qc = r.req_cpu + p.req_cpu, qm = r.req_mem + p.req_mem;
   const bool fit = DEF || q.fit;
-  const double fc = fmin(div_rn(fit ? u52_to_f64(qc) : (double)qc, u52_to_f64(r.alloc_cpu), inv_c), 1.0);
-  const double fm = fmin(div_rn(fit ? u52_to_f64(qm) : (double)qm, u52_to_f64(r.alloc_mem), inv_m), 1.0);
+  const double dc = div_rn(fit ? u52_to_f64(qc) : (double)qc, u52_to_f64(r.alloc_cpu), inv_c);
+  const double dm = div_rn(fit ? u52_to_f64(qm) : (double)qm, u52_to_f64(r.alloc_mem), inv_m);
+  const double fc = qc > r.alloc_cpu ? 1.0 : dc;
+  const double fm = qm > r.alloc_mem ? 1.0 : dm;
   const int32_t b = (int32_t)((1 - fabs((fc - fm) / 2)) * (double)kMaxNodeScore);
   return (hc && hm) ? b : kMaxNodeScore;
 }

@@ -377,7 +377,9 @@ def edge_objects(n_pods: int = 160, seed: int = SEEDS[1] ^ 0xED6E) -> Tuple[List
     overcommit a node), allowed pods 0, quantities at and past 2^52 (the exact
     division path) and past 2^56 (leastRequestedScore's int64 product wraps
     in Go), BestEffort pods (non-zero defaults), init containers.  Returns
-    (nodes, bound pods, pending pods)."""
+    (nodes, bound pods, pending pods).  With allocatables of 4Pi and more the
+    cluster is not narrow: it exercises the generic int64 / IEEE-division
+    arithmetic only; tests/fastcases.py covers the FAST key's."""
     r = Rng(seed)
 
     def node(i, cpu, mem, pods="110"):
