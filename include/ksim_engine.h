@@ -868,9 +868,10 @@ int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allow
  *               sees whether any matching pod is left cluster-wide.  The adds
  *               come from ksim_set_bound_pod_adds (KSIM_E_INVALID without
  *               them).  Ignored when the filter list has no InterPodAffinity;
- *   PTS_HARD    its Filter needs the minimum over every domain after each
- *               removal: KSIM_E_UNSUPPORTED (the message names PTS_HARD), also
- *               beside InterPodAffinity uses.
+ *   PTS_HARD    KSIM_E_UNSUPPORTED from this call and ksim_preempt_nominated (the
+ *               message names PTS_HARD), also beside InterPodAffinity uses:
+ *               their callers fall back on that code.  ksim_preempt_spread
+ *               runs the dry run for such pods.
  * Also KSIM_E_UNSUPPORTED: shard handles, NetworkBandwidth in the filter list,
  * KSIM_POD_NODE_NAMES pods. */
 int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
@@ -891,6 +892,45 @@ int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, in
 int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                            const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
                            const int32_t* first, const int32_t* count, ksim_preempt_out* out);
+
+/* ksim_preempt_nominated that also accepts KSIM_USE_PTS_HARD uses (n_groups = 0
+ * is allowed); for a pod without one it returns what ksim_preempt_nominated
+ * returns.  The dry run then re-runs PodTopologySpread beside the other
+ * filters, all on the moved row:
+ *   potential nodes  a node whose first failing filter is PodTopologySpread
+ *               with KSIM_PTS_SKEW is Unschedulable, so a potential node;
+ *               KSIM_PTS_MISSING_LABEL is UnschedulableAndUnresolvable and is
+ *               not.  The reason is re-derived from the node's row, with a
+ *               nominated group's adds on it (pass 1);
+ *   what moves  upstream's updateWithPod: a pod of node n moves constraint i's
+ *               pair only if n carries every DoNotSchedule constraint's key, n
+ *               passes constraint i's node inclusion policies for the
+ *               preemptor (nodeAffinityPolicy, Honor by default;
+ *               nodeTaintsPolicy, Ignore by default: KSIM_USEF_HONOR_*), and
+ *               the pod counts into the use's selector class (same namespace,
+ *               the selector matches), by the adds of
+ *               ksim_set_bound_pod_adds (KSIM_E_INVALID without them; the
+ *               message names that call) and a nominated group's own.  On a
+ *               node that is not eligible nothing moves and the verdict is the
+ *               status pass's;
+ *   the Filter  per constraint i, own' + selfMatch - min(own', others_i(n)) >
+ *               maxSkew fails: own' is the count of n's domain after the
+ *               moves, others_i(n) the minimum over the present domains other
+ *               than n's (MaxInt32 when n's is the only one).  Only n's own
+ *               pods move in n's dry run (upstream copies the cycle state per
+ *               node), so others_i(n) is fixed and this is upstream's
+ *               criticalPaths exactly.  minDomains is ignored (its gate is off
+ *               in 1.26);
+ *   the pod passes  when NodeResourcesFit, NodePorts, InterPodAffinity and
+ *               PodTopologySpread all pass; a preemptor may carry all of these
+ *               use kinds at once.
+ * Ignored when the profile's filter list has no PodTopologySpread.  Pass 2 of
+ * RunFilterPluginsWithNominatedPods is not re-run inside the dry run, as in
+ * ksim_preempt_nominated; the other refusals (shard handles, NetworkBandwidth,
+ * KSIM_POD_NODE_NAMES) stay. */
+int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
+                        const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
+                        const int32_t* first, const int32_t* count, ksim_preempt_out* out);
 
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's

@@ -727,14 +727,28 @@ func (p *postFilter) PostFilter(ctx context.Context, state *framework.CycleState
 	var out C.ksim_preempt_out
 	out.victims = (*C.int32_t)(unsafe.Pointer(&victims[0]))
 	out.victims_cap = C.int32_t(len(victims))
+	// a pod with a DoNotSchedule spread constraint (KSIM_USE_PTS_HARD) takes the
+	// call that also re-runs PodTopologySpread; like pods with required pod
+	// (anti-)affinity it is the engine's: BoundTable sent every class the bound
+	// pods count into, which the dry run moves
+	hardSpread := false
+	for _, tsc := range pod.Spec.TopologySpreadConstraints {
+		if tsc.WhenUnsatisfiable == v1.DoNotSchedule {
+			hardSpread = true
+		}
+	}
 	pr.Engine.mu.Lock()
-	rc := C.ksim_preempt_nominated(pr.Engine.h, c.ps, 0, C.int32_t(prio), nps, C.int32_t(len(gnodes)), gn, gf, gc, &out)
+	var rc C.int
+	if hardSpread {
+		rc = C.ksim_preempt_spread(pr.Engine.h, c.ps, 0, C.int32_t(prio), nps, C.int32_t(len(gnodes)), gn, gf, gc, &out)
+	} else {
+		rc = C.ksim_preempt_nominated(pr.Engine.h, c.ps, 0, C.int32_t(prio), nps, C.int32_t(len(gnodes)), gn, gf, gc, &out)
+	}
 	perr := pr.Engine.err(rc) // under the mutex: the handle's last error is this call's
 	pr.Engine.mu.Unlock()
 	if rc == C.KSIM_E_UNSUPPORTED {
-		// a pod with DoNotSchedule spread (KSIM_USE_PTS_HARD): the original answers.
-		// Pods with required pod (anti-)affinity are the engine's: BoundTable sent
-		// every class the bound pods count into, which their dry run moves
+		// the other refusals (NetworkBandwidth in the filter list, a pod a
+		// PreFilterResult restricts): the original answers
 		return p.orig.(framework.PostFilterPlugin).PostFilter(ctx, state, pod, m)
 	}
 	if perr != nil {

@@ -223,6 +223,7 @@ struct ksim_handle {
   // DefaultPreemption: bound pods per node in importance order
   std::vector<DevBuf> pre_bufs;
   std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
+  int64_t* pre_smin = nullptr;          // ksim_preempt_spread's per-use minima (in pre_bufs; k_preempt_spread_mins)
   std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
   std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
   DevPreempt pre{};
@@ -4911,6 +4912,8 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   d.nreq = nullptr;
   if ((rc = upload(h, h->pre_bufs, nullptr, 8 * (size_t)KSIM_MAX_USES, &p))) return rc;
   d.afftot = (int64_t*)p;
+  if ((rc = upload(h, h->pre_bufs, nullptr, 8 * 3 * (size_t)KSIM_MAX_USES, &p))) return rc;
+  h->pre_smin = (int64_t*)p;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->pre = d;
   h->pre_index = ix;
@@ -5002,9 +5005,11 @@ extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_
   return ksim_preempt_nominated(h, ps, pod_index, priority, nullptr, 0, nullptr, nullptr, nullptr, out);
 }
 
-extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                                      const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
-                                      const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+// The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
+// DoNotSchedule spread uses are refused) and ksim_preempt_spread.
+static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
+                       const int32_t* count, ksim_preempt_out* out, bool spread) {
   int rc = ensure_ready(h);
   if (rc) return rc;
   if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
@@ -5030,31 +5035,38 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
   if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
   if ((rc = validate_pod(h, ps, pod_index))) return rc;
-  int32_t fit = -1, port = -1, ipa = -1;
+  int32_t fit = -1, port = -1, ipa = -1, pts = -1;
   for (int f = 0; f < h->prof.n_filter; f++) {
     if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
     if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
     if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) ipa = f;
+    if (h->prof.filter[f] == KSIM_PL_POD_TOPOLOGY_SPREAD) pts = f;
   }
-  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity.  Uses
-  // that no Filter reads (ScheduleAnyway spread, InterPodAffinity scores,
-  // ImageLocality) are ignored; DoNotSchedule spread, whose Filter needs the
-  // minimum over every domain after each removal, is refused.
+  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity and,
+  // through ksim_preempt_spread, PodTopologySpread.  Uses that no Filter reads
+  // (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
+  // ignored; the two older entry points refuse DoNotSchedule spread (their
+  // callers fall back on that code).
   const ksim_pod& pp = ps->pods[pod_index];
   const bool topo = pp.use_count > 0;
-  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0;
-  for (int32_t k = 0; k < pp.use_count; k++)
+  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
+  for (int32_t k = 0; k < pp.use_count && !spread; k++)
     if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
       return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
-                                            "victims' domains)");
+                                            "victims' domains: ksim_preempt_spread)");
   for (int32_t k = 0; k < pp.use_count; k++) {
     const uint8_t kind = ps->uses[pp.use_first + k].kind;
     if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
     if (kind == KSIM_USE_IPA_AFFINITY && ipa >= 0) aff_mask |= 1u << k;
     if (kind == KSIM_USE_IPA_ANTI && ipa >= 0) anti_mask |= 1u << k;
     if (kind == KSIM_USE_IPA_EXISTING_ANTI && ipa >= 0) exist_mask |= 1u << k;
+    if (kind == KSIM_USE_PTS_HARD && pts >= 0) hard_mask |= 1u << k;
   }
-  const bool dom_form = (aff_mask | anti_mask | exist_mask) != 0;   // the domain form of k_preempt_nodes
+  // the domain form of k_preempt_nodes (the spread form is one: it reads the same row)
+  const bool dom_form = (aff_mask | anti_mask | exist_mask | hard_mask) != 0;
+  if (hard_mask && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "ksim_preempt_spread for a pod with DoNotSchedule spread: "
+                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
   if (port_mask && !dom_form && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
                                       "(after ksim_set_bound_pods)");
@@ -5137,7 +5149,8 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
       HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
     }
   }
-  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask);
+  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
+                 hard_mask, h->pre_smin);
   HIPCHK(h, hipGetLastError());
   if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
   if (n_groups > 0) {
@@ -5166,6 +5179,18 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
         if (flag[j - off[0]] == want) out->victims[k++] = h->pre_index[j];
   }
   return KSIM_OK;
+}
+
+extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                      const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                      const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false);
+}
+
+extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                   const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                   const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true);
 }
 
 // ---- selector / affinity-term matching (ksim_match.hip) ------

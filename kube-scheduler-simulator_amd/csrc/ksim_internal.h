@@ -306,9 +306,13 @@ struct DevPreempt {
 // ipa_index / aff, anti, exist: InterPodAffinity's place and the preemptor's
 // required-affinity, required-anti-affinity and existing-anti-affinity uses
 // (the domain form: s.dom still holds the status pass's domain tables).
+// pts_index / hard / smin: PodTopologySpread's place, the preemptor's
+// DoNotSchedule spread uses (the spread form, which reads the same tables) and
+// [KSIM_MAX_USES][3] device words for k_preempt_spread_mins' minima.
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio, hipStream_t stream,
                     bool filter = true, int32_t port_index = -1, uint32_t port_mask = 0, int32_t ipa_index = -1,
-                    uint32_t aff = 0, uint32_t anti = 0, uint32_t exist = 0);
+                    uint32_t aff = 0, uint32_t anti = 0, uint32_t exist = 0, int32_t pts_index = -1,
+                    uint32_t hard = 0, int64_t* smin = nullptr);
 
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);

@@ -19,13 +19,19 @@
 // InterPodAffinity for an anti-affinity reason is a potential node too.  With
 // PodDisruptionBudgets on the table (ksim_set_bound_pod_pdbs) the thread first
 // splits the lower-priority pods as filterPodsWithPDBViolation does (the PDB
-// form, kernels of their own) and reprieves the violating ones first.  One
+// form, kernels of their own) and reprieves the violating ones first.  A pod
+// with DoNotSchedule spread uses (ksim_preempt_spread) takes the spread form:
+// the domain form plus PodTopologySpread's Filter on the moved row, against
+// min(the node's own domain, the minimum over the other present domains),
+// which k_preempt_spread_mins takes once per dry run.  One
 // block then keeps candidates in nodeTree order (upstream scans from a random
 // offset; offset 0 here) until numCandidates were found and one of them has
 // no PDB violation, and picks one by pickOneNodeForPreemption's criteria.
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
+
+#include <type_traits>
 
 namespace ksim {
 
@@ -73,10 +79,25 @@ struct PreemptDom {
   uint32_t aff, anti, exist;
   int32_t ipa_index;
 };
+// The spread form's argument (the other forms keep PreemptDom, and with it
+// their kernel arguments): the preemptor's DoNotSchedule spread uses when the
+// profile filters on PodTopologySpread, that filter's place, and per use
+// {the minimum over the present domains, the value id of one arg-min, the
+// minimum over the others} (k_preempt_spread_mins; [KSIM_MAX_USES][3]).
+struct PreemptSpread : PreemptDom {
+  uint32_t hard;
+  int32_t pts_index;
+  int64_t* smin;
+};
 // NodeInfo.AddPod / RemovePod and PreFilterExtensions.AddPod / RemovePod of one
 // pod (or nominated group) on the node's row: sign x count of every add whose
 // class a filter-read use reads.  A use whose key the node lacks (t.v[i] == 0)
 // moves too, but no Filter reads its count (upstream leaves its maps alone).
+// A DoNotSchedule spread use's entry carries the presence marks above its
+// count (kDomMarkShift): the count of the pods the status pass summed never
+// goes below zero, so adding to the whole entry leaves the marks alone; such a
+// use moves only on a node that is eligible for it (its cls[i] is
+// kNoPortClass elsewhere: podtopologyspread's updateWithPod).
 __device__ __forceinline__ void topo_add(TopoRow& t, const int32_t (&cls)[KSIM_MAX_USES],
                                          const ksim_class_add* __restrict__ adds, int32_t e0, int32_t e1, int sign) {
   for (int32_t e = e0; e < e1; e++) {
@@ -85,6 +106,35 @@ __device__ __forceinline__ void topo_add(TopoRow& t, const int32_t (&cls)[KSIM_M
     for (int i = 0; i < KSIM_MAX_USES; i++)
       if (cls[i] == x.cls) t.x[i] += (int64_t)sign * x.count;
   }
+}
+// podtopologyspread Filter on the moved row -> 0 or KSIM_PTS_* (the first
+// failing constraint's reason, as pts_filter).  Constraint i fails for skew
+// when match + selfMatch - crit > maxSkew, crit = min(match, others_i) on a
+// node that is eligible for it (its own domain is present and moves) and
+// others_i elsewhere (nothing moved: the status pass's minimum).  With
+// thr[i] = others_i - (selfMatch - maxSkew), fixed for the dry run, that is
+// match > thr[i], or selfMatch > maxSkew on an eligible node (bit i of `over`:
+// the own domain alone is too many).
+__device__ __forceinline__ uint32_t spread_filter(uint32_t hard, uint32_t over, const int64_t (&thr)[KSIM_MAX_USES],
+                                                  const TopoRow& t) {
+  uint32_t why = 0;
+#pragma unroll
+  for (int i = 0; i < KSIM_MAX_USES; i++) {
+    if (why != 0 || !((hard >> i) & 1u)) continue;
+    const int64_t match = t.x[i] & kDomCountMask;                  // absent pair: 0
+    if (t.v[i] == 0) why = KSIM_PTS_MISSING_LABEL;
+    else if (((over >> i) & 1u) || match > thr[i]) why = KSIM_PTS_SKEW;
+  }
+  return why;
+}
+// spread_filter(...) != 0 without the order of the reasons: what a trial asks
+__device__ __forceinline__ bool spread_fails(uint32_t hard, uint32_t over, const int64_t (&thr)[KSIM_MAX_USES],
+                                             const TopoRow& t) {
+  bool bad = (hard & over) != 0;
+#pragma unroll
+  for (int i = 0; i < KSIM_MAX_USES; i++)
+    if ((hard >> i) & 1u) bad |= t.v[i] == 0 || (t.x[i] & kDomCountMask) > thr[i];
+  return bad;
 }
 // len(state.affinityCounts) > 0 on the moved row: a matching pod outside the
 // node's domains (outside: the use's cluster-wide total minus the node's domain
@@ -113,11 +163,22 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
 // the number of budgets).  The violating rows are reprieved first, then the
 // others, so the victims list need not be sorted by priority: `high` is the
 // first victim appended, `early` follows the true maximum priority.
-template <bool PORTS, bool DOM = false, bool PDB = false>
+// SPREAD (the spread form; implies DOM): the dry run also re-runs
+// PodTopologySpread on the row.  In node n's dry run only n's pods move, so
+// per constraint only the count of n's own domain moves and the critical path
+// is min(own count, others_i): the minimum over the other present domains
+// (dm.smin: the second minimum when n's value is the arg-min), fixed for the
+// whole dry run and folded into thr[i].  A pod of n moves constraint i only when n is
+// eligible for it (every hard constraint's key on n, and n passes i's node
+// inclusion policies: what k_topo_prefilter counted); elsewhere the verdict
+// is the status pass's.  A node that failed PodTopologySpread is a potential
+// node only for the skew reason, re-derived from the row like
+// InterPodAffinity's.
+template <bool PORTS, bool DOM = false, bool PDB = false, bool SPREAD = false, typename DM = PreemptDom>
 __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
                                                const ksim_pod& p, const PodPlan& plan, const ksim_topo_use* U,
                                                const DevPreempt& pre, int32_t node, int32_t prio, bool fit,
-                                               uint32_t port_mask, const PreemptDom& dm, bool at_ipa,
+                                               uint32_t port_mask, const DM& dm, bool at_ipa, bool at_pts,
                                                PreemptNode& out) {
   const int32_t a = pre.off[node], b = pre.off[node + 1];
   int32_t j0 = a;
@@ -135,6 +196,8 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
   TopoRow t;
   UseMasks mm{};                                        // the roles the dry run's filters read
   bool outside = false;
+  uint32_t elig = 0, over = 0;                          // SPREAD: the hard uses this node's pods move; spread_filter
+  int64_t thr[KSIM_MAX_USES];                           // SPREAD: per hard use, the count the row may reach
   if (DOM) {
     mm.port = port_mask;
     mm.aff = dm.aff;
@@ -142,13 +205,42 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
     mm.exist = dm.exist;
     const uint32_t read = port_mask | dm.aff | dm.anti | dm.exist;
     load_topo_row(c, U, p.use_count, plan.m, s, P.ptab, node, t);
+    if constexpr (SPREAD) {                             // updateWithPod's node tests, once per node
+      bool all_hard = true;                             // nodeLabelsMatchSpreadConstraints
+#pragma unroll
+      for (int i = 0; i < KSIM_MAX_USES; i++)
+        if (((dm.hard >> i) & 1u) && t.v[i] == 0) all_hard = false;
+      if (all_hard) {                                   // matchNodeInclusionPolicies, as k_topo_prefilter
+        const bool aff_ok = (plan.m.honor_aff & dm.hard) ? required_node_affinity_match(c, P, p, node) : true;
+        const bool taint_ok = (plan.m.honor_taints & dm.hard) ? !node_has_untolerated_taint(c, p, node) : true;
+        elig = dm.hard & ~(aff_ok ? 0u : plan.m.honor_aff) & ~(taint_ok ? 0u : plan.m.honor_taints);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < KSIM_MAX_USES; i++) {
       cls[i] = kNoPortClass;
       if ((read >> i) & 1u) cls[i] = load_use(U, i).cls;
       if (((dm.aff >> i) & 1u) && t.v[i] != 0 && pre.afftot[i] - t.x[i] > 0) outside = true;
+      if constexpr (SPREAD) {
+        thr[i] = 0;
+        if ((dm.hard >> i) & 1u) {
+          const int64_t* mn = dm.smin + 3 * i;          // {min1, the arg-min's value id, min2}
+          const ksim_topo_use u = load_use(U, i);
+          const bool mine = (elig >> i) & 1u;
+          // others_i(n): the second minimum when n's own domain is the arg-min
+          const int64_t oth = mine && (int64_t)t.v[i] == mn[1] ? mn[2] : mn[0];
+          const int64_t lim = (int64_t)((plan.m.self_match >> i) & 1u) - (int64_t)u.arg;
+          thr[i] = oth - lim;
+          if (mine && lim > 0) over |= 1u << i;
+          if (mine) cls[i] = u.cls;
+        }
+      }
     }
     if (g >= 0) topo_add(t, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
+    if constexpr (SPREAD) {
+      if (at_pts && spread_filter(dm.hard, over, thr, t) == KSIM_PTS_MISSING_LABEL)
+        return;                                         // the status pass's detail: UnschedulableAndUnresolvable
+    }
     if (at_ipa) {                                       // the status pass's InterPodAffinity detail
       const uint32_t why = ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t);
       if (why != KSIM_IPA_ANTI_AFFINITY && why != KSIM_IPA_EXISTING_ANTI) return;   // UnschedulableAndUnresolvable
@@ -175,6 +267,9 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
   // the filters the dry run re-runs: 0 = the pod passes
   auto fails = [&]() -> bool {
     if ((!(PORTS || DOM) || fit) && fits_request(r, p, c.n_scalar, c.fit_ignore) != 0) return true;
+    if constexpr (SPREAD) {
+      if (spread_fails(dm.hard, over, thr, t)) return true;
+    }
     if (DOM) return node_port_conflict(mm, t) || ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t) != 0;
     return PORTS && hold_conflict(h);
   };
@@ -250,11 +345,14 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
 // of its own, so a preemptor without such uses runs the code (and keeps the
 // registers) it had before that form existed.  PDB: the PDB form, likewise
 // kernels of their own, launched only when the table carries budgets.
-template <bool DOM, bool PDB>
+// SPREAD: the spread form (ksim_preempt_spread for a preemptor with
+// DoNotSchedule spread uses; DOM with it), kernels of their own again: a node
+// that failed PodTopologySpread for the skew reason is a potential node too.
+template <bool DOM, bool PDB, bool SPREAD = false>
 __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, const DevState* __restrict__ st,
                                                        DevScratch s, DevPreempt pre, int32_t fit_index,
                                                        int32_t prio, int32_t port_index, uint32_t port_mask,
-                                                       PreemptDom dm) {
+                                                       std::conditional_t<SPREAD, PreemptSpread, PreemptDom> dm) {
   const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
   if (node >= c.n) return;
   PreemptNode out{};
@@ -262,20 +360,27 @@ __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, 
   const uint8_t f = s.fail[node];
   const ksim_pod& p = P.pods[st->cursor];
   const ksim_topo_use* U = P.uses + p.use_first;
-  if (DOM) {
+  if constexpr (SPREAD) {
+    const bool at_ipa = (dm.aff | dm.anti | dm.exist) != 0 && f == (uint8_t)dm.ipa_index;
+    const bool at_pts = f == (uint8_t)dm.pts_index;
+    if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa || at_pts)
+      select_victims<false, true, PDB, true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0,
+                                             port_mask, dm, at_ipa, at_pts, out);
+  } else if (DOM) {
     const bool at_ipa = f == (uint8_t)dm.ipa_index;
     if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa)
       select_victims<false, true, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
-                                  at_ipa, out);
+                                  at_ipa, false, out);
   } else {
     const bool potential = (fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index);
     out.potential = potential;
     if (potential) {
       if (port_mask)                                   // kernel argument: one uniform branch
         select_victims<true, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
-                             false, out);
+                             false, false, out);
       else
-        select_victims<false, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, out);
+        select_victims<false, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, false,
+                                          out);
     }
   }
   pre.res[node] = out;
@@ -307,6 +412,85 @@ __global__ __launch_bounds__(256) void k_preempt_totals(DevCluster c, DevPods P,
     if (lane == 0) sh[w] = sum;
     __syncthreads();
     if (tid == 0) pre.afftot[i] = sh[0] + sh[1] + sh[2] + sh[3];
+  }
+}
+
+// TpKeyToCriticalPaths for a dry run that moves one domain: per DoNotSchedule
+// spread use of the preemptor (one block each, block k = the k-th set bit of
+// `hard`), over the present entries of the table load_topo_row reads,
+// smin[3 i ..] = {the minimum, the value id of one arg-min, the minimum
+// over the present values other than that one}; math.MaxInt32 where there is
+// none.  Launched after the status pass, before k_preempt_nodes.
+__global__ __launch_bounds__(256) void k_preempt_spread_mins(DevCluster c, DevPods P,
+                                                             const DevState* __restrict__ st, DevScratch s,
+                                                             int64_t* __restrict__ smin, uint32_t hard) {
+  __shared__ int64_t sh_m[4];
+  __shared__ int32_t sh_v[4];
+  __shared__ int64_t s_m1;
+  __shared__ int32_t s_v1;
+  constexpr int64_t kNone = 2147483647;
+  int i = 0;                                           // this block's use
+  for (int k = blockIdx.x; i < KSIM_MAX_USES; i++)
+    if (((hard >> i) & 1u) && k-- == 0) break;
+  if (i >= KSIM_MAX_USES) return;
+  const int32_t pi = st->cursor;
+  const ksim_pod& p = P.pods[pi];
+  const ksim_topo_use u = load_use(P.uses + p.use_first, i);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int32_t V = u.col != KSIM_COL_NONE ? c.col_nvals[u.col] : 0;
+  const int64_t* d = ((P.plans[pi].m.ptab >> i) & 1u) ? P.ptab + u._pad : s.dom + (size_t)i * c.vmax;
+  // the pair (count, value id), smallest count first, then the smallest id
+  auto less = [](int64_t ma, int32_t va, int64_t mb, int32_t vb) { return ma < mb || (ma == mb && va < vb); };
+  int64_t m1 = kNone, m2 = kNone;
+  int32_t v1 = -1;
+  for (int pass = 0; pass < 2; pass++) {               // pass 1: the same over the values other than v1
+    int64_t m = kNone;
+    int32_t at = INT32_MAX;
+    for (int32_t v = tid; v < V; v += blockDim.x) {
+      const int64_t x = d[v];
+      if ((x >> kDomMarkShift) == 0 || (pass == 1 && v == v1)) continue;
+      const int64_t cnt = x & kDomCountMask;
+      if (less(cnt, v, m, at)) {
+        m = cnt;
+        at = v;
+      }
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+      const int64_t mo = __shfl_xor(m, k, 64);
+      const int32_t vo = __shfl_xor(at, k, 64);
+      if (less(mo, vo, m, at)) {
+        m = mo;
+        at = vo;
+      }
+    }
+    __syncthreads();                                    // the last pass's readers are done
+    if (lane == 0) {
+      sh_m[w] = m;
+      sh_v[w] = at;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int k = 1; k < 4; k++)
+        if (less(sh_m[k], sh_v[k], m, at)) {
+          m = sh_m[k];
+          at = sh_v[k];
+        }
+      s_m1 = m;
+      s_v1 = at == INT32_MAX ? -1 : at;
+    }
+    __syncthreads();
+    if (pass == 0) {
+      m1 = s_m1;
+      v1 = s_v1;
+    } else {
+      m2 = s_m1;
+    }
+  }
+  if (tid == 0) {
+    smin[3 * i] = m1;
+    smin[3 * i + 1] = v1;
+    smin[3 * i + 2] = m2;
   }
 }
 
@@ -420,17 +604,29 @@ __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, Dev
 
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
                     hipStream_t stream, bool filter, int32_t port_index, uint32_t port_mask, int32_t ipa_index,
-                    uint32_t aff, uint32_t anti, uint32_t exist) {
+                    uint32_t aff, uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin) {
   const int blocks = (a.c.n + 255) / 256;
   if (filter) launch_filter_only(a, stream);             // the filter statuses of every node
   if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
   if (ipa_index < 0) aff = anti = exist = 0;             // nor the InterPodAffinity uses without that filter
+  if (pts_index < 0) hard = 0;                           // nor the DoNotSchedule spread uses without PodTopologySpread
   const PreemptDom dm{aff, anti, exist, ipa_index};
   const bool dom = (aff | anti | exist) != 0, pdb = pre.poff != nullptr;
   if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
-  auto nodes = dom ? (pdb ? k_preempt_nodes<true, true> : k_preempt_nodes<true, false>)
-                   : (pdb ? k_preempt_nodes<false, true> : k_preempt_nodes<false, false>);
-  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
+  if (hard) {                                            // the spread form
+    PreemptSpread ds{};
+    static_cast<PreemptDom&>(ds) = dm;
+    ds.hard = hard;
+    ds.pts_index = pts_index;
+    ds.smin = smin;
+    k_preempt_spread_mins<<<__builtin_popcount(hard), 256, 0, stream>>>(a.c, a.P, a.st, a.s, smin, hard);
+    auto nodes = pdb ? k_preempt_nodes<true, true, true> : k_preempt_nodes<true, false, true>;
+    nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, ds);
+  } else {
+    auto nodes = dom ? (pdb ? k_preempt_nodes<true, true> : k_preempt_nodes<true, false>)
+                     : (pdb ? k_preempt_nodes<false, true> : k_preempt_nodes<false, false>);
+    nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
+  }
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

@@ -31,7 +31,7 @@ EXPORTS = [
     "ksim_emit_cycle_json", "ksim_eval_pod_filter", "ksim_eval_pod_finish",
     "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_set_bound_pod_pdbs", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
-    "ksim_fw_filter_nominated", "ksim_preempt_nominated",
+    "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -109,6 +109,8 @@ def _load(path):
         L.ksim_set_bound_pod_pdbs.argtypes = [vp, i32, vp, vp, vp]
     L.ksim_preempt.argtypes = [vp, vp, i32, i32, vp]
     L.ksim_preempt_nominated.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    if hasattr(L, "ksim_preempt_spread"):       # likewise
+        L.ksim_preempt_spread.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -420,28 +422,35 @@ class Engine:
         self._chk(self.L.ksim_set_bound_pod_pdbs(self.h, int(allowed.size), *(a.ctypes.data_as(ctypes.c_void_p)
                                                                               for a in (allowed, off, ids))))
 
-    def preempt(self, pods, index: int, priority: int, groups=None, with_pdb: bool = False) -> tuple:
+    def preempt(self, pods, index: int, priority: int, groups=None, with_pdb: bool = False,
+                hard_spread: bool = False) -> tuple:
         """DefaultPreemption PostFilter dry run: (nominated node or -1, victim
         indices into the bound-pod table in the dry run's list order, potential
         nodes, candidates kept); ``with_pdb`` appends the nominated node's
         victims that violate a PodDisruptionBudget (n_pdb_violations).
         ``groups`` = [(node, [indices of ``pods``]), ...]: the PodNominator's
-        pods of priority >= ``priority`` per node (ksim_preempt_nominated)."""
+        pods of priority >= ``priority`` per node (ksim_preempt_nominated).
+        ``hard_spread``: the dry run through ksim_preempt_spread, which also
+        takes a pod with DoNotSchedule spread constraints (the table then
+        needs every class of its rows: ``bound_table(..., full_adds=True)``);
+        off, such a pod is refused (KSIM_E_UNSUPPORTED)."""
         self._sync()
         self._ran = True
         out = abi.PreemptOut(max(getattr(self, "_bound_n", 1), 1))
         result = out.result_with_pdb if with_pdb else out.result
         ps = pods.pod_set()
-        if not groups:
+        if not groups and not hard_spread:
             self._chk(self.L.ksim_preempt(self.h, ctypes.byref(ps), index, priority, ctypes.byref(out.c)))
+            return result()
+        call = self.L.ksim_preempt_spread if hard_spread else self.L.ksim_preempt_nominated
+        if not groups:
+            self._chk(call(self.h, ctypes.byref(ps), index, priority, None, 0, None, None, None, ctypes.byref(out.c)))
             return result()
         nodes, first, count, order = _nominated_groups(groups)
         sub = pods.subset_indices(order)      # kept alive: the pod set points into it
         nps = sub.pod_set()
-        self._chk(self.L.ksim_preempt_nominated(self.h, ctypes.byref(ps), index, priority, ctypes.byref(nps),
-                                                len(nodes), *(a.ctypes.data_as(ctypes.c_void_p)
-                                                              for a in (nodes, first, count)),
-                                                ctypes.byref(out.c)))
+        self._chk(call(self.h, ctypes.byref(ps), index, priority, ctypes.byref(nps), len(nodes),
+                       *(a.ctypes.data_as(ctypes.c_void_p) for a in (nodes, first, count)), ctypes.byref(out.c)))
         return result()
 
     def match_terms(self, mp: abi.MatchProblem, n_words: int, counts: Optional[np.ndarray]) -> np.ndarray:

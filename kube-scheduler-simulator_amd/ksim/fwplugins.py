@@ -34,7 +34,8 @@ Nominated pods (RunFilterPluginsWithNominatedPods, framework.go v1.26): the
 framework hands Filter a NodeInfo / CycleState clone carrying the node's
 nominated pods of priority >= the pod's (PreFilterExtensions.AddPod); the
 plugins answer that first pass from ksim_fw_filter_nominated, one call per
-cycle over every such node, and the dry run from ksim_preempt_nominated.
+cycle over every such node, and the dry run from ksim_preempt_nominated
+(ksim_preempt_spread when post_filter's ``hard_spread`` is set).
 
 One cycle is in flight at a time (upstream scheduleOne is serial); the wrapped
 plugins of a profile share one ``EnginePlugins``.
@@ -216,7 +217,8 @@ class EnginePlugins:
             self.b.forget(a[0], a[1], a[2])
 
     def post_filter(self, priority: int, bound=None, nominated_node: int = -1, nominated_status=None,
-                    terminating_lower=None, pdbs=None) -> Tuple[Status, int, List[int], bool]:
+                    terminating_lower=None, pdbs=None, hard_spread: bool = False
+                    ) -> Tuple[Status, int, List[int], bool]:
         """DefaultPreemption.PostFilter (default_preemption.go v1.26):
         PodEligibleToPreemptOthers, then the dry run over this cycle's
         nominated groups.  Returns (status, nominated node or -1, victim
@@ -231,7 +233,9 @@ class EnginePlugins:
         bound pod's required anti-affinity term matches, needs every class
         the bound pods count into: the same call with ``full_adds=True``.
         Pods with DoNotSchedule spread are refused (KsimError,
-        KSIM_E_UNSUPPORTED).  ``pdbs``: (allowed, off, ids), the
+        KSIM_E_UNSUPPORTED) unless ``hard_spread`` is set: the dry run then
+        goes through ksim_preempt_spread, which re-runs PodTopologySpread on
+        each node's moved domain counts (the ``full_adds=True`` table).  ``pdbs``: (allowed, off, ids), the
         PodDisruptionBudgets over the table's rows, set on the engine before
         the dry run (Engine.set_bound_pod_pdbs)."""
         if nominated_node >= 0 and (nominated_status is None or
@@ -241,10 +245,11 @@ class EnginePlugins:
                                               "nominated node."), -1, [], False)
         if pdbs is not None:
             self.b.set_bound_pod_pdbs(*pdbs)
+        kw = {"hard_spread": True} if hard_spread else {}
         if bound is None:
-            node, victims = self.b.preempt(self._pods, self._idx, priority, groups=self._groups)[:2]
+            node, victims = self.b.preempt(self._pods, self._idx, priority, groups=self._groups, **kw)[:2]
         else:
-            node, victims = self.b.preempt(self._pods, self._idx, priority, bound, groups=self._groups)[:2]
+            node, victims = self.b.preempt(self._pods, self._idx, priority, bound, groups=self._groups, **kw)[:2]
         if node < 0:
             return Status(UNSCHEDULABLE, "preemption: no candidate node"), -1, [], True
         return Status(), int(node), list(victims), True

@@ -175,7 +175,7 @@ def record_cycle(store: Store, cluster: EncodedCluster, prof: SchedulerProfile, 
 
 
 def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: SchedulerProfile, pods, index: int,
-                 priority: int = 0, bound=None, pdbs=None) -> Dict:
+                 priority: int = 0, bound=None, pdbs=None, hard_spread: bool = False) -> Dict:
     """One deterministic compat cycle as the wrapped plugins see it: the cycle
     (ksim_eval_pod), then for an unschedulable pod DefaultPreemption's
     PostFilter dry run (ksim_preempt over the bound-pod table set with
@@ -186,7 +186,9 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     after ``pods`` was compiled); for a pod with required pod (anti-)affinity,
     or one a bound pod's required anti-affinity term matches, every class they
     count into (``full_adds=True``).  A pod with DoNotSchedule spread is refused
-    (KSIM_E_UNSUPPORTED)."""
+    (KSIM_E_UNSUPPORTED) unless ``hard_spread`` is set: the dry run then goes
+    through ksim_preempt_spread (``Engine.preempt(..., hard_spread=True)``),
+    which re-runs PodTopologySpread too and needs the ``full_adds=True`` table."""
     res = backend.eval_pod(pods, index) if hasattr(backend, "eval_pod") else backend.cycle(pods, index)
     nominated = -1
     post = [original_name(p.name) for p in prof.plugins["postFilter"].enabled]
@@ -195,8 +197,9 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
         if not (names is not None and len(names) == 0):
             if pdbs is not None:
                 backend.set_bound_pod_pdbs(*pdbs)
-            out = backend.preempt(pods, index, priority) if bound is None else \
-                backend.preempt(pods, index, priority, bound)
+            kw = {"hard_spread": True} if hard_spread else {}
+            out = backend.preempt(pods, index, priority, **kw) if bound is None else \
+                backend.preempt(pods, index, priority, bound, **kw)
             nominated = int(out[0])
     res["nominated"] = nominated
     ns, name = pods.names[index]

@@ -12,17 +12,24 @@ anti-affinity term against app=x: every node is a potential node (Fit fails
 first), each runs the domain form of the dry run, and the 50 holders' nodes are
 the candidates.  The table carries every row's class contributions.
 
+--spread: --anti's cluster (50 zones, an app=x pod of priority 10 on each
+zone's first node) and a preemptor that is an x pod with one DoNotSchedule
+constraint (maxSkew 1 on the zone over app=x): every node is a potential node
+(Fit fails first), each runs the spread form of the dry run through
+ksim_preempt_spread (one more small launch, k_preempt_spread_mins), and every
+node is a candidate.
+
 --pdbs K: K PodDisruptionBudgets with disruptionsAllowed 1 over the table,
 the bound pods of node v in budget v % K (ksim_set_bound_pod_pdbs), so all but
 the most important lower-priority pod of a node violate: the call takes the
-PDB form of the kernels.  With --anti too.
+PDB form of the kernels.  With --anti or --spread too.
 
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti] [--pdbs K]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread] [--pdbs K]
 """
 import argparse
 import json
@@ -40,7 +47,7 @@ import numpy as np  # noqa: E402
 
 from ksim import abi, engine, profile  # noqa: E402
 from ksim.encode import encode_cluster, encode_pods  # noqa: E402
-from ksim.model import Container, LabelSelector, Node, Pod, PodAffinityTerm  # noqa: E402
+from ksim.model import Container, LabelSelector, Node, Pod, PodAffinityTerm, TopologySpreadConstraint  # noqa: E402
 
 ZONE, N_ZONES = "topology.kubernetes.io/zone", 50
 
@@ -67,8 +74,9 @@ def build(n_nodes: int):
     return cluster, table, enc, prof
 
 
-def build_anti(n_nodes: int):
-    """build()'s load on N_ZONES zones, an app=x pod per zone, the anti-affine preemptor."""
+def build_anti(n_nodes: int, spread: bool = False):
+    """build()'s load on N_ZONES zones, an app=x pod per zone, the anti-affine
+    preemptor (``spread``: the one with a DoNotSchedule zone constraint)."""
     from ksim.preemption import bound_table
     rng = np.random.default_rng(7)
     nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}", ZONE: f"z{i % N_ZONES:02d}"},
@@ -82,10 +90,15 @@ def build_anti(n_nodes: int):
                              containers=[Container({"cpu": "2400m"})]))
             start[bound[-1].name] = int(rng.integers(0, 1000))
     cluster, _ = encode_cluster(nodes, bound)
-    pod = Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})],
-              pod_anti_affinity_required=[PodAffinityTerm(ZONE, LabelSelector({"app": "x"}))])
+    if spread:
+        pod = Pod("preemptor", priority=1000, labels={"app": "x"}, containers=[Container({"cpu": "2000m"})],
+                  topology_spread=[TopologySpreadConstraint(1, ZONE, "DoNotSchedule", LabelSelector({"app": "x"}))])
+    else:
+        pod = Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})],
+                  pod_anti_affinity_required=[PodAffinityTerm(ZONE, LabelSelector({"app": "x"}))])
     enc = encode_pods(cluster, [pod])
-    assert int(enc.pods[0]["use_count"]) == 1 and int(enc.uses["kind"][0]) == abi.USE_IPA_ANTI
+    assert int(enc.pods[0]["use_count"]) == 1
+    assert int(enc.uses["kind"][0]) == (abi.USE_PTS_HARD if spread else abi.USE_IPA_ANTI)
     table = bound_table(cluster, bound, start, cluster.topo, full_adds=True)
     prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
     return cluster, table, enc, prof
@@ -108,9 +121,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
+    ap.add_argument("--spread", action="store_true", help="a preemptor with a DoNotSchedule zone spread constraint")
     ap.add_argument("--pdbs", type=int, default=0, help="this many budgets (disruptionsAllowed 1), each bound pod in one")
     args = ap.parse_args()
-    cluster, table, enc, prof = (build_anti if args.anti else build)(args.nodes)
+    if args.anti and args.spread:
+        ap.error("--anti or --spread, not both")
+    cluster, table, enc, prof = build_anti(args.nodes, args.spread) if args.anti or args.spread else build(args.nodes)
+    kw = dict(hard_spread=True) if args.spread else {}
     budgets = None
     if args.pdbs > 0:
         budgets = (np.ones(args.pdbs, np.int32), np.arange(table.n + 1, dtype=np.int32),
@@ -124,16 +141,16 @@ def main():
         if budgets is not None:
             eng.set_bound_pod_pdbs(*budgets)
         for _ in range(args.warmup):
-            result = eng.preempt(enc, 0, 1000, with_pdb=True) if budgets is not None else eng.preempt(enc, 0, 1000)
+            result = eng.preempt(enc, 0, 1000, with_pdb=budgets is not None, **kw)
         us = []
         for _ in range(args.calls):
             t0 = time.perf_counter()
-            eng.preempt(enc, 0, 1000)
+            eng.preempt(enc, 0, 1000, **kw)
             us.append((time.perf_counter() - t0) * 1e6)
         eng.close()
         runs.append(summary(us))
         every += us
-    name = ("preempt_zone_anti" if args.anti else "preempt_use_free") + ("_pdb" if budgets is not None else "")
+    name = ("preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else "preempt_use_free") + ("_pdb" if budgets is not None else "")
     extra = dict(pdbs=args.pdbs, pdb_violations=result[4]) if budgets is not None else {}
     print(json.dumps(dict(bench=name, library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
                           bound_pods=table.n, calls=args.calls, repeats=args.repeats,
