@@ -749,9 +749,25 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * out[27] batch runs of this handle that took the request-class table (the
  * pods of a loaded queue that share their resource requests share a class,
  * and a long enough P100 run reads each class's verdict and scores per node
- * from a table instead of computing them per pod), since ksim_create.
+ * from a table instead of computing them per pod), since ksim_create;
+ * out[28..32] the deferred-commit batch runs' host loop since ksim_create
+ * (it enqueues batches while none can start past the end of the run, from
+ * the progress word the batches' state writers store to host-mapped memory):
+ * [28] host synchronisations inside those runs, [29] batches enqueued past
+ * the end of their run, [30] stretches that ended with a flush and a
+ * synchronised state read instead (the word did not move by the deadline, or
+ * KSIM_FEED_FLUSH=1 in the environment asks for that form of every stretch),
+ * [31] top-ups: the times batches were enqueued behind a run's first stretch,
+ * [32] runs whose last flush had an odd ring index, so that the end launch
+ * copied the second snapshot buffer back to the handle's own.
  * Returns the number of values written (<= n). */
 int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n);
+/* The deferred-commit runs' enqueue rule (host arithmetic, no device): with
+ * `left` pods behind the last commit the host has seen and `pending` batches
+ * enqueued that start at or after it, how many more batches may be enqueued
+ * with none starting past the end of the run (a batch commits at most B pods:
+ * ceil(left / B) - pending, never below 0). */
+int32_t ksim_feed_more_batches(int32_t left, int32_t pending);
 /* Batch-path geometry compiled into the library: out[0] pods per batch (B),
  * out[1] candidate keys kept per pod (T), out[2] nodes per wave tile,
  * out[3] keys a tile keeps per pod.  Returns the number written (<= n). */

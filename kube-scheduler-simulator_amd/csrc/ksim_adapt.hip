@@ -1194,6 +1194,7 @@ __global__ __launch_bounds__(256) void k_adapt_mask_commit(DevCluster c, DevPods
     __builtin_memcpy(wd, &ns, sizeof(ns));
 #pragma unroll
     for (int q = 0; q < kWords; q++) reinterpret_cast<uint64_t*>(L.st_out)[q] = wd[q];
+    if (L.prog) *L.prog = lazy_progress(ns.cursor, ns.batches);   // run_lazy's feeder polls it
     if (FLUSH) *L.e_self = -1;
   }
   // this thread's node: S_i row = X[p ^ 1] + delta; written to X[p] by the

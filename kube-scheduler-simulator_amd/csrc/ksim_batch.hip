@@ -1121,6 +1121,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     __builtin_memcpy(w, &ns, sizeof(ns));
 #pragma unroll
     for (int q = 0; q < kWords; q++) reinterpret_cast<uint64_t*>(L.st_out)[q] = w[q];
+    if (L.prog) *L.prog = lazy_progress(ns.cursor, ns.batches);   // run_lazy's feeder polls it
     if (FLUSH) *L.e_self = -1;
   };
   const bool st_writer = b == 0 && tid == kThreads - 64;   // the last wave's first lane

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -293,6 +294,25 @@ struct ksim_handle {
   int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
   hipGraphExec_t graph_lazy = nullptr;
   hipGraphExec_t graph_lazy_adapt = nullptr;
+  // the tail graphs: kLazySlots batches of the same flavour, captured with and
+  // dropped with the kGraphBatches graph beside them (run_lazy's top-ups of
+  // fewer than kGraphBatches batches)
+  hipGraphExec_t graph_lazy4 = nullptr, graph_lazy4_adapt = nullptr, graph_lazy4_rt = nullptr;
+  // run_lazy's progress words (host-mapped pinned, alloc_lazy): [0] the last
+  // state writer's lazy_progress, [1] the batch counter the run started from
+  unsigned long long* prog = nullptr;
+  unsigned long long* prog_d = nullptr;
+  // ksim_schedule_loaded leaves the zeroing of the call's counters to its first
+  // run (run_range: run_lazy's begin launch takes it, every other run calls
+  // reset_counters first)
+  bool counters_pending = false;
+  // deferred-commit runs since ksim_create (ksim_get_diag out[28..32]): host
+  // synchronisations inside them, batches enqueued past the end of their run,
+  // stretches ended by a flush and a state read instead of the progress word,
+  // top-ups (batches enqueued after a run's first stretch, by the word or a
+  // read), runs whose last flush had an odd ring index (the end launch copied
+  // X[1] and st[1] back)
+  int64_t feed_syncs = 0, feed_past_end = 0, feed_fallbacks = 0, feed_topups = 0, feed_odd_ends = 0;
   // request classes of the loaded queue (ksim_internal.h ReqTab): per loaded
   // pod its class (0xffff: none), the classes' requests, and the table's two
   // halves [2][rq_ncls][dc.n] with the ring's patch entries
@@ -408,6 +428,19 @@ void drop_cycle_graphs(ksim_handle* h) {
   h->graph_gen++;
 }
 
+// A deferred-commit graph with its tail graph.
+void drop_lazy_pair(hipGraphExec_t& g, hipGraphExec_t& g4) {
+  if (g) (void)hipGraphExecDestroy(g);
+  if (g4) (void)hipGraphExecDestroy(g4);
+  g = g4 = nullptr;
+}
+
+void drop_lazy_graphs(ksim_handle* h) {
+  drop_lazy_pair(h->graph_lazy, h->graph_lazy4);
+  drop_lazy_pair(h->graph_lazy_adapt, h->graph_lazy4_adapt);
+  drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
+}
+
 void drop_graphs(ksim_handle* h) {
   drop_cycle_graphs(h);
   for (auto& kv : h->sweep_graphs)               // they hold the static columns and the queue
@@ -418,15 +451,10 @@ void drop_graphs(ksim_handle* h) {
   if (h->graph_batch_stab) (void)hipGraphExecDestroy(h->graph_batch_stab);
   h->graph_batch_stab = nullptr;
   if (h->graph_tbatch) (void)hipGraphExecDestroy(h->graph_tbatch);
-  if (h->graph_lazy) (void)hipGraphExecDestroy(h->graph_lazy);
-  if (h->graph_lazy_adapt) (void)hipGraphExecDestroy(h->graph_lazy_adapt);
-  h->graph_lazy_adapt = nullptr;
-  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
-  h->graph_lazy_rt = nullptr;
+  drop_lazy_graphs(h);
   h->graph_batch_fast = nullptr;
   h->graph_batch = nullptr;
   h->graph_tbatch = nullptr;
-  h->graph_lazy = nullptr;
 }
 
 bool plugin_supported(int id) { return id >= 0 && id < KSIM_PL_COUNT; }
@@ -927,12 +955,19 @@ bool lazy_ok(const ksim_handle* h, int32_t a, int32_t b, bool fast, bool stab = 
 int alloc_lazy(ksim_handle* h) {
   if (h->lazy_n == h->dc.n) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->graph_lazy) (void)hipGraphExecDestroy(h->graph_lazy);
-  if (h->graph_lazy_adapt) (void)hipGraphExecDestroy(h->graph_lazy_adapt);
-  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
-  h->graph_lazy = h->graph_lazy_adapt = h->graph_lazy_rt = nullptr;
+  drop_lazy_graphs(h);
   free_bufs(h->lazy_bufs);
   h->lazy_n = -1;
+  if (!h->prog) {   // kept for the handle's life: the graphs hold its address
+    hipError_t e = hipHostMalloc((void**)&h->prog, 2 * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped);
+    if (e != hipSuccess) {
+      h->prog = nullptr;
+      return hip_fail(h, e, "hipHostMalloc (progress word)");
+    }
+    h->prog[0] = h->prog[1] = 0;
+    if ((e = hipHostGetDevicePointer((void**)&h->prog_d, h->prog, 0)) != hipSuccess)
+      return hip_fail(h, e, "hipHostGetDevicePointer");
+  }
   const size_t n = (size_t)h->dc.n;
   int rc;
   void* p = nullptr;
@@ -1007,8 +1042,7 @@ int ensure_rtab(ksim_handle* h) {
   const size_t need = rtab_halves_bytes(h) + sizeof(uint16_t) * kLazySlots * (size_t)h->rq_ncls * kBatchPods;
   if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->graph_lazy_rt) (void)hipGraphExecDestroy(h->graph_lazy_rt);
-  h->graph_lazy_rt = nullptr;
+  drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
   free_bufs(h->rtab_bufs);
   h->rtab_bytes = 0;
   void* p = nullptr;
@@ -1037,6 +1071,7 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool
   z.step.g2 = h->lazy_g + (size_t)q2 * kBatchPods;
   z.step.e2 = h->lazy_e + q2;
   z.step.e_self = h->lazy_e + q;
+  z.step.prog = h->prog_d;
   z.st = st[p];
   z.gkey = h->lazy_g + (size_t)q * kBatchPods;
   z.pmax = h->lazy_m + (size_t)q * kBatchPods;
@@ -1125,9 +1160,88 @@ int reqtab_begin(ksim_handle* h, const LaunchArgs& la) {
   return KSIM_OK;
 }
 
-int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
+// run_lazy's begin in one launch (k_lazy_move): reset_counters when the call's
+// counters are still to zero, set_run and lazy_begin.
+int lazy_begin_run(ksim_handle* h, int32_t first, int32_t end, bool zero_counters) {
   int rc;
-  if ((rc = lazy_begin(h))) return rc;
+  if ((rc = alloc_lazy(h))) return rc;
+  h->run_hdr[0] = first;
+  h->run_hdr[1] = end;
+  LazyMove m{};
+  m.src = dyn_cols(h->dc);
+  m.dst = h->lazy_x1;
+  m.n = h->dc.n;
+  m.begin = 1;
+  m.zero_counters = zero_counters ? 1 : 0;
+  m.first = first;
+  m.end = end;
+  m.st_src = h->st;
+  m.st_dst = h->st;
+  m.st_dst2 = h->lazy_st1;
+  m.win = h->sc.win;
+  m.ring_e = h->lazy_e;
+  m.batches0 = h->prog_d + 1;
+  launch_lazy_move(m, h->stream);
+  HIPCHK(h, hipGetLastError());
+  return KSIM_OK;
+}
+
+// lazy_end in one launch.
+int lazy_end_run(ksim_handle* h, int64_t f) {
+  if ((f & 1) == 0) return KSIM_OK;
+  LazyMove m{};
+  m.src = h->lazy_x1;
+  m.dst = dyn_cols(h->dc);
+  m.n = h->dc.n;
+  m.st_src = h->lazy_st1;
+  m.st_dst = h->st;
+  launch_lazy_move(m, h->stream);
+  HIPCHK(h, hipGetLastError());
+  return KSIM_OK;
+}
+
+// kGraphBatches (tail: kLazySlots) batches of the flavour from ring phase 0.
+int capture_lazy(ksim_handle* h, const LaunchArgs& la, bool rt, int batches, hipGraphExec_t* out) {
+  hipGraph_t g = nullptr;
+  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  for (int i = 0; i < batches; i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
+  hipError_t e = hipStreamEndCapture(h->stream, &g);
+  if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
+  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (e != hipSuccess) {
+    *out = nullptr;
+    return hip_fail(h, e, "hipGraphInstantiate");
+  }
+  h->graph_captures++;
+  return KSIM_OK;
+}
+
+// KSIM_FEED_FLUSH=1 (read at every run): every stretch ends with a flush and
+// a synchronised state read, the loop's fallback taken unconditionally (an
+// A/B form of the same runs, and the fallback's test).
+bool feed_flush_forced() {
+  const char* v = std::getenv("KSIM_FEED_FLUSH");
+  return v && v[0] == '1';
+}
+
+// The host enqueues batches while none can start past the end, from the
+// freshest commit it knows: the state writer of every evaluation launch and of
+// every flush stores (cursor, batches) to the handle's progress word, which the
+// host polls while the device works, so the stream is topped up without a
+// flush, a state read and a synchronisation per stretch.  Only the last
+// enqueued batch, when it may end the run, is committed by a flush, whose word
+// the host waits for.  A word that does not move within the deadline (sized by
+// the launches outstanding) ends the stretch the old way: a flush, a state
+// read, a synchronisation.  zero_counters: the begin launch zeroes the call's
+// counters (run_range).
+int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la, bool zero_counters) {
+  int rc;
+  if ((rc = alloc_lazy(h))) return rc;
+  volatile unsigned long long* const word = h->prog;
+  constexpr unsigned long long kNoWord = ~0ull;     // no cursor is -1
+  word[0] = kNoWord;                                // nothing in flight writes it: every run ends waited for
+  if ((rc = lazy_begin_run(h, a, b, zero_counters))) return rc;
   // the request-class table, rebuilt from the run's starting snapshot in
   // stream order: anything may have moved X since the last run
   const bool rt = reqtab_ok(h, a, b);
@@ -1137,47 +1251,119 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
   }
   if (rt && h->graph_lazy_rt && h->rt_graph_ncls != h->rq_ncls) {   // a reloaded queue with other classes
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipGraphExecDestroy(h->graph_lazy_rt);
-    h->graph_lazy_rt = nullptr;
+    drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
   }
   hipGraphExec_t& graph = adapt_mode(h) ? h->graph_lazy_adapt : rt ? h->graph_lazy_rt : h->graph_lazy;
-  if (!graph) {
+  hipGraphExec_t& graph4 = adapt_mode(h) ? h->graph_lazy4_adapt : rt ? h->graph_lazy4_rt : h->graph_lazy4;
+  if (!graph || !graph4) {
     if (rt) h->rt_graph_ncls = h->rq_ncls;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kGraphBatches; i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
-    e = hipGraphInstantiate(&graph, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-      graph = nullptr;
-      return hip_fail(h, e, "hipGraphInstantiate");
-    }
-    h->graph_captures++;
+    drop_lazy_pair(graph, graph4);
+    if ((rc = capture_lazy(h, la, rt, kGraphBatches, &graph)) || (rc = capture_lazy(h, la, rt, kLazySlots, &graph4)))
+      return rc;
   }
   static_assert(kGraphBatches % kLazySlots == 0, "lazy graphs keep the ring phase");
-  int64_t i = 0;
-  int32_t cursor = a;
-  while (cursor < b) {
-    int32_t nb = (b - cursor + kBatchPods - 1) / kBatchPods;
+  const bool forced = feed_flush_forced();
+  int64_t i = 0;                  // the next launch's ring index (flushes take one)
+  int32_t launched = 0, done = 0; // the run's batches enqueued; committed as far as the host has seen
+  int32_t cursor = a;             // ... and the cursor after those commits
+  bool flushed = false;           // a flush is the last launch enqueued
+  unsigned long long last = kNoWord;
+  // nb more batches: single launches to the ring phase 0, whole graphs, tail
+  // graphs, single launches for the rest
+  auto enqueue = [&](int32_t nb) -> int {
     const int32_t align = (int32_t)((kLazySlots - (i & 3)) & 3);
-    if (nb >= align + kGraphBatches) {
+    if (nb >= align + kLazySlots) {
       for (int32_t r = 0; r < align; r++, i++, nb--) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
-      for (int32_t r = 0; r < nb / kGraphBatches; r++, i += kGraphBatches) HIPCHK(h, hipGraphLaunch(graph, h->stream));
-    } else {
-      for (int32_t r = 0; r < nb; r++, i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
+      launched += align;
+      for (; nb >= kGraphBatches; nb -= kGraphBatches, i += kGraphBatches, launched += kGraphBatches)
+        HIPCHK(h, hipGraphLaunch(graph, h->stream));
+      for (; nb >= kLazySlots; nb -= kLazySlots, i += kLazySlots, launched += kLazySlots)
+        HIPCHK(h, hipGraphLaunch(graph4, h->stream));
     }
-    lazy_flush(h, lazy_batch(h, la, i, rt), h->stream);
+    for (; nb > 0; nb--, i++, launched++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
     HIPCHK(h, hipGetLastError());
-    DevState st;
-    if ((rc = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return rc;
-    if (st.cursor <= cursor) return set_err(h, KSIM_E_DEVICE, "deferred-commit batch path made no progress");
-    cursor = st.cursor;
-    i++;
+    flushed = false;
+    return KSIM_OK;
+  };
+  // What the commits seen so far allow: more batches, and the flush behind the
+  // one batch outstanding when no batch may follow it before its commit is
+  // known (it may end the run; the first evaluation launch behind a flush
+  // repeats the flush's word, so the host does not wait for it).
+  auto act = [&](bool top_up) -> int {
+    const int32_t pending = launched - done;
+    const int32_t more = lazy_more_batches(b - cursor, pending, kBatchPods);
+    const int32_t align = (int32_t)((kLazySlots - (i & 3)) & 3);
+    // (a whole graph's worth at once; a tail graph's only with less than a
+    // graph still queued; single launches only when the stream is about to run dry)
+    if (more > 0 && (more >= align + kGraphBatches || (more >= align + kLazySlots && pending <= kGraphBatches - kLazySlots) ||
+                     pending <= 2)) {
+      if (int r = enqueue(more)) return r;
+      if (top_up) h->feed_topups++;
+    }
+    if (!forced && !flushed && launched - done == 1 && lazy_more_batches(b - cursor, 1, kBatchPods) == 0) {
+      lazy_flush(h, lazy_batch(h, la, i, rt), h->stream);
+      HIPCHK(h, hipGetLastError());
+      i++;
+      flushed = true;
+    }
+    return KSIM_OK;
+  };
+  if ((rc = act(false))) return rc;
+  while (cursor < b) {
+    // the word's next value, or none by the deadline
+    bool news = false;
+    if (!forced) {
+      const auto deadline = std::chrono::steady_clock::now() +
+                            std::chrono::milliseconds(50 + 5 * (int64_t)(launched - done + 1));
+      for (uint32_t spin = 1;; spin++) {
+        const unsigned long long w = word[0];
+        if (w != last) {
+          last = w;
+          news = true;
+          break;
+        }
+        if ((spin & 1023) == 0) {
+          // a wait far longer than a batch: an error ends the loop, with no
+          // launch behind it (no query on the usual path: it may enqueue a
+          // marker behind the batches)
+          if ((spin & 16383) == 0) {
+            const hipError_t q = hipStreamQuery(h->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) return hip_fail(h, q, "hipStreamQuery");
+          }
+          if (std::chrono::steady_clock::now() > deadline) break;
+        }
+        __builtin_ia32_pause();
+      }
+    }
+    if (news) {
+      cursor = (int32_t)(last >> 32);
+      done = (int32_t)((uint32_t)last - (uint32_t)word[1]);
+    } else {
+      // the stretch ends with a flush and a state read (none behind an error)
+      if (!forced) {
+        const hipError_t q = hipStreamQuery(h->stream);
+        if (q != hipSuccess && q != hipErrorNotReady) return hip_fail(h, q, "hipStreamQuery");
+      }
+      lazy_flush(h, lazy_batch(h, la, i, rt), h->stream);
+      HIPCHK(h, hipGetLastError());
+      DevState st;
+      if ((rc = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return rc;
+      h->feed_syncs++;
+      h->feed_fallbacks++;
+      i++;
+      flushed = true;
+      last = word[0];
+      if (st.cursor <= cursor) return set_err(h, KSIM_E_DEVICE, "deferred-commit batch path made no progress");
+      cursor = st.cursor;
+      done = launched;
+    }
+    if (cursor < b && (rc = act(true))) return rc;
   }
-  return lazy_end(h, i - 1);
+  if (!flushed) return set_err(h, KSIM_E_DEVICE, "deferred-commit run ended without its flush");
+  h->feed_past_end += launched - done;
+  h->feed_odd_ends += (i - 1) & 1;
+  return lazy_end_run(h, i - 1);
 }
 
 // ---- packed policy sweep (ksim_sweep_loaded; ksim_internal.h SweepLane) -------
@@ -1433,14 +1619,27 @@ int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lan
   return KSIM_OK;
 }
 
+int reset_counters(ksim_handle* h, hipStream_t stream);
+
 // Run pods [a, b) on one path (all of them share the path).
 int run_range(ksim_handle* h, int32_t a, int32_t b, bool batch, bool topo) {
   int rc;
-  if ((rc = set_run(h, a, b))) return rc;
   // No launch is ever issued past the end of the run (a launch there would
   // exit at once and skew per-kernel averages): whole graphs while they fit,
   // then single launches for the remainder.
   LaunchArgs la = make_args(h, h->dp, h->d_chosen);
+  // the call's counters are zeroed before its first run: by a deferred-commit
+  // run's begin launch, which sets the run header too, or on their own
+  const bool zero = h->counters_pending;
+  h->counters_pending = false;
+  if (batch && !topo) {
+    // the FAST evaluation kernel when every pod of the run is trivial with
+    // cpu/memory scoring, or is in a static class (STAB)
+    pick_keys(h, a, b, la);
+    if (lazy_ok(h, a, b, la.fast, la.stab)) return run_lazy(h, a, b, la, zero);
+  }
+  if (zero && (rc = reset_counters(h, h->stream))) return rc;
+  if ((rc = set_run(h, a, b))) return rc;
   if (!batch) {
     la.fuse_min = topo;
     for (int32_t i = a; i < b && la.fuse_min; i++) la.fuse_min = h->hard_small[i] != 0;
@@ -1457,10 +1656,6 @@ int run_range(ksim_handle* h, int32_t a, int32_t b, bool batch, bool topo) {
     return KSIM_OK;
   }
   if (topo) return run_tbatch(h, a, b, la);
-  // the FAST evaluation kernel when every pod of the run is trivial with
-  // cpu/memory scoring, or is in a static class (STAB)
-  pick_keys(h, a, b, la);
-  if (lazy_ok(h, a, b, la.fast, la.stab)) return run_lazy(h, a, b, la);
   hipGraphExec_t& gb = la.stab ? h->graph_batch_stab : la.fast ? h->graph_batch_fast : h->graph_batch;
   if (!gb && (rc = capture(h, true, false, &gb, la.fast, false, false, false, la.stab))) return rc;
   // every batch commits between 1 and kBatchPods pods: a graph of
@@ -2197,6 +2392,7 @@ void ksim_destroy(ksim_handle* h) {
   for (auto& a : h->fw_arena)
     if (a.p) (void)hipFree(a.p);
   if (h->fwh) (void)hipHostFree(h->fwh);
+  if (h->prog) (void)hipHostFree(h->prog);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->pout) (void)hipHostFree(h->pout);
   free_bufs(h->pre_bufs);
@@ -4346,17 +4542,22 @@ int ksim_schedule_loaded(ksim_handle* h, int32_t first, int32_t count, int32_t* 
   if (first < 0 || count < 0 || first + count > h->dp.n_pods) return set_err(h, KSIM_E_INVALID, "range out of loaded pods");
   HIPCHK(h, hipSetDevice(h->device));
   if ((rc = ensure_stab(h))) return rc;
-  if ((rc = reset_counters(h, h->stream))) return rc;
+  // the counters start from zero: an unsharded call's first run zeroes them
+  // (run_range; a deferred-commit run does it in its begin launch)
+  const bool defer_zero = !is_sharded(h) && count > 0;
+  if (!defer_zero && (rc = reset_counters(h, h->stream))) return rc;
   int64_t perpod = 0;
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   if (is_sharded(h)) {
     for (int32_t i = first; i < first + count; i++) perpod += pod_on_batch(h, i) ? 0 : 1;
     rc = shard_schedule({h}, first, count);
   } else {
+    h->counters_pending = defer_zero;
     rc = for_each_run(h, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
       if (!batch) perpod += b - a;
       return run_range(h, a, b, batch, topo);
     });
+    h->counters_pending = false;
   }
   if (rc) return rc;
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
@@ -4589,7 +4790,9 @@ int ksim_schedule_batch(ksim_handle* h, const ksim_pod_set* ps, int32_t* chosen,
 int ksim_reset_cluster(ksim_handle* h) {
   if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
   if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "cluster not set");
-  h->stab_dirty = true;
+  // the static table stays: k_static_table reads a node's flags, taints and
+  // labels (static_filters_pass, count_intolerable_prefer, pref_term_mask),
+  // none of the columns restored here
   HIPCHK(h, hipSetDevice(h->device));
   const size_t N = (size_t)h->dc.n;
   const DevCluster& c = h->dc;
@@ -4831,7 +5034,7 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   DevState st;
   int rc = read_state(h, st);
   if (rc) return rc;
-  int64_t v[3 + 16 + 2 + 4 + 3] = {st.batches, st.truncations, st.cuts};
+  int64_t v[3 + 16 + 2 + 4 + 3 + 5] = {st.batches, st.truncations, st.cuts};
   if (h->has_cluster) HIPCHK(h, hcopy(h, v + 3, h->sc.dbg, 8 * 16, hipMemcpyDeviceToHost));
   if (unsigned long long* cp = cp_clock_buffer())   // KSIM_CP_CLOCKS builds: the chain + pairs phase clocks
     HIPCHK(h, hcopy(h, v + 3, cp, 8 * 8, hipMemcpyDeviceToHost));
@@ -4843,9 +5046,18 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   v[25] = (int64_t)batch_variant_reach();
   if (h->has_cluster && h->sc.tb_vpods) HIPCHK(h, hcopy(h, v + 26, h->sc.tb_vpods, 8, hipMemcpyDeviceToHost));
   v[27] = h->rtab_runs;
-  const int32_t m = n < 28 ? n : 28;
+  v[28] = h->feed_syncs;
+  v[29] = h->feed_past_end;
+  v[30] = h->feed_fallbacks;
+  v[31] = h->feed_topups;
+  v[32] = h->feed_odd_ends;
+  const int32_t m = n < 33 ? n : 33;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
+}
+
+extern "C" int32_t ksim_feed_more_batches(int32_t left, int32_t pending) {
+  return lazy_more_batches(left, pending, kBatchPods);
 }
 
 extern "C" int ksim_batch_geometry(int32_t* out, int32_t n) {

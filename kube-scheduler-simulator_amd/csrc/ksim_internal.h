@@ -170,7 +170,23 @@ struct LazyStep {
   const uint64_t* g1; const uint64_t* m1; const int32_t* e1;   // batch i-1's slot: guesses, pair maxima, prefix
   const uint64_t* g2; const int32_t* e2;                       // batch i-2's slot: guesses, prefix
   int32_t* e_self;                                 // batch i's slot (a flush marks it empty: -1)
+  // run_lazy's progress word (host-mapped, null: none): the state writer
+  // stores lazy_progress(cursor, batches) of the state it wrote
+  unsigned long long* prog = nullptr;
 };
+// The progress word: the cursor after the launch's commit above the handle's
+// batch counter (DevState::batches, which counts committed batches).
+__host__ __device__ inline unsigned long long lazy_progress(int32_t cursor, int32_t batches) {
+  return ((unsigned long long)(uint32_t)cursor << 32) | (uint32_t)batches;
+}
+// How many more batches run_lazy may enqueue without one starting past the
+// end: `left` pods remain after the last commit the host has seen and
+// `pending` enqueued batches start at or after it; a batch commits at most
+// kBatchPods pods, so ceil(left / kBatchPods) batches never pass the end.
+constexpr int32_t lazy_more_batches(int32_t left, int32_t pending, int32_t batch_pods) {
+  // ((left - 1) / B + 1: no overflow near INT32_MAX)
+  return left <= 0 ? 0 : ((left - 1) / batch_pods + 1 > pending ? (left - 1) / batch_pods + 1 - pending : 0);
+}
 struct LazyBatch {
   LaunchArgs a;        // a.c: static columns + X[p ^ 1]
   DevCluster cw;       // static columns + X[p]
@@ -376,6 +392,25 @@ struct ResetList {
   }
 };
 void launch_reset_copy(const ResetList& L, hipStream_t stream);
+// run_lazy's begin and end in one launch each (k_lazy_move): the six dynamic
+// columns dst = src by element (any n, any alignment) and the state.
+// begin: st_dst and st_dst2 receive st_src with the run header (first, end),
+// bcap zeroed and, zero_counters set, the call's counters zeroed; the window
+// state zeroed, every ring slot emptied and the batch counter the run starts
+// from stored to *batches0 (the progress word's base, host-mapped).
+// End (begin = 0): st_dst = st_src.
+struct LazyMove {
+  DynCols src, dst;
+  int32_t n;
+  int32_t begin, zero_counters, first, end;
+  const DevState* st_src;
+  DevState* st_dst;
+  DevState* st_dst2;
+  WinState* win;
+  int32_t* ring_e;                                 // [kLazySlots]
+  unsigned long long* batches0;
+};
+void launch_lazy_move(const LazyMove& m, hipStream_t stream);
 
 // Selector / term matching as an int8 contraction (ksim_match.hip, ksim_match_terms).
 constexpr int kMatchMaxReqs = 4096;     // requirement columns (LDS: 16 rows x 4096 bits)

@@ -1147,6 +1147,55 @@ void launch_reset_copy(const ResetList& L, hipStream_t stream) {
   k_reset_copy<<<blocks, 256, 0, stream>>>(L);
 }
 
+// The start or the end of a deferred-commit run in one launch (LazyMove; one
+// dispatch instead of reset_counters' four fills, set_run's copy and two
+// fills and lazy_begin's seven copies and one fill, or lazy_end's seven
+// copies).  The columns move by element, so no size or alignment is special.
+__global__ __launch_bounds__(256) void k_lazy_move(LazyMove m) {
+  const int32_t stride = (int32_t)(gridDim.x * blockDim.x);
+  const int32_t t0 = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  for (int32_t i = t0; i < m.n; i += stride) {
+    const int64_t a = m.src.req_cpu[i], b = m.src.req_mem[i], c = m.src.req_eph[i], d = m.src.nz_cpu[i],
+                  e = m.src.nz_mem[i];
+    const int32_t f = m.src.num_pods[i];
+    m.dst.req_cpu[i] = a;
+    m.dst.req_mem[i] = b;
+    m.dst.req_eph[i] = c;
+    m.dst.nz_cpu[i] = d;
+    m.dst.nz_mem[i] = e;
+    m.dst.num_pods[i] = f;
+  }
+  if (m.begin) {
+    static_assert(sizeof(WinState) % 4 == 0, "WinState by words");
+    for (int32_t i = t0; i < (int32_t)(sizeof(WinState) / 4); i += stride) reinterpret_cast<uint32_t*>(m.win)[i] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < kLazySlots) m.ring_e[threadIdx.x] = -1;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    DevState s = *m.st_src;
+    if (m.begin) {
+      s.cursor = m.first;
+      s.end = m.end;
+      s.bcap = 0;
+      if (m.zero_counters) {
+        s.truncations = 0;
+        s.evals = 0;
+        s.scheduled = 0;
+        s.unschedulable = 0;
+        s.batches = 0;
+        s.cuts = 0;
+      }
+      *m.st_dst2 = s;
+      if (m.batches0) *m.batches0 = (unsigned long long)(uint32_t)s.batches;
+    }
+    *m.st_dst = s;
+  }
+}
+
+void launch_lazy_move(const LazyMove& m, hipStream_t stream) {
+  const int blocks = std::min(256, std::max(1, (m.n + 255) / 256));
+  k_lazy_move<<<blocks, 256, 0, stream>>>(m);
+}
+
 __global__ void k_assume(DevCluster c, DevPods P, int32_t pod, int32_t node, int sign) {
   if (threadIdx.x == 0 && blockIdx.x == 0) assume_pod(c, P, P.pods[pod], node, sign);
 }

@@ -36,7 +36,7 @@ EXPORTS = [
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
     "ksim_encoder_bind", "ksim_encoder_unbind", "ksim_encoder_bound_node", "ksim_encoder_changed_rows",
-    "ksim_update_node_rows",
+    "ksim_update_node_rows", "ksim_feed_more_batches",
 ]
 
 
@@ -131,6 +131,9 @@ def _load(path):
     L.ksim_time_eval.argtypes = [vp, i32, i32, vp, vp]
     L.ksim_kernel_name.restype = ctypes.c_char_p
     L.ksim_get_diag.argtypes = [vp, vp, i32]
+    if hasattr(L, "ksim_feed_more_batches"):    # an addition within ABI 12: detected by symbol
+        L.ksim_feed_more_batches.argtypes = [i32, i32]
+        L.ksim_feed_more_batches.restype = i32
     L.ksim_batch_geometry.argtypes = [vp, i32]
     L.ksim_set_shard.argtypes = [vp, i32, i32]
     L.ksim_comm_unique_id.argtypes = [vp]
@@ -546,15 +549,20 @@ class Engine:
 
     def diag(self) -> dict:
         """Batch-path diagnostics of the last schedule_loaded call."""
-        out = np.zeros(28, np.int64)
-        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 28)
+        out = np.zeros(33, np.int64)
+        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 33)
         if n < 0:
             self._chk(n)
         d = {"batches": int(out[0]), "truncations": int(out[1]), "cuts": int(out[2]),
              "graph_captures": int(out[19]), "dbg": [int(x) for x in out[3:19]], "match_ns": int(out[20]),
              "fw_score_host": int(out[21]), "fw_score_device": int(out[22]), "fw_normalize_cached": int(out[23]),
              "fw_normalize_device": int(out[24]), "variants": int(out[25]), "tb_variant_pods": int(out[26]),
-             "reqtab_runs": int(out[27])}
+             "reqtab_runs": int(out[27]),
+             # the deferred-commit runs' host loop: synchronisations inside the runs, batches
+             # enqueued past a run's end, stretches ended by flush + state read, top-ups,
+             # runs that ended on the second snapshot buffer
+             "feed_syncs": int(out[28]), "feed_past_end": int(out[29]), "feed_fallbacks": int(out[30]),
+             "feed_topups": int(out[31]), "feed_odd_ends": int(out[32])}
         if out[6]:
             d["chain_us"] = {"setup": out[3] / out[6] / 100.0, "rounds": out[4] / out[6] / 100.0,
                              "epilogue": out[5] / out[6] / 100.0, "rounds_per_batch": out[7] / out[6]}
