@@ -879,6 +879,39 @@ struct UpRow {
   int32_t alloc_pods, node;                        // node -1: no row
 };
 
+// a pod record (ksim_internal.h PodRec) as its three 16-byte words
+__device__ __forceinline__ PodRec load_rec(const PodRec* __restrict__ p) {
+  const uint4* __restrict__ w = reinterpret_cast<const uint4*>(p);
+  const uint4 a = w[0], b = w[1], c = w[2];
+  auto i64 = [](uint32_t lo, uint32_t hi) { return (int64_t)(((uint64_t)hi << 32) | lo); };
+  PodRec r;
+  r.req = PodReq{i64(a.x, a.y), i64(a.z, a.w), i64(b.x, b.y), i64(b.z, b.w), i64(c.x, c.y)};
+  r.cls = (uint16_t)c.z;
+  r.valid = (uint16_t)(c.z >> 16);
+  r._pad = 0;
+  return r;
+}
+__device__ __forceinline__ void store_rec(PodRec* __restrict__ p, const PodRec& r) {
+  auto lo = [](int64_t x) { return (uint32_t)(uint64_t)x; };
+  auto hi = [](int64_t x) { return (uint32_t)((uint64_t)x >> 32); };
+  uint4* __restrict__ w = reinterpret_cast<uint4*>(p);
+  w[0] = make_uint4(lo(r.req.cpu), hi(r.req.cpu), lo(r.req.mem), hi(r.req.mem));
+  w[1] = make_uint4(lo(r.req.eph), hi(r.req.eph), lo(r.req.nzc), hi(r.req.nzc));
+  w[2] = make_uint4(lo(r.req.nzm), hi(r.req.nzm), (uint32_t)r.cls | ((uint32_t)r.valid << 16), 0u);
+}
+// ... of loaded pod q of a run that ends at `end`
+__device__ __forceinline__ PodRec pod_rec(const DevPods& P, const uint16_t* __restrict__ rcls, int32_t q,
+                                          int32_t end) {
+  PodRec r{};
+  if (q < end) {
+    const ksim_pod& y = P.pods[q];
+    r.req = PodReq{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem};
+    r.cls = rcls[q];
+    r.valid = 1;
+  }
+  return r;
+}
+
 // The launch's body (k_batch_top_commit, and the packed sweep's
 // k_sweep_top_commit with a lane's buffers).
 // RT (KEEP, DEF, DIRECT; ksim_internal.h ReqTab): the block's pod takes its
@@ -942,15 +975,30 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   // depend on cur0): pod tid of batch i-1 (its request, kept if committed) and
   // the candidates cur0 + pod0 + t for this block's pods of batch i
   ResCols rq{0, 0, 0, 0, 0, 0};
-  for (int x = tid; x < 2 * kBatchPods + (NS ? kNsPods : 1); x += kThreads) {
-    const int32_t q = x < kBatchPods ? cur0 + x : cur0 + pod0 + (x - kBatchPods);
-    if (q < end) {
-      const ksim_pod& y = P.pods[q];
-      if (x < kBatchPods) {
-        rq = ResCols{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem, 1};
+  if constexpr (RT) {
+    // ... as the records the launch before this one wrote once it knew cur0
+    // (ReqTab::h_in): record x, and b + t for candidate t, at addresses that
+    // do not wait for the state (a record past the end: zero, no class)
+    static_assert(2 * kBatchPods + 1 <= kThreads, "one record per thread");
+    if (tid < 2 * kBatchPods + 1) {
+      const PodRec r = load_rec(rt.h_in + (tid < kBatchPods ? tid : b + (tid - kBatchPods)));
+      if (tid < kBatchPods) {
+        rq = ResCols{r.req.cpu, r.req.mem, r.req.eph, r.req.nzc, r.req.nzm, (int32_t)r.valid};
       } else {
-        s_pc[x - kBatchPods] = PodReq{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem};
-        if constexpr (RT && !FLUSH) s_cls[x - kBatchPods] = rt.rcls[q];
+        s_pc[tid - kBatchPods] = r.req;
+        s_cls[tid - kBatchPods] = r.valid ? r.cls : kNoClass;
+      }
+    }
+  } else {
+    for (int x = tid; x < 2 * kBatchPods + (NS ? kNsPods : 1); x += kThreads) {
+      const int32_t q = x < kBatchPods ? cur0 + x : cur0 + pod0 + (x - kBatchPods);
+      if (q < end) {
+        const ksim_pod& y = P.pods[q];
+        if (x < kBatchPods) {
+          rq = ResCols{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem, 1};
+        } else {
+          s_pc[x - kBatchPods] = PodReq{y.req_cpu, y.req_mem, y.req_eph, y.nz_cpu, y.nz_mem};
+        }
       }
     }
   }
@@ -994,6 +1042,10 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   const int32_t base = cur0 + committed;
   const int32_t pi = base + pod0;
   const bool live = !FLUSH && pi < min(end, base + kBatchPods);   // block-uniform
+  // RT: the block's two records for the next launch, by six otherwise idle
+  // lanes, one 8-byte word each (write_records)
+  const int rl = tid - (kThreads - 128);            // the last wave but one's first lanes: word rl
+  const bool rec_writer = RT && rl >= 0 && rl < (int)(sizeof(PodRec) / 8);
   lds_barrier();
 #ifdef KSIM_TC_CLOCKS
   tp[2] = __builtin_amdgcn_s_memrealtime();
@@ -1125,6 +1177,27 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     if (FLUSH) *L.e_self = -1;
   };
   const bool st_writer = b == 0 && tid == kThreads - 64;   // the last wave's first lane
+  // RT: H[p] records b (this block's own pod of batch i, which it holds as
+  // candidate `committed`) and kBatchPods + b, off the critical path like the
+  // state.  Pod base + kBatchPods + b is new to the device's caches, so it is
+  // loaded here, behind the merge: issued when base was known (one lane's
+  // scalar loads, which every LDS wait of the wave waits for) it held the
+  // whole block at the next barrier.
+  auto write_records = [&]() {
+    if constexpr (RT) {
+      static_assert(offsetof(ksim_pod, req_cpu) == 0 && offsetof(ksim_pod, nz_mem) == 32, "ksim_pod starts as PodReq");
+      const int32_t q = base + kBatchPods + b;
+      uint64_t rec2 = 0;
+      if (q < end)
+        rec2 = rl < 5 ? reinterpret_cast<const uint64_t*>(&P.pods[q])[rl] : ((uint64_t)rt.rcls[q] | (1ull << 16));
+      uint64_t own = 0;
+      if (pi < end)
+        own = rl < 5 ? reinterpret_cast<const uint64_t*>(&s_pc[committed])[rl]
+                     : ((uint64_t)s_cls[committed] | (1ull << 16));
+      reinterpret_cast<uint64_t*>(rt.h_out + b)[rl] = own;
+      reinterpret_cast<uint64_t*>(rt.h_out + kBatchPods + b)[rl] = rec2;
+    }
+  };
   // the overlay delta of a node (zero when batch i-1 did not bind it)
   auto delta = [&](int32_t node) -> ResCols {
     if constexpr (DIRECT) {
@@ -1199,6 +1272,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
       lds_barrier();
       upkeep();
     }
+    if (rec_writer) write_records();
     if (st_writer) update_state();
     return;
   }
@@ -1376,7 +1450,8 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
     top_finish<kThreads>(a, nfeas, b, topk, topk_cnt, topk_complete, xsend);
 #endif
   upkeep();                                   // (top_finish's barriers follow materialize())
-  if (st_writer) update_state();              // waves past the first return from the merge early
+  if (rec_writer) write_records();            // waves past the first return from the merge early
+  if (st_writer) update_state();
   }
 }
 
@@ -1524,6 +1599,19 @@ __global__ __launch_bounds__(256) void k_req_table(DevCluster c, const BatchProg
 
 void launch_req_table(const LaunchArgs& a, const ReqTab& rt, uint16_t* t0, uint16_t* t1, hipStream_t stream) {
   k_req_table<<<dim3((a.c.n + 255) / 256, rt.n_cls), 256, 0, stream>>>(a.c, a.dbp, rt, t0, t1);
+}
+
+// The pod records a run's first evaluation launch reads (ReqTab::h_in of batch
+// 0): pods first + [0, 2 * kBatchPods), one thread each.
+__global__ __launch_bounds__(kBatchPods) void k_req_records(DevPods P, const uint16_t* __restrict__ rcls,
+                                                            int32_t first, int32_t end, PodRec* __restrict__ out) {
+  const int32_t x = blockIdx.x * kBatchPods + threadIdx.x;
+  store_rec(out + x, pod_rec(P, rcls, first + x, end));
+}
+
+void launch_req_records(const LaunchArgs& a, const ReqTab& rt, int32_t first, int32_t end, PodRec* out,
+                        hipStream_t stream) {
+  k_req_records<<<2, kBatchPods, 0, stream>>>(a.P, rt.rcls, first, end, out);
 }
 
 const char* const kLazyKernelNames[kKernelsPerLazy] = {"k_batch_top_commit", "k_batch_chain_pairs"};

@@ -1033,13 +1033,17 @@ bool reqtab_ok(const ksim_handle* h, int32_t a, int32_t b) {
 
 // The table's two halves for the handle's cluster, then (at a 256-byte step)
 // the ring's patch entries P[kLazySlots][C][kBatchPods]; a reallocation drops
-// the graph that holds their addresses (ensure_stab's rule).
+// the graph that holds their addresses (ensure_stab's rule).  Behind them (a
+// slot is a multiple of 512 bytes) the pod records H[2][2 * kBatchPods].
 size_t rtab_halves_bytes(const ksim_handle* h) {
   const size_t t = 2 * sizeof(uint16_t) * (size_t)h->rq_ncls * (size_t)h->dc.n;
   return (t + 255) & ~(size_t)255;
 }
+size_t rtab_patch_bytes(const ksim_handle* h) {
+  return sizeof(uint16_t) * kLazySlots * (size_t)h->rq_ncls * kBatchPods;
+}
 int ensure_rtab(ksim_handle* h) {
-  const size_t need = rtab_halves_bytes(h) + sizeof(uint16_t) * kLazySlots * (size_t)h->rq_ncls * kBatchPods;
+  const size_t need = rtab_halves_bytes(h) + rtab_patch_bytes(h) + sizeof(PodRec) * 2 * 2 * kBatchPods;
   if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
@@ -1094,6 +1098,10 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool
     const size_t slot = (size_t)h->rq_ncls * kBatchPods;
     z.rt.p_in = pe + (size_t)q1 * slot;
     z.rt.p_out = pe + (size_t)q * slot;
+    // the pod records: batch i's evaluation launch reads batch i-1's and writes its own
+    PodRec* const rec = (PodRec*)((char*)pe + rtab_patch_bytes(h));
+    z.rt.h_in = rec + (size_t)(p ^ 1) * 2 * kBatchPods;
+    z.rt.h_out = rec + (size_t)p * 2 * kBatchPods;
   }
   return z;
 }
@@ -1151,12 +1159,15 @@ void lazy_flush(const ksim_handle* h, const LazyBatch& z, hipStream_t stream) {
   else launch_lazy_flush(z, stream);
 }
 
-// Both halves of the table from the run's starting snapshot (lazy_begin done).
-int reqtab_begin(ksim_handle* h, const LaunchArgs& la) {
+// Both halves of the table from the run's starting snapshot (lazy_begin done),
+// and the pod records batch 0's evaluation launch reads: those of the run's
+// first pods (nothing in H is kept from an earlier run).
+int reqtab_begin(ksim_handle* h, const LaunchArgs& la, int32_t first, int32_t end) {
   int rc;
   if ((rc = ensure_rtab(h))) return rc;
   const LazyBatch z0 = lazy_batch(h, la, 0, true);
   launch_req_table(la, z0.rt, z0.rt.t_out, const_cast<uint16_t*>(z0.rt.t_in), h->stream);
+  launch_req_records(la, z0.rt, first, end, const_cast<PodRec*>(z0.rt.h_in), h->stream);
   return KSIM_OK;
 }
 
@@ -1247,7 +1258,7 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la, bool ze
   const bool rt = reqtab_ok(h, a, b);
   if (rt) {
     h->rtab_runs++;
-    if ((rc = reqtab_begin(h, la))) return rc;
+    if ((rc = reqtab_begin(h, la, a, b))) return rc;
   }
   if (rt && h->graph_lazy_rt && h->rt_graph_ncls != h->rq_ncls) {   // a reloaded queue with other classes
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4853,7 +4864,7 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
     // end takes it: the launch the timing stands for)
     if ((rc = lazy_begin(h))) return rc;
     const bool rt = reqtab_ok(h, first, h->dp.n_pods);
-    if (rt && (rc = reqtab_begin(h, a))) return rc;
+    if (rt && (rc = reqtab_begin(h, a, first, end))) return rc;
     launch_batch_lazy(lazy_batch(h, a, 0, rt), h->stream);
     const LazyBatch z = lazy_batch(h, a, 1, rt);
     launch_lazy_top(z, h->stream);
@@ -4946,7 +4957,7 @@ int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_
       HIPCHK(h, hipMemsetAsync(&h->st->batches, 0, 4, h->stream));
       if ((r = lazy_begin(h))) return r;
       const bool rt = reqtab_ok(h, lo, hi);
-      if (rt && (r = reqtab_begin(h, a))) return r;
+      if (rt && (r = reqtab_begin(h, a, lo, hi))) return r;
       int64_t i = 0;
       int32_t cursor = lo, done_batches = 0;
       while (cursor < hi) {

@@ -153,7 +153,21 @@ struct DynCols {
 // i + 1's evaluation launch reads its class's row of that slot, entry t under
 // t < i* <= chain_end only, so a stale slot or a stale tail is never selected.
 // Only the node that takes two pods at a cut is keyed in the evaluation launch.
+// The pod records H[2][2 * kBatchPods] ride the batch parity like st[] / X[]:
+// batch i's evaluation launch, once it knows where batch i starts (base),
+// writes the records of pods base + [0, 2 * kBatchPods) into H[p] (block b its
+// own pod base + b and pod base + kBatchPods + b), and batch i + 1's reads its
+// 2 * kBatchPods + 1 records (batch i's requests, its own candidates) from
+// there, at addresses that do not depend on the state's cursor.  A flush
+// writes them too; reqtab_begin fills H[1] at a run's start.
 constexpr int kReqMaxClasses = 256;
+struct alignas(16) PodRec {
+  PodReq req;                                      // zero past the run's end
+  uint16_t cls, valid;                             // request class; 1: the pod is before the run's end
+  uint32_t _pad;
+};
+static_assert(sizeof(PodRec) == 48, "pod record: three 16-byte words");
+constexpr uint16_t kNoClass = 0xffff;              // s_cls of a record past the run's end
 struct ReqTab {
   const uint16_t* t_in = nullptr;                  // T[p ^ 1], [n_cls][n]
   uint16_t* t_out = nullptr;                       // T[p]
@@ -161,6 +175,8 @@ struct ReqTab {
   const uint16_t* rcls = nullptr;                  // [n_pods] class of each loaded pod
   const uint16_t* p_in = nullptr;                  // P[(i - 1) & 3], [n_cls][kBatchPods]: batch i-1's patch entries
   uint16_t* p_out = nullptr;                       // P[i & 3]: batch i's, written by its pairs launch
+  const PodRec* h_in = nullptr;                    // H[p ^ 1]: the records batch i-1's evaluation launch wrote
+  PodRec* h_out = nullptr;                         // H[p]: batch i's, for batch i+1
   int32_t n_cls = 0, _pad = 0;
 };
 struct LazyStep {
@@ -243,6 +259,9 @@ void launch_static_table(const LaunchArgs& a, const int32_t* rep, int32_t n_cls,
 uint32_t launch_batch_lazy(const LazyBatch& z, hipStream_t stream, hipEvent_t* evs = nullptr);
 // both halves of the request-class table from the snapshot a.c (k_req_table)
 void launch_req_table(const LaunchArgs& a, const ReqTab& rt, uint16_t* t0, uint16_t* t1, hipStream_t stream);
+// the pod records of pods first + [0, 2 * kBatchPods) of a run that ends at `end` (k_req_records)
+void launch_req_records(const LaunchArgs& a, const ReqTab& rt, int32_t first, int32_t end, PodRec* out,
+                        hipStream_t stream);
 void launch_lazy_flush(const LazyBatch& z, hipStream_t stream);
 // the evaluation-launch instantiations launched so far (ksim_get_diag out[25])
 uint64_t batch_variant_reach();
