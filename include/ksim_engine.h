@@ -101,7 +101,8 @@ enum ksim_plugin {
 #define KSIM_POD_HAS_REQUIRED_AFFINITY   2u  /* spec.affinity.nodeAffinity.required != nil */
 #define KSIM_POD_HAS_SCALAR              4u  /* len(request.ScalarResources) > 0 */
 #define KSIM_POD_HAS_HOST_PORTS          8u  /* ports not compiled to KSIM_USE_NODE_PORT uses -> KSIM_E_UNSUPPORTED */
-#define KSIM_POD_HAS_VOLUMES            16u  /* unsupported by the engine -> KSIM_E_UNSUPPORTED */
+#define KSIM_POD_HAS_VOLUMES            16u  /* unsupported by the engine -> KSIM_E_UNSUPPORTED (volumes the host did
+                                                not compile: inline disks, ...; counted PVs become KSIM_USE_VOLUME uses) */
 /* NodeAffinity's PreFilterResult (nodeaffinity.PreFilter: the union over the
  * required terms of the intersection of each term's metadata.name In
  * matchFields; a term without one means all nodes, i.e. no flag).  The cycle
@@ -339,6 +340,15 @@ typedef struct ksim_pod {
 #define KSIM_USE_IPA_SCORE_HARD     6
 #define KSIM_USE_NODE_PORT          7   /* NodePorts: the node must hold no pod of class cls (col unused) */
 #define KSIM_USE_IMAGE              8   /* ImageLocality: raw score = class count (per node, static) */
+/* Node volume limits (EBSLimits / GCEPDLimits / AzureDiskLimits /
+ * NodeVolumeLimits; see "Node volume limits" at ksim_set_volume_limits): the
+ * pod holds volumes of family `col` (a family index, not a label column).
+ * cls >= 0: one volume other pods hold as well, class_count[cls][node] = the
+ * pods on the node holding it, arg = 1.  cls = -1: `arg` volumes no other pod
+ * known to the host holds.  The use is also the pod's contribution once bound:
+ * volume classes never appear in ksim_class_add. */
+#define KSIM_USE_VOLUME             9
+#define KSIM_MAX_VOL_FAMILIES       8   /* limit keys (attachable-volumes-*) per cluster */
 #define KSIM_USEF_SELF_MATCH        1u   /* PTS: constraint selector matches the pod itself */
 #define KSIM_USEF_HONOR_AFFINITY    2u   /* PTS: nodeAffinityPolicy Honor (default) */
 #define KSIM_USEF_HONOR_TAINTS      4u   /* PTS: nodeTaintsPolicy Honor (default Ignore) */
@@ -508,6 +518,38 @@ int ksim_get_node_state(ksim_handle* h, int64_t* req_cpu, int64_t* req_mem, int6
 int ksim_get_nb_alloc(ksim_handle* h, int64_t* out);
 /* Read back the count classes [n_classes][n_nodes] (PodTopologySpread / InterPodAffinity state). */
 int ksim_get_class_count(ksim_handle* h, int32_t* out);
+/* Node volume limits ([upstream] v1.26.2 nodevolumelimits/non_csi.go and
+ * csi.go, restated from memory).  A family is one limit key: the three in-tree
+ * ones (attachable-volumes-aws-ebs / -gce-pd / -azure-disk, owned by EBSLimits
+ * / GCEPDLimits / AzureDiskLimits) and one per CSI driver some node publishes
+ * attachable-volumes-csi-<driver> for (NodeVolumeLimits; csiNode is nil and CSI
+ * migration is off: the export carries no CSINode objects).
+ *   family_plugin[f]   the KSIM_PL_*_LIMITS plugin owning family f
+ *   limit[f][node]     the node's limit; INT32_MAX: none (a CSI family on a
+ *                      node without the key).  The host resolves allocatable
+ *                      and upstream's defaults (KUBE_MAX_PD_VOLS is not modelled).
+ *   attached[f][node]  distinct family-f volumes of the pods on the node
+ * Filter of plugin P for a pod, per family f of P the pod has a
+ * KSIM_USE_VOLUME use of:
+ *   new = sum over those uses: cls >= 0 ? (class_count[cls][node] == 0) : arg
+ *   in-tree: fail when attached + new > limit (also with new == 0)
+ *   CSI:     fail when new > 0 and attached + new > limit
+ * in 64 bits; status Unschedulable, "node(s) exceed max volume count",
+ * detail 0.  The plugins run only for pods with such uses.  A bind (the cycle's
+ * own, ksim_assume / ksim_forget, a queued Reserve, ksim_fw_filter_nominated's
+ * assume / forget) adds the sign to each class use's count, and to attached
+ * when that count leaves or reaches 0; a classless use moves attached by arg.
+ * Call after ksim_set_cluster (a new snapshot drops the table; n_families 0
+ * drops it as well); the loaded queue is dropped.  ksim_reset_cluster restores
+ * `attached`.  Pods with such uses take the per-pod cycle.  KSIM_E_INVALID: a
+ * volume use without a table or with a family >= n_families.
+ * KSIM_E_UNSUPPORTED: the preemption dry runs for such a preemptor; shard and
+ * replicated handles; ksim_upsert_nodes / ksim_remove_node /
+ * ksim_update_node_rows while a table is set. */
+int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* family_plugin, const int32_t* limit,
+                           const int32_t* attached);
+/* Read back attached [n_families][n_nodes]. */
+int ksim_get_volume_attached(ksim_handle* h, int32_t* out);
 int ksim_get_next_start(ksim_handle* h, int32_t* next_start);
 int ksim_set_next_start(ksim_handle* h, int32_t next_start);
 /* Pod sequence number used by the tie-break (advances once per cycle). */

@@ -76,6 +76,13 @@ struct DevCluster {
   // the FAST batch kernels divide by them (div_rn)
   const double* inv_cpu;
   const double* inv_mem;
+  // Node volume limits (ksim_set_volume_limits; vol_nf == 0: no table).
+  // vol_plug: four bits per family, its plugin as id - KSIM_PL_EBS_LIMITS.
+  // vol_attached follows every bind of a pod with KSIM_USE_VOLUME uses.
+  int32_t vol_nf;
+  uint32_t vol_plug;
+  const int32_t* vol_limit;      // [vol_nf][n]; INT32_MAX: no limit
+  int32_t* vol_attached;         // [vol_nf][n] distinct volumes of the family on the node
 };
 
 // DevCluster.cflags
@@ -981,10 +988,11 @@ constexpr uint8_t kUseUniqueCol = 0x80;
 
 // The use's per-node number is the node's own class count (no domain table):
 // PodTopologySpread ScheduleAnyway on hostname (upstream counts the node's
-// pods), NodePorts, ImageLocality, and InterPodAffinity on a unique column.
+// pods), NodePorts, ImageLocality, node volume limits, and InterPodAffinity on
+// a unique column.
 __host__ __device__ __forceinline__ bool use_node_count(const ksim_topo_use& u) {
   return (u.kind == KSIM_USE_PTS_SOFT && (u.flags & KSIM_USEF_HOSTNAME)) || u.kind == KSIM_USE_NODE_PORT ||
-         u.kind == KSIM_USE_IMAGE ||
+         u.kind == KSIM_USE_IMAGE || u.kind == KSIM_USE_VOLUME ||
          ((u.flags & kUseUniqueCol) && u.kind >= KSIM_USE_IPA_EXISTING_ANTI && u.kind <= KSIM_USE_IPA_SCORE_HARD);
 }
 
@@ -1012,7 +1020,7 @@ struct UseMasks {
   uint32_t dom;                  // k_topo_prefilter fills the use's domain table (use_needs_dom, and adds)
   uint32_t honor_aff, honor_taints;   // PTS nodeAffinityPolicy / nodeTaintsPolicy Honor
   uint32_t ptab;                 // dom uses read from a persistent table (kPlanPtab pods)
-  uint32_t _pad;
+  uint32_t vol;                  // KSIM_USE_VOLUME uses (device copies: family in _pad, col none)
 };
 
 // Per-pod plan of the per-pod cycle, compiled by the host when a pod set is
@@ -1062,6 +1070,8 @@ __device__ __forceinline__ uint32_t ipa_filter(const UseMasks& m, const ksim_pod
 __device__ __forceinline__ int64_t ipa_score(const ksim_profile& prof, const ksim_topo_use* U, const UseMasks& m,
                                              const TopoRow& t);
 __device__ __forceinline__ bool node_port_conflict(const UseMasks& m, const TopoRow& t);
+__device__ __forceinline__ uint32_t volume_limit_fails(const DevCluster& c, const ksim_topo_use* U, const UseMasks& m,
+                                                       const TopoRow& t, int32_t node);
 __device__ __forceinline__ int64_t image_locality_score(const UseMasks& m, const TopoRow& t);
 
 // U / m / t: the pod's uses (p.use_count of them), their masks and the node's TopoRow.
@@ -1106,6 +1116,13 @@ __device__ __forceinline__ uint8_t run_filter_plugins(const DevCluster& c, const
       }
       case KSIM_PL_NODE_PORTS:
         if (nu && node_port_conflict(m, t)) return (uint8_t)f;
+        break;
+      case KSIM_PL_EBS_LIMITS:
+      case KSIM_PL_GCEPD_LIMITS:
+      case KSIM_PL_NODE_VOLUME_LIMITS:
+      case KSIM_PL_AZURE_DISK_LIMITS:
+        if (m.vol && ((volume_limit_fails(c, U, m, t, node) >> (prof_filter(prof, f) - KSIM_PL_EBS_LIMITS)) & 1u))
+          return (uint8_t)f;
         break;
       case KSIM_PL_POD_TOPOLOGY_SPREAD: {
         const uint32_t why = nu ? pts_filter(U, m, min_match, t) : 0;
@@ -1155,6 +1172,9 @@ __device__ __forceinline__ int64_t score_plugin_raw(const DevCluster& c, const D
 // only the plugins that can matter for this pod on this cluster (uniform bits),
 // then pick the first failure by profile position: the same result, because
 // the filter plugins are pure.
+static_assert(KSIM_PL_GCEPD_LIMITS == KSIM_PL_EBS_LIMITS + 1 && KSIM_PL_NODE_VOLUME_LIMITS == KSIM_PL_EBS_LIMITS + 2 &&
+              KSIM_PL_AZURE_DISK_LIMITS == KSIM_PL_EBS_LIMITS + 3, "the four limit plugins are consecutive ids");
+constexpr uint32_t kVolumeLimitPlugins = 15u << KSIM_PL_EBS_LIMITS;
 struct FilterPlan {
   uint64_t rank_lo, rank_hi;   // profile position of each plugin id, 5 bits each (ids 0..11 | 12..)
   uint32_t en;                 // plugin ids to evaluate (1 << id)
@@ -1189,7 +1209,11 @@ inline uint32_t plan_filter_en(const ksim_profile& prof, const ksim_pod& p, cons
       case KSIM_PL_NETWORK_BANDWIDTH: on = true; break;
       case KSIM_PL_VOLUME_BINDING: on = p.vb_count > 0; break;
       case KSIM_PL_VOLUME_ZONE: on = p.vz_count > 0; break;
-      default: break;    // the other volume plugins pass (bound PVCs of unlimited kinds)
+      case KSIM_PL_EBS_LIMITS:
+      case KSIM_PL_GCEPD_LIMITS:
+      case KSIM_PL_NODE_VOLUME_LIMITS:
+      case KSIM_PL_AZURE_DISK_LIMITS: on = m.vol != 0; break;   // volume_limit_fails names the owner of each family
+      default: break;    // VolumeRestrictions passes (ReadWriteOncePod is refused by the host)
     }
     if (on) en |= 1u << pl;
   }
@@ -1255,6 +1279,12 @@ __device__ __forceinline__ uint8_t run_filter_plan(const DevCluster& c, const De
     take(KSIM_PL_NODE_RESOURCES_FIT, bits != 0, bits, false);
   }
   if (fp.en & (1u << KSIM_PL_NODE_PORTS)) take(KSIM_PL_NODE_PORTS, node_port_conflict(m, t), 0, false);
+  if (fp.en & kVolumeLimitPlugins) {               // pods with KSIM_USE_VOLUME uses only
+    const uint32_t bad = volume_limit_fails(c, U, m, t, node);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (fp.en & (1u << (KSIM_PL_EBS_LIMITS + k))) take(KSIM_PL_EBS_LIMITS + k, (bad >> k) & 1u, 0, false);
+  }
   if (fp.en & (1u << KSIM_PL_POD_TOPOLOGY_SPREAD)) {
     const uint32_t why = pts_filter(U, m, min_match, t);
     take(KSIM_PL_POD_TOPOLOGY_SPREAD, why != 0, why, false);
@@ -1423,6 +1453,7 @@ __host__ __device__ __forceinline__ UseMasks use_masks(const ksim_profile& prof,
     if (ipa_coef(prof, u) != 0) m.score |= b;
     if (u.kind == KSIM_USE_NODE_PORT) m.port |= b;
     if (u.kind == KSIM_USE_IMAGE) m.image |= b;
+    if (u.kind == KSIM_USE_VOLUME) m.vol |= b;
     if (use_node_count(u)) m.node_count |= b;
     if (u.flags & KSIM_USEF_SELF_MATCH) m.self_match |= b;
     if (u.flags & KSIM_USEF_HONOR_AFFINITY) m.honor_aff |= b;
@@ -1463,6 +1494,37 @@ __device__ __forceinline__ bool node_port_conflict(const UseMasks& m, const Topo
   for (int i = 0; i < KSIM_MAX_USES; i++)
     if (((m.port >> i) & 1u) && t.x[i] > 0) hit = true;
   return hit;
+}
+
+// nodevolumelimits Filter (non_csi.go / csi.go), per family f the pod has a
+// volume of: new = the pod's family-f volumes not attached to the node (a class
+// use counts when the node holds no pod of the class, a classless use brings
+// arg volumes nobody else holds); an in-tree family fails when
+// attached + new > limit, a CSI family when new > 0 as well.  Returns the
+// failing plugins, bit = id - KSIM_PL_EBS_LIMITS.  The uses are the device
+// copies (family in _pad); 64-bit sums, INT32_MAX = no limit.
+__device__ __forceinline__ uint32_t volume_limit_fails(const DevCluster& c, const ksim_topo_use* U, const UseMasks& m,
+                                                       const TopoRow& t, int32_t node) {
+  uint32_t bad = 0;
+  for (int f = 0; f < c.vol_nf; f++) {
+    int64_t add = 0;
+    bool has = false;
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      if (!((m.vol >> i) & 1u)) continue;
+      const ksim_topo_use u = load_use(U, i);
+      if (u._pad != f) continue;
+      has = true;
+      add += u.cls >= 0 ? (t.x[i] == 0 ? 1 : 0) : (int64_t)u.arg;
+    }
+    if (!has) continue;
+    const uint32_t pl = (c.vol_plug >> (4 * f)) & 15u;
+    const int64_t limit = c.vol_limit[(size_t)f * c.n + node];
+    const int64_t total = (int64_t)c.vol_attached[(size_t)f * c.n + node] + add;
+    const bool csi = pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS);
+    if (limit != 2147483647 && total > limit && (!csi || add > 0)) bad |= 1u << pl;
+  }
+  return bad;
 }
 
 // imagelocality Score: calculatePriority(sumImageScores) depends only on the
@@ -2029,9 +2091,32 @@ __device__ __forceinline__ void row_add_pod(NodeRow& r, const ksim_pod& p, int s
   r.num_pods += sign;
 }
 
+// NodeInfo.AddPod / RemovePod on the node's attached volumes (one thread; only
+// with a volume table, so other clusters read no use here): a class use moves
+// its class count, and the family's distinct count when that leaves or reaches
+// 0; a classless use moves the family's count by its arg.
+__device__ __forceinline__ void volume_bind(const DevCluster& c, const DevPods& P, const ksim_pod& p, int32_t node,
+                                            int sign) {
+  if (!c.vol_nf) return;
+  for (int i = 0; i < p.use_count; i++) {
+    const ksim_topo_use u = P.uses[p.use_first + i];
+    if (u.kind != KSIM_USE_VOLUME || (uint32_t)u._pad >= (uint32_t)c.vol_nf) continue;
+    int32_t* att = c.vol_attached + (size_t)u._pad * c.n + node;
+    if (u.cls < 0) {
+      *att += sign * u.arg;
+      continue;
+    }
+    int32_t* cnt = c.cnt + (size_t)u.cls * c.n + node;
+    const int32_t old = *cnt;
+    *cnt = old + sign;
+    if (sign > 0 ? old == 0 : old == 1) *att += sign;
+  }
+}
+
 __device__ __forceinline__ void assume_pod(const DevCluster& c, const DevPods& P, const ksim_pod& p, int32_t node,
                                            int sign) {
   apply_adds(c, P, p, node, sign);
+  volume_bind(c, P, p, node, sign);
   c.req_cpu[node] += sign * p.req_cpu;
   c.req_mem[node] += sign * p.req_mem;
   c.req_eph[node] += sign * p.req_eph;
@@ -2081,6 +2166,7 @@ __device__ __forceinline__ void assume_pod_wave(const DevCluster& c, const DevPo
   if (lane == 4) atomic_add_i64(&c.nz_mem[node], sign * p.nz_mem);
   if (lane == 5) atomicAdd(&c.num_pods[node], sign);
   if (lane == 6 && p.nb_add) atomic_add_i64(&c.nb_alloc[node], sign * p.nb_add);
+  if (lane == 7) volume_bind(c, P, p, node, sign);
   if (lane >= 8 && lane < 8 + c.n_scalar) {
     const int k = lane - 8;
     int64_t q = 0;

@@ -118,6 +118,10 @@ struct ksim_handle {
     int32_t *num_pods, *cnt;
     int64_t* nb_alloc;
   } init{};
+  // node volume limits (ksim_set_volume_limits): limit, attached and the copy
+  // of attached that ksim_reset_cluster restores
+  std::vector<DevBuf> vol_bufs;
+  int32_t* vol_init = nullptr;
   std::vector<int32_t> col_nvals;       // host copy (pod validation)
   std::vector<uint8_t> col_unique;      // host copy of DevCluster.col_unique (kUseUniqueCol on upload)
   std::vector<uint8_t> col_total;       // per label column: every node carries the key
@@ -506,8 +510,16 @@ int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i) {
     return set_err(h, KSIM_E_INVALID, who + "bad topology use range");
   for (int32_t k = 0; k < p.use_count; k++) {
     const ksim_topo_use& u = ps->uses[p.use_first + k];
-    if (u.kind > KSIM_USE_IMAGE) return set_err(h, KSIM_E_INVALID, who + "bad topology use kind");
+    if (u.kind > KSIM_USE_VOLUME) return set_err(h, KSIM_E_INVALID, who + "bad topology use kind");
     if (u.cls < -1 || u.cls >= c.n_classes) return set_err(h, KSIM_E_INVALID, who + "topology use class out of range");
+    if (u.kind == KSIM_USE_VOLUME) {                 // col is a family index, not a label column
+      if (is_sharded(h) || h->replicated)
+        return set_err(h, KSIM_E_UNSUPPORTED, who + "volume uses run on unsharded handles");
+      if (!c.vol_nf) return set_err(h, KSIM_E_INVALID, who + "volume use without a volume table (ksim_set_volume_limits)");
+      if (u.col >= c.vol_nf) return set_err(h, KSIM_E_INVALID, who + "volume use family out of range");
+      if (u.cls < 0 ? u.arg < 1 : u.arg != 1) return set_err(h, KSIM_E_INVALID, who + "bad volume use count");
+      continue;
+    }
     if (u.col != KSIM_COL_NONE && u.col >= c.n_label_cols)
       return set_err(h, KSIM_E_INVALID, who + "topology key column out of range");
     if (u.kind == KSIM_USE_PTS_SOFT && c.n_topo_log < c.n + 1)
@@ -762,7 +774,7 @@ bool tbatch_admit(const ksim_handle* h, const ksim_pod& p, const PodPlan& pl, bo
   if (p.flags & KSIM_POD_NODE_NAMES) return false;
   if (p.vb_count > 0 || p.vz_count > 0 || profile_nb(h->prof) || p.nb_add != 0) return false;
   const UseMasks& m = pl.m;
-  if (m.port || m.soft_val || !hard_small || !soft_le1) return false;
+  if (m.port || m.vol || m.soft_val || !hard_small || !soft_le1) return false;
   const bool pt = (pl.flags & kPlanPtab) != 0;
   if ((m.dom & ~(pt ? m.ptab : 0u)) != 0) return false;     // a domain sum k_topo_prefilter would build
   if ((m.aff | m.score) != 0 && !pt) return false;         // the InterPodAffinity flags come from the tables
@@ -2388,6 +2400,7 @@ void ksim_destroy(ksim_handle* h) {
   drop_graphs(h);
   if (h->comm && rccl().ok) (void)rccl().comm_destroy(h->comm);
   free_bufs(h->cluster_bufs);
+  free_bufs(h->vol_bufs);
   free_bufs(h->scratch_bufs);
   free_bufs(h->ash_bufs);
   free_bufs(h->lazy_bufs);
@@ -2587,6 +2600,8 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   h->replicated = false;
   drop_graphs(h);
   free_bufs(h->cluster_bufs);
+  free_bufs(h->vol_bufs);               // the volume table belongs to the old snapshot (DevCluster c{} below)
+  h->vol_init = nullptr;
   free_bufs(h->scratch_bufs);
   free_bufs(h->ash_bufs);
   free_bufs(h->lazy_bufs);
@@ -2838,6 +2853,9 @@ int ksim_upsert_nodes(ksim_handle* h, const ksim_node_table* t, const ksim_vocab
   h->stab_dirty = true;
   if (!h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_upsert_nodes before ksim_set_cluster");
   if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_upsert_nodes on a shard handle");
+  if (h->dc.vol_nf)
+    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_upsert_nodes while a volume table is set (send the snapshot and "
+                                          "ksim_set_volume_limits again)");
   HIPCHK(h, hipSetDevice(h->device));
   const int32_t n = t->n_nodes, n0 = h->dc.n;
   if (n < 0 || n > KSIM_MAX_NODES) return set_err(h, KSIM_E_INVALID, "n_nodes out of range");
@@ -2928,6 +2946,9 @@ int ksim_update_node_rows(ksim_handle* h, const ksim_node_table* t, const ksim_v
   if (!h || !t || !v || n_rows < 0 || (n_rows > 0 && !rows)) return KSIM_E_INVALID;
   if (!h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_update_node_rows before ksim_set_cluster");
   if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_update_node_rows on a shard handle");
+  if (h->dc.vol_nf)
+    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_update_node_rows while a volume table is set (send the snapshot and "
+                                          "ksim_set_volume_limits again)");
   const DevCluster& c = h->dc;
   const int32_t n = c.n;
   if (t->n_nodes != n || t->n_scalar != c.n_scalar || t->n_label_cols != c.n_label_cols ||
@@ -3036,6 +3057,9 @@ int ksim_remove_node(ksim_handle* h, int32_t pos) {
   if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "cluster not set");
   h->stab_dirty = true;
   if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_remove_node on a shard handle");
+  if (h->dc.vol_nf)
+    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_remove_node while a volume table is set (send the snapshot and "
+                                          "ksim_set_volume_limits again)");
   const int32_t n0 = h->dc.n;
   if (pos < 0 || pos >= n0) return set_err(h, KSIM_E_INVALID, "node position out of range");
   h->replicated = false;                        // a new snapshot: ksim_set_eval_range again
@@ -3143,6 +3167,76 @@ int ksim_get_nb_alloc(ksim_handle* h, int64_t* out) {
   return KSIM_OK;
 }
 
+// A pod's KSIM_USE_VOLUME uses (host arrays, the ABI form).
+static bool has_volume_use(const ksim_pod_set* ps, int32_t i) {
+  if (!ps || !ps->pods || !ps->uses || i < 0 || i >= ps->n_pods) return false;
+  const ksim_pod& p = ps->pods[i];
+  if (p.use_first < 0 || p.use_count < 0 || (int64_t)p.use_first + p.use_count > ps->n_uses) return false;
+  for (int32_t k = 0; k < p.use_count; k++)
+    if (ps->uses[p.use_first + k].kind == KSIM_USE_VOLUME) return true;
+  return false;
+}
+
+int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* family_plugin, const int32_t* limit,
+                           const int32_t* attached) {
+  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
+  if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_set_volume_limits before ksim_set_cluster");
+  if (is_sharded(h) || h->replicated || h->world > 1)
+    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_set_volume_limits on a shard or replicated handle");
+  if (n_families < 0 || n_families > KSIM_MAX_VOL_FAMILIES)
+    return set_err(h, KSIM_E_INVALID, "n_families out of range");
+  const size_t N = (size_t)h->dc.n;
+  if (n_families > 0 && (!family_plugin || (N > 0 && (!limit || !attached))))
+    return set_err(h, KSIM_E_INVALID, "null volume table");
+  uint32_t plug = 0;
+  for (int32_t f = 0; f < n_families; f++) {
+    if (family_plugin[f] < KSIM_PL_EBS_LIMITS || family_plugin[f] > KSIM_PL_AZURE_DISK_LIMITS)
+      return set_err(h, KSIM_E_INVALID, "family_plugin is not a volume limit plugin");
+    plug |= (uint32_t)(family_plugin[f] - KSIM_PL_EBS_LIMITS) << (4 * f);
+  }
+  for (size_t i = 0; i < N * (size_t)n_families; i++)
+    if (limit[i] < 0 || attached[i] < 0) return set_err(h, KSIM_E_INVALID, "negative volume limit / attached count");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // the kernels take the cluster by value, and a pod's validation and plan
+  // depend on the table: captured graphs and the loaded queue go
+  drop_graphs(h);
+  h->dp = DevPods{};
+  h->batchable.clear();
+  free_bufs(h->vol_bufs);
+  h->vol_init = nullptr;
+  h->dc.vol_nf = 0;
+  h->dc.vol_plug = 0;
+  h->dc.vol_limit = nullptr;
+  h->dc.vol_attached = nullptr;
+  if (n_families == 0) return KSIM_OK;
+  const size_t bytes = 4 * N * (size_t)n_families;
+  void *dl = nullptr, *da = nullptr, *di = nullptr;
+  int rc;
+  if ((rc = upload(h, h->vol_bufs, limit, bytes, &dl)) || (rc = upload(h, h->vol_bufs, attached, bytes, &da)) ||
+      (rc = upload(h, h->vol_bufs, attached, bytes, &di))) {
+    free_bufs(h->vol_bufs);
+    return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->dc.vol_nf = n_families;
+  h->dc.vol_plug = plug;
+  h->dc.vol_limit = (const int32_t*)dl;
+  h->dc.vol_attached = (int32_t*)da;
+  h->vol_init = (int32_t*)di;
+  return KSIM_OK;
+}
+
+int ksim_get_volume_attached(ksim_handle* h, int32_t* out) {
+  if (!h || !h->has_cluster || !out) return set_err(h, KSIM_E_INVALID, "cluster not set / null out");
+  if (!h->dc.vol_nf) return set_err(h, KSIM_E_INVALID, "no volume table (ksim_set_volume_limits)");
+  if (int rc = flush_idle(h)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hcopy(h, out, h->dc.vol_attached, 4 * (size_t)h->dc.n * h->dc.vol_nf, hipMemcpyDeviceToHost));
+  return KSIM_OK;
+}
+
 int ksim_get_class_count(ksim_handle* h, int32_t* out) {
   if (!h || !h->has_cluster || !out) return set_err(h, KSIM_E_INVALID, "cluster not set / null out");
   if (int rc = flush_idle(h)) return rc;
@@ -3181,9 +3275,15 @@ int ksim_set_pod_seq(ksim_handle* h, int64_t seq) {
 
 // Device copies of topology uses carry kUseUniqueCol when their key column is
 // unique per node (ksim_device.h use_node_count).
+// A KSIM_USE_VOLUME copy carries its family in _pad and no column, so nothing
+// that walks a pod's uses reads a label column for it.
 static void mark_unique(const ksim_handle* h, ksim_topo_use* u, size_t n) {
   for (size_t i = 0; i < n; i++)
-    if (u[i].col != KSIM_COL_NONE && u[i].col < h->col_unique.size() && h->col_unique[u[i].col])
+    if (u[i].kind == KSIM_USE_VOLUME) {
+      if (u[i].col == KSIM_COL_NONE) continue;   // a copy already (validate_pod admits no such family)
+      u[i]._pad = u[i].col;
+      u[i].col = KSIM_COL_NONE;
+    } else if (u[i].col != KSIM_COL_NONE && u[i].col < h->col_unique.size() && h->col_unique[u[i].col])
       u[i].flags |= kUseUniqueCol;
 }
 
@@ -4689,6 +4789,7 @@ int ksim_set_eval_range(ksim_handle* h, int32_t eval_lo, int32_t eval_hi) {
   if (!h) return KSIM_E_INVALID;
   if (!h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_set_eval_range needs the cluster (ksim_set_cluster)");
   if (h->shard_total != 0) return set_err(h, KSIM_E_INVALID, "a node-shard handle holds only its nodes: no eval range");
+  if (h->dc.vol_nf) return set_err(h, KSIM_E_UNSUPPORTED, "a handle with a volume table (ksim_set_volume_limits) cannot be replicated");
   if (eval_lo < 0 || eval_hi < eval_lo || eval_hi > h->dc.n) return set_err(h, KSIM_E_INVALID, "bad eval range");
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   drop_cycle_graphs(h);                        // shard batch graphs captured with the old range
@@ -4712,6 +4813,8 @@ int ksim_comm_init(ksim_handle* h, int32_t rank, int32_t world, const uint8_t* i
   if (!h || !id) return KSIM_E_INVALID;
   if (world < 1 || world > kMaxShards || rank < 0 || rank >= world)
     return set_err(h, KSIM_E_INVALID, "world must be 1.." + std::to_string(kMaxShards));
+  if (h->has_cluster && h->dc.vol_nf)
+    return set_err(h, KSIM_E_UNSUPPORTED, "a handle with a volume table (ksim_set_volume_limits) cannot join a group");
   if (!rccl().ok) return set_err(h, KSIM_E_RCCL, "librccl not found");
   HIPCHK(h, hipSetDevice(h->device));
   if (h->comm) (void)rccl().comm_destroy(h->comm);
@@ -4824,6 +4927,7 @@ int ksim_reset_cluster(ksim_handle* h) {
   put(c.num_pods, h->init.num_pods, 4 * N);
   if (c.n_classes) put(c.cnt, h->init.cnt, 4 * N * c.n_classes);
   put(c.nb_alloc, h->init.nb_alloc, 8 * N);
+  if (c.vol_nf) put(c.vol_attached, h->vol_init, 4 * N * c.vol_nf);
   static_assert(sizeof(DevState) % 4 == 0, "DevState by words");
   put(h->st, nullptr, sizeof(DevState));
   HIPCHK(h, fe);
@@ -5239,6 +5343,9 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
     return set_err(h, KSIM_E_INVALID, "bad pod set / index");
   if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
     return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
+  if (has_volume_use(ps, pod_index))
+    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
+                                          "re-run the node volume limit plugins)");
   {
     std::vector<uint8_t> seen((size_t)std::max(h->dc.n, 1), 0);
     for (int32_t k = 0; k < n_groups; k++) {

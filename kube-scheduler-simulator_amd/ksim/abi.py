@@ -24,6 +24,7 @@ MAX_RES = 4
 MAX_SHAPE = 16
 MAX_USES = 16
 MAX_CLASSES = 4096
+INT32_MAX = 2**31 - 1          # ksim_set_volume_limits: no limit
 COL_NONE = 0xFFFF
 
 OK = 0
@@ -61,6 +62,10 @@ PL_TAINT_TOLERATION = 2
 PL_NODE_AFFINITY = 3
 PL_NODE_PORTS = 4
 PL_NODE_RESOURCES_FIT = 5
+PL_EBS_LIMITS = 7
+PL_GCEPD_LIMITS = 8
+PL_NODE_VOLUME_LIMITS = 9
+PL_AZURE_DISK_LIMITS = 10
 PL_POD_TOPOLOGY_SPREAD = 13
 PL_INTER_POD_AFFINITY = 14
 PL_BALANCED_ALLOCATION = 15
@@ -110,6 +115,8 @@ USE_IPA_SCORE = 5
 USE_IPA_SCORE_HARD = 6
 USE_NODE_PORT = 7
 USE_IMAGE = 8
+USE_VOLUME = 9                 # node volume limits: col = family index, cls = shared-volume class or -1, arg = count
+MAX_VOL_FAMILIES = 8
 USEF_SELF_MATCH = 1
 USEF_HONOR_AFFINITY = 2
 USEF_HONOR_TAINTS = 4

@@ -151,6 +151,7 @@ class EncodedCluster:
     topo: Optional[TopologyIndex] = None
     class_count: Optional[np.ndarray] = None          # [C][N] int32
     topo_log: Optional[np.ndarray] = None             # [N+1] float64
+    vol_limits: Optional[object] = None               # node volume limits (set_volume_limits)
     # NetworkBandwidth (ksim/netbw.py), milli-units
     nb_limit: Optional[np.ndarray] = None             # [N] int64
     nb_alloc: Optional[np.ndarray] = None             # [N] int64
@@ -170,6 +171,17 @@ class EncodedCluster:
             self.nb_limit = np.zeros(self.n_nodes, np.int64)
         if self.nb_alloc is None:
             self.nb_alloc = np.zeros(self.n_nodes, np.int64)
+
+    def set_volume_limits(self, vl) -> None:
+        """Attach a ksim.volumes.VolumeLimits compile (ksim_set_volume_limits;
+        Engine.set_cluster sends it with the snapshot): its tables in this
+        cluster's node order, and a count class per shared volume with the
+        bound pods' counts.  Call it before the pods are encoded."""
+        vl = vl.reordered(self.node_names)
+        for (f, name), counts in vl.shared.items():
+            self.topo.volume_class(vl.families[f], name, counts)
+        self.vol_limits = vl
+        self.refresh_classes()
 
     def refresh_classes(self) -> None:
         """Re-materialise class_count after classes were registered."""
@@ -572,7 +584,10 @@ def encode_pods(cluster: EncodedCluster, pods: Sequence[Pod], volumes=None, adde
     PreScore precomputation of Fit, TaintToleration and NodeAffinity).
     ``volumes``: a ksim.volumes.VolumeIndex for pods with PersistentVolumeClaims
     (VolumeBinding / VolumeZone groups); without one such pods are flagged
-    KSIM_POD_HAS_VOLUMES (the engine refuses them).
+    KSIM_POD_HAS_VOLUMES (the engine refuses them).  Claims bound to PVs a node
+    volume limit plugin counts become KSIM_USE_VOLUME uses when the cluster
+    carries the limits compile (EncodedCluster.set_volume_limits) and the
+    compile knows the pod; else the pod is flagged as well.
     ``added_affinity``: the profile's NodeAffinityArgs (ksim.profile): its
     required terms become every pod's KSIM_POD_ADDED_AFFINITY terms (one shared
     term range), its preferred terms are appended to every pod's own
@@ -658,6 +673,7 @@ def encode_pods(cluster: EncodedCluster, pods: Sequence[Pod], volumes=None, adde
         if added_count:
             flags |= abi.POD_ADDED_AFFINITY
             rec["added_term_first"], rec["added_term_count"] = added_first, added_count
+        vol_uses = None
         if p.has_volumes:
             flags |= abi.POD_HAS_VOLUMES
         elif p.pvc_claims:
@@ -665,6 +681,11 @@ def encode_pods(cluster: EncodedCluster, pods: Sequence[Pod], volumes=None, adde
             if volumes is not None:
                 try:
                     groups = volumes.groups(p)
+                    if volumes.counted_volumes(p):
+                        vl = cluster.vol_limits
+                        vol_uses = None if vl is None else vl.pod_uses.get((p.namespace, p.name))
+                        if vol_uses is None:              # counted volumes nobody compiled: refused
+                            groups = None
                 except VolumeUnsupported:
                     groups = None
             if groups is None:
@@ -695,6 +716,16 @@ def encode_pods(cluster: EncodedCluster, pods: Sequence[Pod], volumes=None, adde
             u, tflags = pod_uses(topo, cluster, p, spread)
         except TopologyError as e:
             raise EncodeError(str(e)) from e
+        if vol_uses and not flags & abi.POD_HAS_VOLUMES:
+            vl = cluster.vol_limits
+            try:
+                for f, shared, count in vol_uses:
+                    cls = -1 if shared is None else topo.volume_class(vl.families[f], shared)
+                    u.append((cls, count, f, abi.USE_VOLUME, 0))
+            except TopologyError as e:
+                raise EncodeError(str(e)) from e
+            if len(u) > abi.MAX_USES:
+                raise EncodeError(f"pod {p.name}: {len(u)} topology uses > {abi.MAX_USES}")
         rec["use_first"], rec["use_count"] = len(uses), len(u)
         uses.extend(u)
         a = topo.adds(p)

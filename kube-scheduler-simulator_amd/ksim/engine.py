@@ -36,7 +36,7 @@ EXPORTS = [
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
     "ksim_encoder_bind", "ksim_encoder_unbind", "ksim_encoder_bound_node", "ksim_encoder_changed_rows",
-    "ksim_update_node_rows", "ksim_feed_more_batches",
+    "ksim_update_node_rows", "ksim_feed_more_batches", "ksim_set_volume_limits", "ksim_get_volume_attached",
 ]
 
 
@@ -97,6 +97,9 @@ def _load(path):
     L.ksim_get_node_state.argtypes = [vp] * 7
     L.ksim_get_class_count.argtypes = [vp, vp]
     L.ksim_get_nb_alloc.argtypes = [vp, vp]
+    if hasattr(L, "ksim_set_volume_limits"):    # an addition within ABI 12: detected by symbol
+        L.ksim_set_volume_limits.argtypes = [vp, i32, vp, vp, vp]
+        L.ksim_get_volume_attached.argtypes = [vp, vp]
     L.ksim_get_next_start.argtypes = [vp, vp]
     L.ksim_set_next_start.argtypes = [vp, i32]
     L.ksim_set_pod_seq.argtypes = [vp, i64]
@@ -250,6 +253,28 @@ class Engine:
         self._chk(self.L.ksim_set_cluster(self.h, ctypes.byref(nt), ctypes.byref(vo)))
         self._track(cluster, nt)
         self._ran = False
+        self.n_vol_families = 0
+        vl = getattr(cluster, "vol_limits", None)
+        if vl is not None and len(vl.families):   # the node volume limits go with the snapshot
+            self.set_volume_limits(vl.family_plugin, vl.limit, vl.attached)
+
+    def set_volume_limits(self, family_plugin, limit, attached):
+        """ksim_set_volume_limits: family_plugin[F], limit[F][N] (abi.INT32_MAX:
+        none) and attached[F][N], after set_cluster; F = 0 drops the table."""
+        fp = np.ascontiguousarray(family_plugin, np.int32)
+        lim = np.ascontiguousarray(limit, np.int32).reshape(fp.size, -1)
+        att = np.ascontiguousarray(attached, np.int32).reshape(fp.size, -1)
+        if fp.size and (lim.shape != (fp.size, self.n_nodes) or att.shape != lim.shape):
+            raise ValueError("limit / attached must be [n_families][n_nodes]")
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._chk(self.L.ksim_set_volume_limits(self.h, int(fp.size), p(fp), p(lim), p(att)))
+        self.n_vol_families = int(fp.size)
+
+    def volume_attached(self) -> np.ndarray:
+        """attached[F][N] as the device holds it now (ksim_get_volume_attached)."""
+        out = np.zeros((getattr(self, "n_vol_families", 0), self.n_nodes), np.int32)
+        self._chk(self.L.ksim_get_volume_attached(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def _track(self, cluster, nt):
         self.cluster = cluster
@@ -303,6 +328,14 @@ class Engine:
         if int(c.class_count.shape[0]) != self._layout[1] and self._ran:
             raise RuntimeError("count classes were registered after cycles ran on this engine: "
                                "encode every pod before scheduling, or re-send the snapshot (upsert_nodes)")
+        if getattr(self, "n_vol_families", 0):
+            # a node delta is refused while a volume table is set: before any
+            # cycle the whole snapshot (and its table) goes again
+            if self._ran:
+                raise RuntimeError("label columns were added after cycles ran on an engine with a volume table: "
+                                   "encode every pod before scheduling")
+            self.set_cluster(c)
+            return
         self.upsert_nodes(c, np.arange(c.n_nodes, dtype=np.int32))
 
     def class_count(self) -> np.ndarray:

@@ -23,9 +23,12 @@ VolumeRestrictions (ksim.volumes): the PV controller's binding of Immediate
 claims at load, bound claims by PV node affinity / topology labels, unbound
 WaitForFirstConsumer claims by static matching or dynamic provisioning, and
 ReadWriteOncePod claims in use; ``schedule_queue`` runs a queue whose pods take
-PVs as they bind.  Pods with volumes the engine does not model (inline disks,
-CSI inline, ephemeral, PVs counted against node volume limits) are reported in
-``unsupported`` and left out of the queue.
+PVs as they bind.  Claims bound to EBS / GCE PD / Azure disk PVs, and to CSI PVs
+of drivers some node publishes an attachable-volumes-csi-* limit for, count
+against the node volume limits (``attach_volume_limits``; ``encode`` does it).
+Pods with volumes the engine does not model (inline disks, CSI inline,
+ephemeral, Cinder PVs, unbound WaitForFirstConsumer claims of counted classes)
+are reported in ``unsupported`` and left out of the queue.
 """
 from __future__ import annotations
 
@@ -339,11 +342,24 @@ def _pod_args(profile: Optional[prof_mod.SchedulerProfile], snap: Optional[Snaps
             "spread": SpreadDefaults(profile.spread, snap.services if snap else (), snap.controllers if snap else ())}
 
 
+def attach_volume_limits(cluster, snap: Snapshot) -> None:
+    """The node volume limits of the snapshot's bound and pending pods
+    (VolumeIndex.volume_limits) attached to its encoded cluster, so encode_pods
+    compiles the pods' volumes to uses and Engine.set_cluster sends the
+    tables.  Before the pods are encoded (``schedule_queue`` encodes them)."""
+    if snap.volumes is None:
+        return
+    vl = snap.volumes.volume_limits(snap.nodes, snap.bound, snap.pending)
+    if vl.families:
+        cluster.set_volume_limits(vl)
+
+
 def encode(snap: Snapshot, profile_index: int = 0):
     """(EncodedCluster, EncodedPods of the pending queue, compiled profile)."""
     from .encode import encode_cluster, encode_pods
     sp = snap.profiles[profile_index][1]
     cluster, _ = encode_cluster(snap.nodes, snap.bound, namespaces=snap.namespaces, nb_args=sp.network_bandwidth)
+    attach_volume_limits(cluster, snap)
     pods = encode_pods(cluster, snap.pending, volumes=snap.volumes, **_pod_args(sp, snap))
     return cluster, pods, prof_mod.compile_profile(sp, cluster.scalar_names)
 

@@ -269,6 +269,11 @@ class PersistentVolume:
     claim_ref: Optional[Tuple[str, str]] = None             # spec.claimRef (namespace, name)
     volume_mode: str = "Filesystem"                         # spec.volumeMode (nil: Filesystem)
     deleting: bool = False                                  # metadata.deletionTimestamp set
+    # what the node volume limit plugins count (ksim.volumes.volume_limits): the
+    # source's id (awsElasticBlockStore.volumeID, gcePersistentDisk.pdName,
+    # azureDisk.diskName, csi.volumeHandle) and, for csi, its driver
+    source_id: str = ""
+    csi_driver: str = ""
 
 
 @dataclass
@@ -306,15 +311,23 @@ _PV_SOURCES = ("csi", "local", "hostPath", "nfs", "awsElasticBlockStore", "gcePe
                "vsphereVolume", "flexVolume", "flocker", "quobyte", "scaleIO", "storageos", "photonPersistentDisk")
 
 
+_PV_SOURCE_ID = {"awsElasticBlockStore": "volumeID", "gcePersistentDisk": "pdName", "azureDisk": "diskName",
+                 "csi": "volumeHandle"}
+
+
 def pv_from_dict(d: dict) -> PersistentVolume:
     md, spec = d.get("metadata", {}) or {}, d.get("spec", {}) or {}
+    source = next((k for k in _PV_SOURCES if k in spec), "")
+    src = spec.get(source) or {} if source else {}
     req = ((spec.get("nodeAffinity") or {}).get("required"))
     ref = spec.get("claimRef") or None
     cap = (spec.get("capacity") or {}).get("storage")
     return PersistentVolume(
         name=md.get("name", ""), labels=dict(md.get("labels") or {}),
         node_affinity=None if req is None else [_term(t) for t in (req.get("nodeSelectorTerms") or [])],
-        source=next((k for k in _PV_SOURCES if k in spec), ""),
+        source=source,
+        source_id=str(src.get(_PV_SOURCE_ID.get(source, ""), "") or ""),
+        csi_driver=str(src.get("driver", "") or "") if source == "csi" else "",
         access_modes=list(spec.get("accessModes") or []),
         capacity=quantity_value(cap) if cap is not None else 0,
         storage_class=spec.get("storageClassName", "") or "",

@@ -93,6 +93,7 @@ class TopologyIndex:
         self.carry_ids: List[int] = []              # carried classes
         self.port_ids: List[int] = []               # host-port classes (NodePorts)
         self.image_ids: List[int] = []              # image-signature classes (ImageLocality)
+        self.vol_ids: List[int] = []                # shared-volume classes (node volume limits)
         self.images: Dict[str, Tuple[int, np.ndarray]] = {}   # image name -> (size, node mask)
         self.bound_ports: List[Tuple[int, tuple]] = []   # (node position, (ip, protocol, port)) of bound pods
         self._carry_uses: Dict[tuple, List[tuple]] = {}   # signature -> carried uses (valid for a class count)
@@ -163,8 +164,21 @@ class TopologyIndex:
         self.ids[key] = cid
         self.counts.append(counts)
         {"sel": self.sel_ids, "carry": self.carry_ids, "port": self.port_ids,
-         "image": self.image_ids}[key[0]].append(cid)
+         "image": self.image_ids, "vol": self.vol_ids}[key[0]].append(cid)
         return cid
+
+    # ---- node volume limits: a class per volume two or more pods hold ----------
+    # ("vol", limit key, unique name) counts the pods on a node holding the
+    # volume (ksim.volumes.VolumeLimits.shared).  The pods' KSIM_USE_VOLUME uses
+    # move the counts when they bind: these classes are in no pod's adds.
+    def volume_class(self, family: str, name: str, counts: Optional[np.ndarray] = None) -> int:
+        key = ("vol", family, name)
+        cid = self.ids.get(key)
+        if cid is not None:
+            return cid
+        if counts is None:
+            raise TopologyError(f"volume {name!r} of {family} has no class (EncodedCluster.set_volume_limits first)")
+        return self._new_class(key, np.asarray(counts, np.int32).copy())
 
     # ---- NodePorts: HostPortInfo as count classes -------------------------------
     # A class ("port", ip, protocol, port) counts the pods on a node using that
@@ -247,6 +261,8 @@ class TopologyIndex:
                 self.selector_class(key[1])
             elif key[0] == "port":
                 self.port_class(*key[1:])
+            elif key[0] == "vol":
+                raise TopologyError("shared-volume classes do not carry over a node delta")
             else:
                 self._image_class(key[1])
 

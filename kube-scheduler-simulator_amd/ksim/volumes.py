@@ -55,26 +55,54 @@ PreBind (``waiting``; it never binds: its bindTimeoutSeconds run out after the
 simulation).  ``provisioning=True`` models a working provisioner instead (the
 PVC is bound to a new PV of the claim's size, without node affinity).
 
+Node volume limits (EBSLimits / GCEPDLimits / AzureDiskLimits /
+NodeVolumeLimits; [upstream] nodevolumelimits/non_csi.go and csi.go, restated
+from memory): ``VolumeIndex.volume_limits`` compiles the bound claims' EBS /
+GCE PD / Azure disk / CSI PVs into families (one per limit key), per-node
+limits and attached counts, each pod's KSIM_USE_VOLUME uses and the count
+classes of the volumes two or more pods hold (ksim_engine.h "Node volume
+limits").  The export carries no CSINode objects, so csiNode is nil and CSI
+migration is off: in-tree PVs count with their in-tree plugin only, CSI PVs
+only for drivers some node publishes attachable-volumes-csi-<driver> for.
+KUBE_MAX_PD_VOLS is not modelled.
+
 Still unsupported (VolumeUnsupported: the pod is reported and not scheduled,
-never mis-scheduled): PVs counted against node volume limits (EBS / GCE PD /
-Azure disk / Cinder by their in-tree limit plugins; CSI volumes by
-NodeVolumeLimits when a node publishes attachable-volumes-* limits);
+never mis-scheduled): Cinder PVs; an unbound WaitForFirstConsumer claim whose
+class provisioner or some candidate PV is counted against a node volume limit
+(the volume's name and family would depend on the PV picked per node);
 ReadWriteOncePod claims (the ReadWriteOncePod feature gate is alpha and off in
 v1.26: the API server refuses the access mode and VolumeRestrictions skips
 the check; the reference sets no feature gates).
 """
 from __future__ import annotations
 
+import re
+from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple
+
+import numpy as np
 
 from . import abi
 from .model import (NodeSelectorTerm, PersistentVolume, PersistentVolumeClaim, Pod, Requirement, StorageClass,
-                    selector_matches)
+                    quantity_value, selector_matches)
 
 # volume_zone.go topologyLabels
 TOPOLOGY_LABELS = ("failure-domain.beta.kubernetes.io/zone", "failure-domain.beta.kubernetes.io/region",
                    "topology.kubernetes.io/zone", "topology.kubernetes.io/region")
 LIMITED_SOURCES = ("awsElasticBlockStore", "gcePersistentDisk", "azureDisk", "cinder")
+# nodevolumelimits: limit key, owning plugin, default limit, in-tree provisioner of each counted in-tree source
+VOLUME_LIMIT_PREFIX = "attachable-volumes-"
+CSI_LIMIT_PREFIX = VOLUME_LIMIT_PREFIX + "csi-"
+IN_TREE_FAMILIES = {
+    "awsElasticBlockStore": (VOLUME_LIMIT_PREFIX + "aws-ebs", abi.PL_EBS_LIMITS, 39, "kubernetes.io/aws-ebs"),
+    "gcePersistentDisk": (VOLUME_LIMIT_PREFIX + "gce-pd", abi.PL_GCEPD_LIMITS, 16, "kubernetes.io/gce-pd"),
+    "azureDisk": (VOLUME_LIMIT_PREFIX + "azure-disk", abi.PL_AZURE_DISK_LIMITS, 16, "kubernetes.io/azure-disk"),
+}
+EBS_NITRO_LIMIT = 25                               # DefaultMaxEBSNitroVolumeLimit
+EBS_NITRO_INSTANCE = re.compile(r"^[cmr]5.*|t3|z1d")   # EBSNitroLimitRegex, regexp.MatchString (a search)
+INSTANCE_TYPE_LABELS = ("node.kubernetes.io/instance-type", "beta.kubernetes.io/instance-type")
+NO_LIMIT = 2**31 - 1                               # ksim_set_volume_limits: INT32_MAX
+MSG_VOLUME_LIMIT = "node(s) exceed max volume count"   # nodevolumelimits ErrReasonMaxVolumeCountExceeded
 NO_PROVISIONER = "kubernetes.io/no-provisioner"                     # volume.NotSupportedProvisioner
 MSG_VOLUME_BINDING = "node(s) had volume node affinity conflict"    # volumebinding ErrReasonNodeConflict
 MSG_BIND_CONFLICT = "node(s) didn't find available persistent volumes to bind"   # ErrReasonBindConflict
@@ -169,6 +197,45 @@ def topology_ok(sc: StorageClass, labels: Dict[str, str]) -> bool:
     return False
 
 
+@dataclass
+class VolumeLimits:
+    """``VolumeIndex.volume_limits``: the node volume limit tables of one
+    snapshot and queue (ksim_set_volume_limits), node order = ``node_names``."""
+    node_names: List[str]
+    families: List[str]                              # limit keys, family index = position
+    family_plugin: np.ndarray                        # [F] int32 abi.PL_*_LIMITS
+    limit: np.ndarray                                # [F][N] int32, NO_LIMIT: none
+    attached: np.ndarray                             # [F][N] int32 distinct volumes of the bound pods
+    # (namespace, name) -> [(family, unique name of a shared volume or None, count)]: one entry per
+    # shared volume, at most one shared-less entry per family (count of the volumes only this pod holds)
+    pod_uses: Dict[Tuple[str, str], List[Tuple[int, Optional[str], int]]] = field(default_factory=dict)
+    # volumes two or more pods (bound or pending) hold: (family, unique name) -> pods per node [N] int32
+    shared: Dict[Tuple[int, str], np.ndarray] = field(default_factory=dict)
+
+    def reordered(self, node_names: Sequence[str]) -> "VolumeLimits":
+        """The same tables with the nodes in another order (the encoded cluster's)."""
+        if list(node_names) == self.node_names:
+            return self
+        pos = {n: i for i, n in enumerate(self.node_names)}
+        idx = np.array([pos[n] for n in node_names], np.int64)
+        return VolumeLimits(list(node_names), self.families, self.family_plugin,
+                            np.ascontiguousarray(self.limit[:, idx]), np.ascontiguousarray(self.attached[:, idx]),
+                            self.pod_uses, {k: np.ascontiguousarray(v[idx]) for k, v in self.shared.items()})
+
+
+def in_tree_limit(source: str, node) -> int:
+    """non_csi.go: the node's allocatable value for the family's key, else the
+    plugin's default (getMaxVolumeFunc; EBS by the instance-type label)."""
+    key, _, default, _ = IN_TREE_FAMILIES[source]
+    if key in node.allocatable:
+        return max(0, min(int(quantity_value(node.allocatable[key])), NO_LIMIT - 1))
+    if source == "awsElasticBlockStore":
+        itype = next((node.labels[k] for k in INSTANCE_TYPE_LABELS if node.labels.get(k)), "")
+        if itype and EBS_NITRO_INSTANCE.search(itype):
+            return EBS_NITRO_LIMIT
+    return default
+
+
 class VolumeIndex:
     """The snapshot's PVs, PVCs and StorageClasses (ResourcesForImport pvs /
     pvcs / storageClasses) and the bindings the run has made so far."""
@@ -184,13 +251,124 @@ class VolumeIndex:
         self.nodes: Optional[list] = None     # the cluster's nodes (the exact group of competing claims)
         self.provisioning = provisioning      # a provisioner acts on selected-node claims (none in the simulator)
         self.waiting: Dict[Tuple[str, str], str] = {}   # pods waiting in PreBind for provisioning -> node
+        # CSI drivers some node publishes attachable-volumes-csi-<driver> for (None: the nodes are unknown)
+        self.csi_drivers: Optional[Set[str]] = None
 
     @staticmethod
     def from_nodes(nodes, pvs=(), pvcs=(), classes=(), provisioning: bool = False) -> "VolumeIndex":
         lim = any(k.startswith("attachable-volumes-") for n in nodes for k in n.allocatable)
         v = VolumeIndex(pvs, pvcs, lim, classes, provisioning)
         v.nodes = list(nodes)
+        v.csi_drivers = {k[len(CSI_LIMIT_PREFIX):] for n in nodes for k in n.allocatable if k.startswith(CSI_LIMIT_PREFIX)}
         return v
+
+    # ---- node volume limits ------------------------------------------------------
+    def counted(self, pv: PersistentVolume) -> Optional[Tuple[str, str]]:
+        """(limit key, unique name) when a node volume limit plugin counts the
+        PV, None when none does.  VolumeUnsupported: Cinder, and a CSI PV whose
+        driver is unknown on a cluster that publishes attachable-volumes-*."""
+        if pv.source in IN_TREE_FAMILIES:
+            return IN_TREE_FAMILIES[pv.source][0], pv.source_id
+        if pv.source == "cinder":
+            raise VolumeUnsupported(f"persistentvolume {pv.name!r}: cinder volumes count against node limits")
+        if pv.source == "csi" and self.csi_limits:
+            if not pv.csi_driver or self.csi_drivers is None:
+                raise VolumeUnsupported(f"persistentvolume {pv.name!r}: csi volumes count against node limits "
+                                        f"(driver or node list unknown)")
+            if pv.csi_driver in self.csi_drivers:
+                return CSI_LIMIT_PREFIX + pv.csi_driver, f"{pv.csi_driver}/{pv.source_id}"
+        return None
+
+    def _counted_provisioner(self, provisioner: str) -> bool:
+        return provisioner in [f[3] for f in IN_TREE_FAMILIES.values()] or \
+            (self.csi_drivers is not None and provisioner in self.csi_drivers)
+
+    def counted_volumes(self, pod: Pod) -> List[Tuple[str, str]]:
+        """The pod's distinct counted volumes (limit key, unique name), through
+        its bound claims, in claim order.  A pod the index refuses
+        (VolumeUnsupported) or PreFilter rejects has none."""
+        got = self._claims(pod)
+        out: List[Tuple[str, str]] = []
+        if isinstance(got, str):
+            return out
+        for pv in got[0]:
+            c = self.counted(pv)
+            if c is not None and c not in out:
+                out.append(c)
+        return out
+
+    def volume_limits(self, nodes: Sequence, bound_pods: Iterable[Pod], pending: Iterable[Pod]) -> VolumeLimits:
+        """The node volume limit compile of ``pending`` on ``nodes`` (in the
+        order given) holding ``bound_pods``: families (the in-tree keys some
+        pod has a volume of, and the CSI keys some node publishes and some pod
+        has a volume of), their plugins, limits and attached counts, every
+        pending pod's uses, and a count class per volume two or more pods hold.
+        Pods the index refuses get no entry."""
+        names = [n.name for n in nodes]
+        pos = {n: i for i, n in enumerate(names)}
+        N = len(names)
+        held: Dict[Tuple[str, str], int] = {}                  # volume -> pods holding it
+        bound_vols, pend_vols = [], []
+        for p in bound_pods:
+            if p.node_name not in pos:
+                continue
+            try:
+                vols = self.counted_volumes(p)
+            except VolumeUnsupported:
+                continue                                         # an existing pod nobody can count: ignored, as today
+            bound_vols.append((pos[p.node_name], vols))
+        for p in pending:
+            try:
+                vols = self.counted_volumes(p)
+            except VolumeUnsupported:
+                continue
+            pend_vols.append((p, vols))
+        for _, vols in bound_vols + pend_vols:
+            for v in vols:
+                held[v] = held.get(v, 0) + 1
+        in_tree_keys = {f[0]: src for src, f in IN_TREE_FAMILIES.items()}
+        families = sorted({v[0] for v in held}, key=lambda k: (k not in in_tree_keys, k))
+        if len(families) > abi.MAX_VOL_FAMILIES:
+            raise VolumeUnsupported(f"{len(families)} volume limit keys > {abi.MAX_VOL_FAMILIES}")
+        fidx = {k: i for i, k in enumerate(families)}
+        F = len(families)
+        plugin = np.array([IN_TREE_FAMILIES[in_tree_keys[k]][1] if k in in_tree_keys else abi.PL_NODE_VOLUME_LIMITS
+                           for k in families], np.int32)
+        limit = np.full((F, N), NO_LIMIT, np.int32)
+        for k, f in fidx.items():
+            for i, n in enumerate(nodes):
+                if k in in_tree_keys:
+                    limit[f, i] = in_tree_limit(in_tree_keys[k], n)
+                elif k in n.allocatable:
+                    limit[f, i] = max(0, min(int(quantity_value(n.allocatable[k])), NO_LIMIT - 1))
+        on_node: List[Set[Tuple[str, str]]] = [set() for _ in range(N)]
+        shared: Dict[Tuple[int, str], np.ndarray] = {}
+        for v, k in held.items():
+            if k >= 2:
+                shared[(fidx[v[0]], v[1])] = np.zeros(N, np.int32)
+        for i, vols in bound_vols:
+            for v in vols:
+                on_node[i].add(v)
+                if held[v] >= 2:
+                    shared[(fidx[v[0]], v[1])][i] += 1
+        attached = np.zeros((F, N), np.int32)
+        for i in range(N):
+            for v in on_node[i]:
+                attached[fidx[v[0]], i] += 1
+        uses: Dict[Tuple[str, str], List[Tuple[int, Optional[str], int]]] = {}
+        for p, vols in pend_vols:
+            if not vols:
+                continue
+            u: List[Tuple[int, Optional[str], int]] = []
+            own = [0] * F
+            for v in vols:
+                if held[v] >= 2:
+                    u.append((fidx[v[0]], v[1], 1))
+                else:
+                    own[fidx[v[0]]] += 1
+            u.extend((f, None, c) for f, c in enumerate(own) if c)
+            uses[(p.namespace, p.name)] = u
+        return VolumeLimits(names, families, plugin, limit, attached, uses, shared)
 
     # ---- the PV controller (Immediate claims) ---------------------------------
     def _class_of(self, pvc: PersistentVolumeClaim) -> str:
@@ -283,13 +461,22 @@ class VolumeIndex:
                 pv = self.pvs.get(pvc.volume_name)
                 if pv is None:
                     raise VolumeUnsupported(f"persistentvolume {pvc.volume_name!r} not found")
-                if pv.source in LIMITED_SOURCES or (pv.source == "csi" and self.csi_limits):
-                    raise VolumeUnsupported(f"persistentvolume {pv.name!r}: {pv.source} volumes count against "
-                                            f"node limits")
+                self.counted(pv)                      # Cinder, a CSI PV of an unknown driver: refused
                 bound.append(pv)
                 continue
             if not self.delay_binding(pvc):
                 return MSG_UNBOUND_IMMEDIATE
+            # the PV picked per node would decide the volume's name and family
+            sc = self.classes.get(self._class_of(pvc))
+            if sc is not None and self._counted_provisioner(sc.provisioner):
+                raise VolumeUnsupported(f"persistentvolumeclaim {pvc.name!r}: unbound, its class provisions volumes "
+                                        f"that count against node limits")
+            for pv in self.candidates(pvc):
+                if pv.source in LIMITED_SOURCES or (pv.source == "csi" and self.csi_limits and
+                                                    (self.csi_drivers is None or not pv.csi_driver or
+                                                     pv.csi_driver in self.csi_drivers)):
+                    raise VolumeUnsupported(f"persistentvolumeclaim {pvc.name!r}: unbound, candidate "
+                                            f"{pv.name!r} counts against node limits")
             delay.append(pvc)
         return bound, delay
 

@@ -82,6 +82,9 @@ def filter_message(cluster: EncodedCluster, plugin: str, detail: int, node: str 
     if plugin == "VolumeZone":
         from .volumes import MSG_VOLUME_ZONE
         return MSG_VOLUME_ZONE
+    if plugin in ("EBSLimits", "GCEPDLimits", "NodeVolumeLimits", "AzureDiskLimits"):
+        from .volumes import MSG_VOLUME_LIMIT
+        return MSG_VOLUME_LIMIT
     return f"{plugin} failed"
 
 
