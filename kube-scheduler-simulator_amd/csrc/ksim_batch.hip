@@ -77,13 +77,19 @@ __device__ __forceinline__ void top_finish(uint64_t (&a)[N], int32_t nfeas, int3
   // the T-th largest of the waves' maxima, L, is <= the T-th largest key, so
   // the pod's top-T lies among the kept keys >= cut = max(thr, L).  Those
   // candidates (a prefix of each lane's sorted list) go to LDS by prefix
-  // sums, and one wave ranks them: no serial extraction rounds.  A block
-  // with more than 64 candidates (a long L tie region cannot happen: keys
-  // are unique) takes the round-by-round extraction below.
+  // sums, and one wave ranks them: no serial extraction rounds.  A wave takes
+  // its base in the candidate array by one returning LDS add of its count
+  // (s_ncand, zeroed before the first barrier; the callers that run this more
+  // than once put a barrier between the calls, which orders the re-zeroing
+  // after every read of the count): the candidates land in no particular wave
+  // order, which the ranking by value does not see.  A block with more than
+  // 64 candidates (a long L tie region cannot happen: keys are unique) stores
+  // the first 64 slots only and takes the round-by-round extraction below.
   {
     __shared__ uint64_t s_wmax[kTopWaves], s_wthr[kTopWaves];
-    __shared__ int32_t s_wc[kTopWaves], s_wf[kTopWaves];
+    __shared__ int32_t s_wf[kTopWaves], s_ncand;
     __shared__ uint64_t s_cand[64];
+    if (threadIdx.x == 0) s_ncand = 0;
     uint64_t lmax = a[0];
     if constexpr (!SORTED) {
 #pragma unroll
@@ -127,31 +133,28 @@ __device__ __forceinline__ void top_finish(uint64_t (&a)[N], int32_t nfeas, int3
       pre += (int32_t)mask_below(cb) << bit;
       wsum += __popcll(cb) << bit;
     }
-    if (lane == 0) s_wc[wv] = wsum;
-    lds_barrier();
+    int32_t wbase = 0;
+    if (lane == 0) wbase = atomicAdd(&s_ncand, wsum);
+    const int32_t base_i = __builtin_amdgcn_readfirstlane(wbase) + pre - cl;
 #ifdef KSIM_TC_CLOCKS
     if (tclk && threadIdx.x == 0) tclk[1] = __builtin_amdgcn_s_memrealtime();
 #endif
-    int32_t off = 0, C = 0;
+    if constexpr (SORTED) {
 #pragma unroll
-    for (int w = 0; w < kTopWaves; w++) {
-      const int32_t x = s_wc[w];
-      off += w < wv ? x : 0;
-      C += x;
+      for (int q = 0; q < N; q++)
+        if (q < cl && base_i + q < 64) s_cand[base_i + q] = a[q];
+    } else {
+      int32_t w = base_i;
+#pragma unroll
+      for (int q = 0; q < N; q++)
+        if (a[q] >= cut) {
+          if (w < 64) s_cand[w] = a[q];
+          w++;
+        }
     }
+    lds_barrier();
+    const int32_t C = s_ncand;
     if (C <= 64) {                                 // block-uniform
-      const int32_t base_i = off + pre - cl;
-      if constexpr (SORTED) {
-#pragma unroll
-        for (int q = 0; q < N; q++)
-          if (q < cl) s_cand[base_i + q] = a[q];
-      } else {
-        int32_t w = base_i;
-#pragma unroll
-        for (int q = 0; q < N; q++)
-          if (a[q] >= cut) s_cand[w++] = a[q];
-      }
-      lds_barrier();
 #ifdef KSIM_TC_CLOCKS
       if (tclk && threadIdx.x == 0) tclk[2] = __builtin_amdgcn_s_memrealtime();
       if (tclk && threadIdx.x == 0) tclk[3] = C;

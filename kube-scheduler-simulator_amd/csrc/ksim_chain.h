@@ -12,11 +12,13 @@ constexpr int kHashSlots = 1 << kHashBits;     // >= 2 x the list entries (linea
 constexpr int kChainRounds = 64;               // exact prefix kept if not converged by then
 
 // KSIM_CHAIN_DELAY builds (the race regression test, tests/test_gpu_chain_race.py):
-// stretch the round boundary the per-parity flags protect.  The last wave
-// sleeps before it reads the round's flag, so the fastest wave (thread 0's,
-// which resets the flag slot) is a whole round ahead when it does; the
-// pre-76f29c9 single flag reset at the top of a round would then be read as
-// "every pod exact" by the sleeping wave.  s_sleep is a scalar ALU wait.
+// stretch the two windows the round tags and the per-parity tables protect.
+// A middle wave sleeps right after the round's barrier, before it reads the
+// round's table and the previous round's flag, so the faster waves have
+// registered for the next round by then; the last wave sleeps before it
+// registers for the next round, so it arrives last at every barrier and the
+// others wait a whole sleep between their reads and its writes.  s_sleep is a
+// scalar ALU wait.
 #ifdef KSIM_CHAIN_DELAY
 #define CHAIN_DELAY(wave_sel)                                                      \
   do {                                                                             \
@@ -37,9 +39,9 @@ constexpr int kChainDirect = 8192;
 constexpr int kChainHoldSlots = kHashSlots > kChainDirect ? kHashSlots : kChainDirect;
 struct ChainLds {
   int32_t key[kHashSlots];                     // node id in the slot, -1 = empty (hash mode)
-  int32_t hold[2][kChainHoldSlots];            // per round parity: lowest pod index holding the slot
+  int32_t hold[2][kChainHoldSlots];            // per round parity: (round tag << 9) | (511 - lowest pod holding the slot)
   int16_t rep[kBatchPods][kTopT];              // slot of each list entry
-  int32_t first[2], cut;                      // first: one slot per round parity (see the round loop)
+  int32_t first[2], cut;                      // first: per round parity, (round tag << 9) | (511 - first changed pod)
 };
 
 // The chain of one batch in one block of kBatchPods threads (thread i = pod
@@ -75,7 +77,8 @@ __device__ __forceinline__ bool chain_block(ChainLds& L, const DevState* __restr
                                             int32_t nb_cap = kBatchPods, int32_t direct_n = 0) {
   int32_t* const s_key = L.key;
   int32_t& s_cut = L.cut;
-  // phase clock (100 MHz realtime): dbg[0] setup, dbg[1] rounds, dbg[2] epilogue, dbg[3] launches, dbg[4] rounds run
+  // phase clock (100 MHz realtime): dbg[0] setup, dbg[1] rounds, dbg[2] epilogue, dbg[3] launches,
+  // dbg[4] passes of the round loop (with the lagging check)
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
   const int i = threadIdx.x;                   // one pod per thread
   // the pod's list, count and state in flight together (independent loads;
@@ -127,7 +130,8 @@ __device__ __forceinline__ bool chain_block(ChainLds& L, const DevState* __restr
   if (nb <= 0) return false;
   const int cnt = i < nb ? cnt0 : 0;
   const bool incomplete = i < nb && !complete0;
-  if (i < 2) L.first[i] = kBatchPods;
+  if (i < 2) L.first[i] = 0;                   // tag 0: no round's flag
+  if (i == 0) s_cut = kBatchPods;              // lowered after the rounds (the epilogue)
   // this pod's slots in registers (selects below, never a dynamic index)
   int32_t rep[kTopT];
   if (direct_n > 0 && direct_n <= kChainDirect) {   // block-uniform: the slot is the node id
@@ -156,55 +160,67 @@ __device__ __forceinline__ bool chain_block(ChainLds& L, const DevState* __restr
     for (int e = 0; e < kTopT; e++) rep[e] = L.rep[i][e];
   }
   // only the slots the lists name are ever read: each pod clears its own (a
-  // slot shared by several lists is cleared by each, to the same value)
+  // slot shared by several lists is cleared by each, to the same value), once:
+  // tag 0 is older than every round's
 #pragma unroll
   for (int e = 0; e < kTopT; e++)
-    if (e < cnt) L.hold[0][rep[e]] = L.hold[1][rep[e]] = kBatchPods;
+    if (e < cnt) L.hold[0][rep[e]] = L.hold[1][rep[e]] = 0;
   lds_barrier();
   const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
   int a = cnt > 0 ? 0 : -1;                    // current guess (entry index) or -1
-  int32_t pra = -1;                            // the slot this pod registered last round
   int first = kBatchPods, rounds = 0;
-  for (; rounds < kChainRounds; rounds++) {
-    // Round r registers in hold[r & 1] and reports in first[r & 1], with two
-    // barriers.  The other parity's table and flag were last read in round
-    // r - 1, by every thread before this round's first barrier, so they are
-    // reset after it, for round r + 1 (resetting the current flag at the top
-    // of the round raced with slower waves still reading the previous round's).
+  // Round r has parity r & 1 and tag r + 1.  It registers (tag << 9) | (511 -
+  // pod) in hold[r & 1] by atomicMax, so the lowest pod of the newest round
+  // wins and a word of an older round (or the setup's 0) reads as empty: no
+  // slot and no flag is ever reset, and a round is one barrier B(r):
+  //   hold[par]  written in round r before B(r); read between B(r) and the
+  //              thread's arrival at B(r + 1); next written in round r + 2,
+  //              after B(r + 1).
+  //   first[par] written between B(r) and B(r + 1); read between B(r + 1) and
+  //              B(r + 2); next written in round r + 2, after B(r + 2).
+  // One table for both parities would not do: a fast wave's round r + 1
+  // registration would overwrite what a slow wave still reads in round r.
+  // The convergence test lags a round (round r reads round r - 1's flag in the
+  // same wait as its table reads), so a launch runs one more registration and
+  // barrier than it has rounds; at the cap the last pass is the barrier and
+  // the flag read alone, and first is round kChainRounds - 1's.
+  static_assert(kBatchPods <= 512, "chain words: 9 bits of pod under the round tag");
+  for (;; rounds++) {
     const int par = rounds & 1;
+    const int32_t mine = ((rounds + 1) << 9) | (511 - i);
     int32_t ra = 0;
 #pragma unroll
     for (int e = 0; e < kTopT; e++) ra = e == a ? rep[e] : ra;
-    if (a >= 0) atomicMin(&L.hold[par][ra], i);
+    if (rounds < kChainRounds && a >= 0) atomicMax(&L.hold[par][ra], mine);
     lds_barrier();
-    CHAIN_DELAY(1);                            // a middle wave late after the first barrier
-    if (pra >= 0) L.hold[par ^ 1][pra] = kBatchPods;
-    if (i == 0) L.first[par ^ 1] = kBatchPods;
-    // every entry's holder at once, then the first one not held by an earlier pod
+    CHAIN_DELAY(1);                            // a middle wave late after the barrier
+    // the previous round's flag and every entry's holder in one wait
+    const int32_t flag = L.first[par ^ 1];
     int32_t held[kTopT];
 #pragma unroll
     for (int e = 0; e < kTopT; e++) held[e] = e < cnt ? L.hold[par][rep[e]] : 0;
+    if (rounds >= 1) {
+      const bool changed = flag >= (rounds << 9);   // round r - 1's tag: some pod changed then
+      first = changed ? 511 - (flag & 511) : kBatchPods;
+      if (!changed || rounds == kChainRounds) break;   // a fixpoint (every pod exact), or the cap
+    }
+    // the first entry not held by an earlier pod in this round
     int na = -1;
 #pragma unroll
     for (int e = kTopT - 1; e >= 0; e--)
-      if (e < cnt && held[e] >= i) na = e;
+      if (e < cnt && held[e] <= mine) na = e;
     {                                          // the wave's first changed pod: one LDS atomic per wave
       const uint64_t chg = __ballot(na != a);
-      if (chg && (threadIdx.x & 63) == 0) atomicMin(&L.first[par], (int)(threadIdx.x & ~63u) + __builtin_ctzll(chg));
+      if (chg && (threadIdx.x & 63) == 0)
+        atomicMax(&L.first[par], ((rounds + 1) << 9) | (511 - ((int)(threadIdx.x & ~63u) + __builtin_ctzll(chg))));
     }
-    pra = a >= 0 ? ra : -1;
     a = na;
-    lds_barrier();
-    CHAIN_DELAY((int)(blockDim.x >> 6) - 1);   // the last wave reads the flag late
-    first = L.first[par];
-    if (first == kBatchPods) break;            // a fixpoint: every pod exact
+    CHAIN_DELAY((int)(blockDim.x >> 6) - 1);   // the last wave registers late
   }
   // exact prefix [0, first); an exhausted incomplete list inside it cuts the chain
-  if (i == 0) s_cut = first < nb ? first : nb;
-  lds_barrier();
   block_first_min(&s_cut, i < first && i < nb && a < 0 && incomplete);
   lds_barrier();
-  const int32_t nchain = s_cut;
+  const int32_t nchain = min(s_cut, min(first, nb));
   const uint64_t t2 = __builtin_amdgcn_s_memrealtime();
   uint64_t ga = 0;
 #pragma unroll

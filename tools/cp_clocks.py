@@ -1,6 +1,10 @@
 """Phase clocks of the chain + pairs launch (KSIM_CP_CLOCKS flavor, block 0 of
 every launch): chain setup (list loads, hash), chain rounds, chain epilogue,
 the whole block; config 2, P100, deferred-commit batches.
+rounds/launch counts the barriers of the round loop: the convergence test
+lags a round (round r reads round r - 1's flag), so a launch counts its
+lagging check round, one more than the rounds that changed a guess or proved
+the fixpoint did before the round tags.
 Run: KSIM_LIB_VARIANT=cpclk python3 tools/cp_clocks.py"""
 import os
 import sys
