@@ -801,7 +801,11 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * KSIM_FEED_FLUSH=1 in the environment asks for that form of every stretch),
  * [31] top-ups: the times batches were enqueued behind a run's first stretch,
  * [32] runs whose last flush had an odd ring index, so that the end launch
- * copied the second snapshot buffer back to the handle's own.
+ * copied the second snapshot buffer back to the handle's own;
+ * out[33..34] the deferred-commit batches' second stretch (a batch goes on
+ * committing pods behind its first pair cut while their guesses still hold;
+ * KSIM_ONE_CUT=1 in the environment, read at every run, keeps every batch to
+ * its first cut): [33] batches that committed pods there, [34] those pods.
  * Returns the number of values written (<= n). */
 int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n);
 /* The deferred-commit runs' enqueue rule (host arithmetic, no device): with

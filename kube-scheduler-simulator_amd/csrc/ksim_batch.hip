@@ -30,6 +30,20 @@
 // first i* with M_i* > guess key, and i* itself (it takes the node of M_i*).
 // An exhausted incomplete list also ends the batch; the next batch starts at
 // the first pod not committed.
+//
+// The second stretch (the deferred-commit form only; KSIM_ONE_CUT=1 keeps it to
+// the rule above): after i* took n* = node(M_i*) = g_k*, the state differs from
+// what the chain assumed in two nodes only: n* holds pods k* and i*, and f =
+// g_i* holds nobody and is still at S0.  While every pod between i* and j kept
+// its guess, pod j's exact choice is the maximum of G_j (the best untouched
+// node other than f), the pair keys of k < j, k not in {i*, k*} (all among M_j's
+// terms), D_j = key_j(S0[n*] + pod k* + pod i*) and F_j = key_j(S0[f]).  M_j is a
+// maximum over a superset (it also holds the two stale pairs), so max(M_j,
+// D_j, F_j) <= G_j proves the guess.  i2 is the first j > i* where that fails:
+// pods i* + 1 .. i2 - 1 commit on their guesses and the batch ends before i2,
+// which the next batch evaluates (a stale M_j may end the stretch early;
+// ending early is always exact).  A batch still binds a node at most once, and
+// n* once more.
 #include "ksim_device.h"
 #include <atomic>
 
@@ -921,7 +935,7 @@ __device__ __forceinline__ PodRec pod_rec(const DevPods& P, const uint16_t* __re
 // verdicts and scores from its request class's row of T[p ^ 1], one 2-byte
 // load per node, and only the tie-break hash is computed per pair.  The nodes
 // batch i-1 bound are stale there (their binds are in the overlay alone):
-// thread t < i* takes entry t's node for the block's class from the patch
+// thread t < committed, t != i*, takes entry t's node for the block's class from the patch
 // entries batch i-1's pairs launch wrote (that launch held the row with pod t
 // bound for its pair keys; one coalesced 2-byte load) into s_patch[t], and the
 // main pass selects by s_ent.  Only the node that takes pod i* too is keyed
@@ -954,6 +968,8 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   __shared__ int16_t s_hval[DIRECT ? 1 : kLazyHash];   // ... its entry
   __shared__ uint32_t s_bits[DIRECT ? 1 : kLazyBitWords];   // nodes batch i-1 bound
   __shared__ int32_t s_istar, s_inode, s_sched, s_unsched;
+  __shared__ int32_t s_fnode, s_i2;              // the second stretch: f (local, -1: none) and i2
+  __shared__ ResCols s_dd;                       // ... pods k* and i* together: n*'s delta
   const int tid = threadIdx.x;
   const int32_t b = blockIdx.x;
   const int32_t pod0 = NS ? (b / kNsSlices) * kNsPods : b;   // the block's first pod (batch i offset)
@@ -1038,9 +1054,90 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   tp[1] = __builtin_amdgcn_s_memrealtime();
 #endif
   const int32_t istar = s_istar;
-  const int32_t committed = istar < nchain ? istar + 1 : nchain;
+  int32_t committed = istar < nchain ? istar + 1 : nchain;
   if (tid == istar && istar < nchain) s_inode = key_node(m1) - c.base;
   if (tid < committed) s_rq[tid] = rq;
+  // The second stretch (the header comment's commit rule): pods i* + 1 .. i2 - 1
+  // keep their guesses.  Thread j of (i*, nchain) keys its own pod on n* with
+  // pods k* and i* bound (D_j) and on f at S (F_j), the pairs launch's
+  // arithmetic on the launch's input snapshot X[p ^ 1] = S; i2 is the first j
+  // with max(M_j, D_j, F_j) > G_j.  A launch behind a batch with no cut, or with
+  // no pod behind it, takes only the branch.
+  const bool stretch = !L.one_cut && istar + 1 < nchain;   // block-uniform
+  if (stretch) {
+    if (tid == istar) {
+      s_fnode = g1 ? key_node(g1) - c.base : -1;   // pod i* had no guess: no f
+      s_i2 = nchain;
+    }
+    lds_barrier();
+    const int32_t nn = s_inode, fn = s_fnode;
+    const bool mine = tid > istar && tid < nchain;
+    NodeRow rn{}, rf{};
+    double icn = 0, imn = 0, icf = 0, imf = 0;
+    if (!FLUSH && mine) {                          // both rows in one round trip
+      const int32_t ff = fn >= 0 ? fn : nn;
+      rn = load_res_row_off(c, nn);
+      icn = ld_off(c.inv_cpu, (uint32_t)nn << 3);
+      imn = ld_off(c.inv_mem, (uint32_t)nn << 3);
+      rf = load_res_row_off(c, ff);
+      icf = ld_off(c.inv_cpu, (uint32_t)ff << 3);
+      imf = ld_off(c.inv_mem, (uint32_t)ff << 3);
+    }
+    if (tid < istar && g1 && key_node(g1) - c.base == nn) {   // thread k*: n* takes pods k* and i*
+      const ResCols x = s_rq[istar];
+      s_dd = ResCols{rq.cpu + x.cpu, rq.mem + x.mem, rq.eph + x.eph, rq.nzc + x.nzc, rq.nzm + x.nzm, rq.pods + x.pods};
+    }
+    lds_barrier();
+    bool ends = false;
+    if (mine) {
+      const ResCols d = s_dd;
+      rn.req_cpu += d.cpu;
+      rn.req_mem += d.mem;
+      rn.req_eph += d.eph;
+      rn.nz_cpu += d.nzc;
+      rn.nz_mem += d.nzm;
+      rn.num_pods += d.pods;
+      ksim_pod pq;
+      pq.req_cpu = rq.cpu;
+      pq.req_mem = rq.mem;
+      pq.req_eph = rq.eph;
+      pq.nz_cpu = rq.nzc;
+      pq.nz_mem = rq.nzm;
+#pragma unroll
+      for (int k = 0; k < KSIM_MAX_SCALAR; k++) pq.scalar_req[k] = 0;   // FAST pods: no scalar requests
+      const FastProg bq = fast_prog(*bp_p);
+      const uint64_t hs = prof_p->tiebreak_seed ^ ((uint64_t)(seq0 + tid) << 20);
+      if constexpr (FLUSH) {
+        // a flush has nothing to hide the second round trip behind and no node
+        // loop whose registers would cover two rows: one row after the other
+        uint64_t k2 = m1;
+#pragma unroll 1
+        for (int w = 0; w < 2; w++) {
+          const int32_t node = w ? fn : nn;
+          if (node < 0) continue;
+          NodeRow r = load_res_row_off(c, node);
+          const double ic = ld_off(c.inv_cpu, (uint32_t)node << 3), im = ld_off(c.inv_mem, (uint32_t)node << 3);
+          if (w == 0) {
+            r.req_cpu += d.cpu;
+            r.req_mem += d.mem;
+            r.req_eph += d.eph;
+            r.nz_cpu += d.nzc;
+            r.nz_mem += d.nzm;
+            r.num_pods += d.pods;
+          }
+          k2 = umax64(k2, dyn_key_fast_t<DEF>(bq, pq, r, ic, im, hs, c.base + node));
+        }
+        ends = k2 > g1;
+      } else {
+        const uint64_t dk = dyn_key_fast_t<DEF>(bq, pq, rn, icn, imn, hs, c.base + nn);
+        const uint64_t fk = fn >= 0 ? dyn_key_fast_t<DEF>(bq, pq, rf, icf, imf, hs, c.base + fn) : 0;
+        ends = umax64(umax64(m1, dk), fk) > g1;
+      }
+    }
+    block_first_min(&s_i2, ends);
+    lds_barrier();
+    committed = s_i2;                              // in (i*, nchain]: pod i2 is left to the next batch
+  }
   // this block's pod of batch i
   const int32_t base = cur0 + committed;
   const int32_t pi = base + pod0;
@@ -1054,11 +1151,12 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   tp[2] = __builtin_amdgcn_s_memrealtime();
 #endif
   const int32_t inode = s_inode;
-  // entry tid < i*: its guessed node takes pod tid, and pod i* when i* chose it
-  const int32_t gnode = (tid < istar && g1) ? key_node(g1) - c.base : -1;
+  // entry tid < committed, tid != i* (pod tid took its guess): its guessed node
+  // takes pod tid, and pod i* when i* chose it (f, pod i*'s own guess, takes nobody)
+  const int32_t gnode = (tid < committed && tid != istar && g1) ? key_node(g1) - c.base : -1;
   // RT: the entry of this thread's node for the block's class with pod tid
-  // bound there, as batch i-1's pairs launch keyed it (ReqTab::p_in; tid < i*
-  // <= e1: the slot holds that batch's), and the lane's entries of its class's
+  // bound there, as batch i-1's pairs launch keyed it (ReqTab::p_in; tid <
+  // committed <= e1: the slot holds that batch's), and the lane's entries of its class's
   // row, all in one round trip and all loaded before the first use.  The node
   // that takes pod i* as well is keyed here: its one lane loads the row.  The
   // patch loads come first, so waiting for them leaves te[] in flight.
@@ -1085,7 +1183,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   if (gnode >= 0) {
     ResCols d = rq;
     if (gnode == inode) {
-      const ResCols x = s_rq[istar];              // never overwritten: only entries < i* are
+      const ResCols x = s_rq[istar];              // never overwritten: entry i* has no guessed node here
       d.cpu += x.cpu;
       d.mem += x.mem;
       d.eph += x.eph;
@@ -1169,8 +1267,15 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
       ns.scheduled += s_sched;
       ns.unschedulable += s_unsched;
       ns.batches += 1;
-      ns.cuts += (committed < nb && istar < nchain ? 1 : 0);
-      ns.truncations += (committed < nb && istar >= nchain ? 1 : 0);
+      // a batch that ended short: at a pair event (the first cut without a
+      // stretch, or i2 inside the chain), else at the chain's exhausted list
+      const bool pair_end = istar < nchain && (!stretch || committed < nchain);
+      ns.cuts += (committed < nb && pair_end ? 1 : 0);
+      ns.truncations += (committed < nb && !pair_end ? 1 : 0);
+      if (stretch && committed > istar + 1) {
+        ns.stretches += 1;
+        ns.stretch_pods += committed - (istar + 1);
+      }
       ns.evals += (int64_t)committed * (c.eval_hi - c.eval_lo);
     }
     __builtin_memcpy(w, &ns, sizeof(ns));
@@ -1435,7 +1540,7 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   if (tid == 0) {
     // dbg: 0 prologue, 1 thread 0's node loop, 2 wait for the block's slowest
     // wave, 3 the finish after its first barrier, 4 prologue to the first
-    // barrier (loads, LDS init), 5 blocks, 6 the cut, 7 the overlay
+    // barrier (loads, LDS init), 5 blocks, 6 the cut, 7 the second cut and the overlay
     const uint64_t t_out = __builtin_amdgcn_s_memrealtime();
     atomicAdd(&g_cp_dbg[0], (unsigned long long)(t_pro - t_in));
     atomicAdd(&g_cp_dbg[1], (unsigned long long)(t_loop - t_pro));
@@ -1458,8 +1563,11 @@ __device__ __forceinline__ void batch_top_commit_body(const DevCluster& c, const
   }
 }
 
+// (the hash-overlay flush keeps the two blocks per CU it had before the second
+// stretch: eight waves per SIMD; every other form is bound by its LDS or its
+// node loop's registers at the four a block needs)
 template <bool FLUSH, bool DIRECT, bool DEF = false, bool KEEP = false, bool NS = false, bool RT = false>
-__global__ __launch_bounds__(1024) void k_batch_top_commit(DevCluster c, DevPods P,
+__global__ __launch_bounds__(1024, (FLUSH && !DIRECT) ? 8 : 4) void k_batch_top_commit(DevCluster c, DevPods P,
                                                            const ksim_profile* __restrict__ prof_p,
                                                            const BatchProg* __restrict__ bp_p, LazyStep L,
                                                            uint64_t* __restrict__ topk, int32_t* __restrict__ topk_cnt,

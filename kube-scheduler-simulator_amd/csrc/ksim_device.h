@@ -167,6 +167,9 @@ struct DevState {
   // generic ADAPT batches: the next batch's pod cap (0: the full batch), set
   // by k_adapt_commit from the last batch's committed pods, reset by set_run
   int32_t bcap;
+  // deferred-commit batches (ksim_batch.hip, the second stretch): batches that
+  // committed pods past their first pair cut, and the pods committed there
+  int32_t stretches, stretch_pods;
 };
 
 // DevState.topo_flags

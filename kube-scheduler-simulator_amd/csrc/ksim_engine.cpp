@@ -355,6 +355,9 @@ struct ksim_handle {
   SweepLane* sweep_tab = nullptr;
   DevArena sweep_profs, sweep_rows;
   std::map<std::pair<int32_t, bool>, hipGraphExec_t> sweep_graphs;
+  // deferred-commit batches end at their first pair cut (KSIM_ONE_CUT=1 at the
+  // last run's start): the setting the handle's deferred-commit graphs hold
+  bool one_cut = false;
   int64_t graph_captures = 0;                  // graphs captured since ksim_create (ksim_get_diag)
   // node-sharded per-pod cycles (group leader): graphs of kGraphCycles cycles
   // per shape (topology, exchange lengths), valid while every handle of the
@@ -964,7 +967,27 @@ bool lazy_ok(const ksim_handle* h, int32_t a, int32_t b, bool fast, bool stab = 
   return true;
 }
 
+// KSIM_ONE_CUT=1 (read at every run, as KSIM_FEED_FLUSH): every deferred-commit
+// batch ends at its first pair cut, the rule before the second stretch
+// (ksim_batch.hip; an A/B form of the same runs).  The setting is a launch
+// argument (LazyStep::one_cut), so the graphs captured under the other one go.
+int sync_one_cut(ksim_handle* h) {
+  const char* v = std::getenv("KSIM_ONE_CUT");
+  const bool want = v && v[0] == '1';
+  if (want == h->one_cut) return KSIM_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_lazy_graphs(h);
+  for (auto& kv : h->sweep_graphs)
+    if (kv.second) (void)hipGraphExecDestroy(kv.second);
+  h->sweep_graphs.clear();
+  for (auto& kv : h->sg_graphs) (void)hipGraphExecDestroy(kv.second);   // a replica group's (its leader's)
+  h->sg_graphs.clear();
+  h->one_cut = want;
+  return KSIM_OK;
+}
+
 int alloc_lazy(ksim_handle* h) {
+  if (int rc = sync_one_cut(h)) return rc;
   if (h->lazy_n == h->dc.n) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_lazy_graphs(h);
@@ -1088,6 +1111,7 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool
   z.step.e2 = h->lazy_e + q2;
   z.step.e_self = h->lazy_e + q;
   z.step.prog = h->prog_d;
+  z.step.one_cut = h->one_cut ? 1 : 0;
   z.st = st[p];
   z.gkey = h->lazy_g + (size_t)q * kBatchPods;
   z.pmax = h->lazy_m + (size_t)q * kBatchPods;
@@ -1393,6 +1417,7 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la, bool ze
 // The lanes' buffers: one slab, carved at 256-byte steps (k_reset_copy moves
 // 16-byte words), zero-filled; sized by (dc.n, lanes) and kept with the handle.
 int alloc_sweep(ksim_handle* h, int32_t lanes) {
+  if (int rc = sync_one_cut(h)) return rc;
   if (!h->sweep_tab) {                              // its address is what the sweep graphs hold: allocated once
     void* t = nullptr;
     hipError_t e = hipMalloc(&t, sizeof(SweepLane) * kLazySlots * kSweepMaxLanes);
@@ -1494,6 +1519,7 @@ SweepLane sweep_record(const ksim_handle* h, int32_t l, int q, int32_t* row, con
   r.step.g2 = b.g + (size_t)q2 * kBatchPods;
   r.step.e2 = b.e + q2;
   r.step.e_self = b.e + q;
+  r.step.one_cut = h->one_cut ? 1 : 0;
   r.gkey = b.g + (size_t)q * kBatchPods;
   r.pmax = b.m + (size_t)q * kBatchPods;
   r.topk = b.topk;
@@ -2322,6 +2348,8 @@ int reset_counters(ksim_handle* h, hipStream_t stream) {
   HIPCHK(h, hipMemsetAsync(&h->st->evals, 0, 3 * sizeof(int64_t), stream));
   HIPCHK(h, hipMemsetAsync(&h->st->batches, 0, 4, stream));
   HIPCHK(h, hipMemsetAsync(&h->st->cuts, 0, 8, stream));
+  static_assert(offsetof(DevState, stretch_pods) == offsetof(DevState, stretches) + 4, "the stretch counters are adjacent");
+  HIPCHK(h, hipMemsetAsync(&h->st->stretches, 0, 8, stream));
   return KSIM_OK;
 }
 
@@ -5149,7 +5177,7 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   DevState st;
   int rc = read_state(h, st);
   if (rc) return rc;
-  int64_t v[3 + 16 + 2 + 4 + 3 + 5] = {st.batches, st.truncations, st.cuts};
+  int64_t v[3 + 16 + 2 + 4 + 3 + 5 + 2] = {st.batches, st.truncations, st.cuts};
   if (h->has_cluster) HIPCHK(h, hcopy(h, v + 3, h->sc.dbg, 8 * 16, hipMemcpyDeviceToHost));
   if (unsigned long long* cp = cp_clock_buffer())   // KSIM_CP_CLOCKS builds: the chain + pairs phase clocks
     HIPCHK(h, hcopy(h, v + 3, cp, 8 * 8, hipMemcpyDeviceToHost));
@@ -5166,7 +5194,9 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   v[30] = h->feed_fallbacks;
   v[31] = h->feed_topups;
   v[32] = h->feed_odd_ends;
-  const int32_t m = n < 33 ? n : 33;
+  v[33] = st.stretches;
+  v[34] = st.stretch_pods;
+  const int32_t m = n < 35 ? n : 35;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
 }

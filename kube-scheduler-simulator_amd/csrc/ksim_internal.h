@@ -189,6 +189,9 @@ struct LazyStep {
   // run_lazy's progress word (host-mapped, null: none): the state writer
   // stores lazy_progress(cursor, batches) of the state it wrote
   unsigned long long* prog = nullptr;
+  // 1: batch i-1 ends at its first pair cut (KSIM_ONE_CUT=1, read per run);
+  // 0: it goes on through the second stretch (ksim_batch.hip)
+  int32_t one_cut = 0, _pad = 0;
 };
 // The progress word: the cursor after the launch's commit above the handle's
 // batch counter (DevState::batches, which counts committed batches).

@@ -1183,6 +1183,8 @@ __global__ __launch_bounds__(256) void k_lazy_move(LazyMove m) {
         s.unschedulable = 0;
         s.batches = 0;
         s.cuts = 0;
+        s.stretches = 0;
+        s.stretch_pods = 0;
       }
       *m.st_dst2 = s;
       if (m.batches0) *m.batches0 = (unsigned long long)(uint32_t)s.batches;

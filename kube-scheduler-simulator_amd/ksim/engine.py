@@ -582,8 +582,8 @@ class Engine:
 
     def diag(self) -> dict:
         """Batch-path diagnostics of the last schedule_loaded call."""
-        out = np.zeros(33, np.int64)
-        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 33)
+        out = np.zeros(35, np.int64)
+        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 35)
         if n < 0:
             self._chk(n)
         d = {"batches": int(out[0]), "truncations": int(out[1]), "cuts": int(out[2]),
@@ -595,7 +595,9 @@ class Engine:
              # enqueued past a run's end, stretches ended by flush + state read, top-ups,
              # runs that ended on the second snapshot buffer
              "feed_syncs": int(out[28]), "feed_past_end": int(out[29]), "feed_fallbacks": int(out[30]),
-             "feed_topups": int(out[31]), "feed_odd_ends": int(out[32])}
+             "feed_topups": int(out[31]), "feed_odd_ends": int(out[32]),
+             # deferred-commit batches that committed pods past their first pair cut, and those pods
+             "stretches": int(out[33]), "stretch_pods": int(out[34])}
         if out[6]:
             d["chain_us"] = {"setup": out[3] / out[6] / 100.0, "rounds": out[4] / out[6] / 100.0,
                              "epilogue": out[5] / out[6] / 100.0, "rounds_per_batch": out[7] / out[6]}
