@@ -543,7 +543,8 @@ int ksim_get_class_count(ksim_handle* h, int32_t* out);
  * drops it as well); the loaded queue is dropped.  ksim_reset_cluster restores
  * `attached`.  Pods with such uses take the per-pod cycle.  KSIM_E_INVALID: a
  * volume use without a table or with a family >= n_families.
- * KSIM_E_UNSUPPORTED: the preemption dry runs for such a preemptor; shard and
+ * KSIM_E_UNSUPPORTED: the preemption dry runs for such a preemptor other than
+ * ksim_preempt_volumes; shard and
  * replicated handles; ksim_upsert_nodes / ksim_remove_node /
  * ksim_update_node_rows while a table is set. */
 int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* family_plugin, const int32_t* limit,
@@ -874,6 +875,22 @@ int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class
  * id outside [0, n_pdbs), an id twice in one row. */
 int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
                             const int32_t* ids);
+/* The counted volumes the bound pods of the last ksim_set_bound_pods hold
+ * (which drops any earlier ones, as does ksim_set_volume_limits), as a CSR over
+ * its rows in the caller's row order: uses[off[i] .. off[i + 1]) are row i's
+ * KSIM_USE_VOLUME uses as a queue pod carries them (col = family, cls >= 0 and
+ * arg = 1 for a volume two or more pods hold, cls = -1 for `arg` volumes only
+ * this pod holds; a row names a class at most once), off has n + 1 entries.
+ * Copied.  The holdings must agree with the device's attached counts and class
+ * counts (attached[f][node] = the node's rows' classless args of family f plus
+ * its family-f classes with a holder; class_count[cls][node] = the node's rows
+ * naming cls), as the rows' requests must agree with the node columns: the dry
+ * run starts from the device's counts and moves them by these entries.
+ * KSIM_E_INVALID: no table set, no volume table (ksim_set_volume_limits),
+ * offsets not monotone, a use of another kind, a family >= n_families, a class
+ * outside [0, n_classes) other than -1, a count a queue pod's use could not
+ * carry.  Needed only before ksim_preempt_volumes for a pod with such uses. */
+int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses);
 /* DefaultPreemption's PostFilter for an unschedulable pod of `priority`
  * (default_preemption.go / preemption.go, v1.26) on the current snapshot,
  * without changing it.  It replaces the original plugin's PostFilter that the
@@ -933,7 +950,11 @@ int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allow
  *   PTS_HARD    KSIM_E_UNSUPPORTED from this call and ksim_preempt_nominated (the
  *               message names PTS_HARD), also beside InterPodAffinity uses:
  *               their callers fall back on that code.  ksim_preempt_spread
- *               runs the dry run for such pods.
+ *               runs the dry run for such pods;
+ *   VOLUME      KSIM_E_UNSUPPORTED from this call, ksim_preempt_nominated and
+ *               ksim_preempt_spread (the message names KSIM_USE_VOLUME): their
+ *               callers fall back on that code.  ksim_preempt_volumes runs the
+ *               dry run for such pods.
  * Also KSIM_E_UNSUPPORTED: shard handles, NetworkBandwidth in the filter list,
  * KSIM_POD_NODE_NAMES pods. */
 int ksim_preempt(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
@@ -993,6 +1014,46 @@ int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* pods, int32_t pod
 int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                         const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
                         const int32_t* first, const int32_t* count, ksim_preempt_out* out);
+
+/* ksim_preempt_nominated that also accepts KSIM_USE_VOLUME uses (n_groups = 0
+ * is allowed); for a pod without one it returns what ksim_preempt_nominated
+ * returns, also on a handle without a volume table.  The dry run then re-runs
+ * the node volume limit plugins of the profile's filter list beside
+ * NodeResourcesFit and NodePorts (the nodevolumelimits filters keep no
+ * PreFilter state: upstream recomputes them from the NodeInfo's pods):
+ *   potential nodes  the four limit plugins return Unschedulable, so a node
+ *               whose first failing filter is one of them is a potential node;
+ *   what moves  in node n's dry run, per family f the preemptor has a use of,
+ *               attached[f][n]: a classless holding of a pod taken out lowers
+ *               it by arg; a class holding lowers the class count on n by 1
+ *               and attached by 1 only when that count reaches 0, i.e. every
+ *               holder on n is out, whatever its priority (pods of priority >=
+ *               `priority` and a nominated group's pods stay and hold); putting
+ *               the pod back reverses exactly that.  The holdings come from
+ *               ksim_set_bound_pod_volumes (KSIM_E_INVALID without them; the
+ *               message names that call) and, on a grouped node, from the
+ *               nominated pods' own KSIM_USE_VOLUME uses, added before the
+ *               first trial.  Only n's own pods move;
+ *   the Filter  ksim_set_volume_limits' rule on the moved counts, in 64 bits:
+ *               new = the pod's classless args plus its class uses no pod left
+ *               on n holds (evicting the last holder of a volume the pod also
+ *               mounts lowers attached by 1 and raises new by 1); an in-tree
+ *               family fails when attached + new > limit, a CSI family when
+ *               new > 0 as well; INT32_MAX: no limit;
+ *   the pod passes  when NodeResourcesFit, NodePorts and every limit plugin of
+ *               the filter list pass.  A family whose plugin the list lacks is
+ *               not read, as port uses are not without NodePorts.
+ * A dry run: attached and the class counts on the device are the same before
+ * and after.  KSIM_E_UNSUPPORTED: a pod with a KSIM_USE_VOLUME use and a
+ * KSIM_USE_IPA_AFFINITY / IPA_ANTI / IPA_EXISTING_ANTI or KSIM_USE_PTS_HARD use
+ * (the message names both kinds), whatever the filter list; the other refusals
+ * (shard handles, NetworkBandwidth, KSIM_POD_NODE_NAMES) stay.  Pass 2 of
+ * RunFilterPluginsWithNominatedPods is not re-run inside the dry run, and
+ * VolumeBinding / VolumeZone are not re-run either (their verdicts do not
+ * depend on the pods of the node). */
+int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
+                         const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
+                         const int32_t* first, const int32_t* count, ksim_preempt_out* out);
 
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's

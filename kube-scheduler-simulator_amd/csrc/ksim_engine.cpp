@@ -231,6 +231,9 @@ struct ksim_handle {
   int64_t* pre_smin = nullptr;          // ksim_preempt_spread's per-use minima (in pre_bufs; k_preempt_spread_mins)
   std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
   std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
+  std::vector<DevBuf> pre_vol_bufs;     // ksim_set_bound_pod_volumes (likewise, and by ksim_set_volume_limits)
+  const int32_t* pre_voff = nullptr;    // [pre_n + 1] CSR order: the rows' volume holdings (null: none set)
+  const VolHold* pre_vols = nullptr;
   DevPreempt pre{};
   std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
   int32_t pre_n = 0;
@@ -2451,6 +2454,7 @@ void ksim_destroy(ksim_handle* h) {
   free_bufs(h->pre_nom_bufs);
   free_bufs(h->pre_add_bufs);
   free_bufs(h->pre_pdb_bufs);
+  free_bufs(h->pre_vol_bufs);
   if (h->d_chosen) (void)hipFree(h->d_chosen);
   if (h->st) (void)hipFree(h->st);
   if (h->d_prof) (void)hipFree(h->d_prof);
@@ -2648,6 +2652,9 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   free_bufs(h->pre_nom_bufs);
   free_bufs(h->pre_add_bufs);
   free_bufs(h->pre_pdb_bufs);
+  free_bufs(h->pre_vol_bufs);
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
   h->pre = DevPreempt{};
   h->pre_index.clear();
   h->pre_n = 0;
@@ -3232,6 +3239,9 @@ int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* fa
   h->dp = DevPods{};
   h->batchable.clear();
   free_bufs(h->vol_bufs);
+  free_bufs(h->pre_vol_bufs);           // the bound pods' holdings named the old table's families
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
   h->vol_init = nullptr;
   h->dc.vol_nf = 0;
   h->dc.vol_plug = 0;
@@ -5247,6 +5257,9 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   free_bufs(h->pre_bufs);
   free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
   free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
+  free_bufs(h->pre_vol_bufs);                  // and the volume holdings
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
   DevPreempt d{};
   void* p = nullptr;
   if ((rc = upload(h, h->pre_bufs, off.data(), 4 * off.size(), &p))) return rc;
@@ -5357,23 +5370,68 @@ extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int
   return KSIM_OK;
 }
 
+extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: ksim_set_bound_pods first");
+  if (!h->dc.vol_nf)
+    return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: no volume table (ksim_set_volume_limits)");
+  const int32_t n = h->pre_n;
+  if (!off || off[0] < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad offsets");
+  for (int32_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: offsets not monotone");
+  if (off[n] > off[0] && !uses) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: uses missing");
+  for (int32_t e = off[0]; e < off[n]; e++) {
+    const ksim_topo_use& u = uses[e];
+    if (u.kind != KSIM_USE_VOLUME)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: a use that is no KSIM_USE_VOLUME");
+    if (u.col >= h->dc.vol_nf) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: family out of range");
+    if (u.cls < -1 || u.cls >= h->dc.n_classes)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: class out of range");
+    if (u.cls < 0 ? u.arg < 1 : u.arg != 1)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad volume use count");
+  }
+  // into the table's per-node importance order (CSR position k = caller row pre_index[k])
+  std::vector<int32_t> voff((size_t)n + 1, 0);
+  std::vector<VolHold> perm;
+  perm.reserve((size_t)(off[n] - off[0]));
+  for (int32_t k = 0; k < n; k++) {
+    const int32_t i = h->pre_index[k];
+    for (int32_t e = off[i]; e < off[i + 1]; e++) perm.push_back({uses[e].cls, (int32_t)uses[e].col, uses[e].arg});
+    voff[(size_t)k + 1] = (int32_t)perm.size();
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  free_bufs(h->pre_vol_bufs);                   // every dry run ends synchronized: nothing reads them
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
+  int rc;
+  void *po = nullptr, *pv = nullptr;
+  if ((rc = upload(h, h->pre_vol_bufs, voff.data(), 4 * voff.size(), &po))) return rc;
+  if ((rc = upload(h, h->pre_vol_bufs, perm.data(), sizeof(VolHold) * perm.size(), &pv))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
+  h->pre_voff = (const int32_t*)po;
+  h->pre_vols = (const VolHold*)pv;
+  return KSIM_OK;
+}
+
 extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                             ksim_preempt_out* out) {
   return ksim_preempt_nominated(h, ps, pod_index, priority, nullptr, 0, nullptr, nullptr, nullptr, out);
 }
 
 // The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
-// DoNotSchedule spread uses are refused) and ksim_preempt_spread.
+// DoNotSchedule spread uses are refused), ksim_preempt_spread and
+// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted).
 static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                        const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
-                       const int32_t* count, ksim_preempt_out* out, bool spread) {
+                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false) {
   int rc = ensure_ready(h);
   if (rc) return rc;
   if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
     return set_err(h, KSIM_E_INVALID, "bad pod set / index");
   if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
     return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
-  if (has_volume_use(ps, pod_index))
+  const bool vol_form = has_volume_use(ps, pod_index);   // the volume form of k_preempt_nodes
+  if (vol_form && !volumes)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
                                           "re-run the node volume limit plugins)");
   {
@@ -5410,6 +5468,14 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   const ksim_pod& pp = ps->pods[pod_index];
   const bool topo = pp.use_count > 0;
   uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
+  for (int32_t k = 0; k < pp.use_count && vol_form; k++) {
+    const uint8_t kind = ps->uses[pp.use_first + k].kind;
+    static const char* const kNames[] = {"KSIM_USE_PTS_HARD", nullptr, "KSIM_USE_IPA_EXISTING_ANTI",
+                                         "KSIM_USE_IPA_AFFINITY", "KSIM_USE_IPA_ANTI"};
+    if (kind <= KSIM_USE_IPA_ANTI && kNames[kind])
+      return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_VOLUME use and a ") +
+                                                kNames[kind] + " use (the volume form moves no domain counts)");
+  }
   for (int32_t k = 0; k < pp.use_count && !spread; k++)
     if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
       return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
@@ -5430,6 +5496,27 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   if (port_mask && !dom_form && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
                                       "(after ksim_set_bound_pods)");
+  if (vol_form && !h->pre_voff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with a KSIM_USE_VOLUME use: ksim_set_bound_pod_volumes "
+                                      "first (after ksim_set_bound_pods)");
+  // what the profile's limit plugins read of the pod (validate_pod checked the families)
+  PreemptVol vm{};
+  vm.at = 0xffffffffu;
+  if (vol_form) {
+    for (int f = 0; f < h->prof.n_filter; f++) {
+      const int32_t k = h->prof.filter[f] - KSIM_PL_EBS_LIMITS;
+      if (k >= 0 && k < 4) vm.at = (vm.at & ~(255u << (8 * k))) | ((uint32_t)f << (8 * k));
+    }
+    for (int32_t k = 0; k < pp.use_count; k++) {
+      const ksim_topo_use& u = ps->uses[pp.use_first + k];
+      if (u.kind != KSIM_USE_VOLUME) continue;
+      const uint32_t pl = (h->dc.vol_plug >> (4 * u.col)) & 15u;
+      if (((vm.at >> (8 * pl)) & 255u) == 255u) continue;   // its plugin is not in the filter list
+      vm.uses |= 1u << k;
+      vm.fams |= 1u << u.col;
+      if (pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS)) vm.csi |= 1u << u.col;
+    }
+  }
   if (dom_form && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
                                       "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
@@ -5458,6 +5545,8 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
   std::vector<int32_t> goff((size_t)n_groups + 1, 0);    // the groups' class contributions (CSR)
   std::vector<ksim_class_add> gadds;
+  std::vector<int32_t> gvoff((size_t)n_groups + 1, 0);   // and their volume holdings, for the volume form
+  std::vector<VolHold> gvols;
   auto bind_group = [&](int32_t k, int sign) -> int {
     for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
       DevPods Q;
@@ -5481,9 +5570,14 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       q[2] += x.req_eph;
       for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
       if ((port_mask || dom_form) && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
+      for (int32_t e = 0; e < x.use_count && vol_form; e++) {
+        const ksim_topo_use& u = nps->uses[x.use_first + e];
+        if (u.kind == KSIM_USE_VOLUME) gvols.push_back({u.cls, (int32_t)u.col, u.arg});
+      }
     }
     q[KSIM_PREEMPT_REQ] = count[k];
     goff[(size_t)k + 1] = (int32_t)gadds.size();
+    gvoff[(size_t)k + 1] = (int32_t)gvols.size();
   }
   if (n_groups > 0) {
     free_bufs(h->pre_nom_bufs);
@@ -5495,6 +5589,12 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       pre.goff = (const int32_t*)p;
       if ((rc = upload(h, h->pre_nom_bufs, gadds.data(), sizeof(ksim_class_add) * gadds.size(), &p))) return rc;
       pre.gadds = (const ksim_class_add*)p;
+    }
+    if (vol_form) {
+      if ((rc = upload(h, h->pre_nom_bufs, gvoff.data(), 4 * gvoff.size(), &p))) return rc;
+      vm.gvoff = (const int32_t*)p;
+      if ((rc = upload(h, h->pre_nom_bufs, gvols.data(), sizeof(VolHold) * gvols.size(), &p))) return rc;
+      vm.gvols = (const VolHold*)p;
     }
   }
   if ((rc = filter_pass(dom_form))) return rc;             // every node as is
@@ -5509,8 +5609,14 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
     }
   }
-  launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
-                 hard_mask, h->pre_smin);
+  if (vol_form) {
+    vm.voff = h->pre_voff;
+    vm.vols = h->pre_vols;
+    launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
+  } else {
+    launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
+                   hard_mask, h->pre_smin);
+  }
   HIPCHK(h, hipGetLastError());
   if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
   if (n_groups > 0) {
@@ -5545,6 +5651,12 @@ extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, in
                                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                       const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
   return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false);
+}
+
+extern "C" int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                    const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                    const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false, true);
 }
 
 extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,

@@ -352,6 +352,32 @@ void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_inde
                     uint32_t aff = 0, uint32_t anti = 0, uint32_t exist = 0, int32_t pts_index = -1,
                     uint32_t hard = 0, int64_t* smin = nullptr);
 
+// One counted-volume holding of a bound pod or of a nominated pod: the device
+// form of a KSIM_USE_VOLUME use (ksim_set_bound_pod_volumes).
+struct VolHold {
+  int32_t cls;                         // the shared volume's count class, -1: `arg` volumes nobody else holds
+  int32_t fam;                         // family index < vol_nf
+  int32_t arg;
+};
+// The volume form's argument (ksim_preempt_volumes for a preemptor with
+// KSIM_USE_VOLUME uses; the other forms keep their kernel arguments).  Only
+// what the profile's limit plugins read is named: a family whose plugin the
+// filter list lacks is in none of the masks.
+struct PreemptVol {
+  const int32_t* voff;                 // [n_bound + 1] CSR order: vols[voff[j] .. voff[j + 1]) of bound pod j
+  const VolHold* vols;
+  const int32_t* gvoff;                // [groups + 1] the same per nominated group (null without groups)
+  const VolHold* gvols;
+  uint32_t uses;                       // the preemptor's volume uses (bit i = use i)
+  uint32_t fams;                       // the families they name (bit f)
+  uint32_t csi;                        // those under NodeVolumeLimits' rule (new > 0)
+  uint32_t at;                         // byte k: the profile position of plugin KSIM_PL_EBS_LIMITS + k, 0xff: absent
+};
+// The volume form: launch_preempt with filter = false for a preemptor with
+// volume uses (and possibly NodePorts uses); a.c carries the volume table.
+void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
+                            hipStream_t stream, int32_t port_index, uint32_t port_mask, const PreemptVol& vm);
+
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);
 // topo: the pod carries uses; the PreFilter pass of its cycle runs first (the

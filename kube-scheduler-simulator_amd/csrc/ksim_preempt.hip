@@ -23,7 +23,11 @@
 // with DoNotSchedule spread uses (ksim_preempt_spread) takes the spread form:
 // the domain form plus PodTopologySpread's Filter on the moved row, against
 // min(the node's own domain, the minimum over the other present domains),
-// which k_preempt_spread_mins takes once per dry run.  One
+// which k_preempt_spread_mins takes once per dry run.  A pod with counted
+// volumes (ksim_preempt_volumes) takes the volume form, k_preempt_nodes_vol:
+// the ports form plus the node volume limit plugins on the node's attached
+// count per family, moved with the rows' holdings (ksim_set_bound_pod_volumes);
+// a node that failed one of those plugins is a potential node too.  One
 // block then keeps candidates in nodeTree order (upstream scans from a random
 // offset; offset 0 here) until numCandidates were found and one of them has
 // no PDB violation, and picks one by pickOneNodeForPreemption's criteria.
@@ -70,6 +74,111 @@ __device__ __forceinline__ bool hold_conflict(const PortHold& h) {
   for (int i = 0; i < KSIM_MAX_USES; i++)
     if (h.held[i] > 0) hit = true;
   return hit;
+}
+
+// The volume form's per-thread state: the node's distinct family-f volumes
+// (c.vol_attached, moved with every pod taken out or put back) and its limit,
+// for the families the preemptor has a use of.  Indexed by unrolled constants
+// only, so both stay in registers.
+struct VolRow {
+  int64_t att[KSIM_MAX_VOL_FAMILIES];
+  int32_t lim[KSIM_MAX_VOL_FAMILIES];
+};
+struct NoVol {};                                         // the other forms' (empty) volume argument
+// nodeports Filter on the holdings of the volume form: only the port uses
+// conflict (a held volume class is no conflict)
+__device__ __forceinline__ bool hold_conflict(const PortHold& h, uint32_t port_mask) {
+  bool hit = false;
+#pragma unroll
+  for (int i = 0; i < KSIM_MAX_USES; i++)
+    if (((port_mask >> i) & 1u) && h.held[i] > 0) hit = true;
+  return hit;
+}
+// Pods of the node's suffix [j0, b) that are out of the trial state (bit 0 of
+// their flag; row `skip` apart) and hold volume class `cls`: a direct count,
+// quadratic in the node's victims like the PDB form's.
+__device__ __forceinline__ int32_t vol_out_holders(const DevPreempt& pre, const PreemptVol& vm, int32_t j0, int32_t b,
+                                                   int32_t skip, int32_t cls) {
+  int32_t n = 0;
+  for (int32_t k = j0; k < b; k++) {
+    if (k == skip || !(pre.vflag[k] & 1)) continue;
+    for (int32_t e = vm.voff[k]; e < vm.voff[k + 1]; e++) n += vm.vols[e].cls == cls;
+  }
+  return n;
+}
+// Entries [e0, e1) of `ents` that hold class `cls`
+__device__ __forceinline__ int32_t vol_class_entries(const VolHold* __restrict__ ents, int32_t e0, int32_t e1,
+                                                     int32_t cls) {
+  int32_t n = 0;
+  for (int32_t e = e0; e < e1; e++) n += ents[e].cls == cls;
+  return n;
+}
+// The holders of volume class x on the node apart from row j, for a class the
+// preemptor does not use: the device's count (every bound holder of the node,
+// whatever its priority, row j among them) and the nominated group's, less the
+// rows that are out.
+struct VolOthers {
+  const DevCluster& c;
+  const DevPreempt& pre;
+  const PreemptVol& vm;
+  int32_t node, g, j0, b, j;
+  __device__ __forceinline__ int32_t operator()(int32_t x, int32_t) const {
+    const int32_t grp = g >= 0 ? vol_class_entries(vm.gvols, vm.gvoff[g], vm.gvoff[g + 1], x) : 0;
+    return (int32_t)class_count(c, x, node) - 1 + grp - vol_out_holders(pre, vm, j0, b, j, x);
+  }
+};
+// NodeInfo.AddPod / RemovePod on the node's attached volumes (volume_bind's
+// rule on the thread's copy): the holdings [e0, e1) of one pod.  A classless
+// holding moves its family's count by arg.  A class holding moves it by one
+// when no other pod on the node holds the volume: for a class of the
+// preemptor's that is held[i] (moved here too), for any other class
+// others(cls, e) counts the other holders.  Families the preemptor has no use
+// of are not read.
+template <typename OTHERS>
+__device__ __forceinline__ void vol_add(VolRow& v, PortHold& h, const int32_t (&cls)[KSIM_MAX_USES],
+                                        const PreemptVol& vm, const VolHold* __restrict__ ents, int32_t e0,
+                                        int32_t e1, int sign, OTHERS others) {
+  for (int32_t e = e0; e < e1; e++) {
+    const VolHold x = ents[e];
+    if (!((vm.fams >> x.fam) & 1u)) continue;
+    int64_t d = (int64_t)sign * x.arg;
+    if (x.cls >= 0) {
+      bool mine = false;
+      int32_t rest = 0;                                  // the volume's other holders on the node
+#pragma unroll
+      for (int i = 0; i < KSIM_MAX_USES; i++)
+        if (((vm.uses >> i) & 1u) && cls[i] == x.cls) {
+          mine = true;
+          rest = sign < 0 ? h.held[i] - 1 : h.held[i];
+          h.held[i] += sign;
+        }
+      if (!mine) rest = others(x.cls, e);
+      d = rest == 0 ? sign : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
+      if (k == x.fam) v.att[k] += d;
+  }
+}
+// nodevolumelimits Filter on the moved counts (volume_limit_fails' rule, 64-bit
+// sums): per family of the preemptor's, new = its classless volumes (own[f])
+// plus its class volumes no pod left on the node holds.  ufam: four bits per
+// use, the family of volume use i.
+__device__ __forceinline__ bool vol_fails(const VolRow& v, const PortHold& h, const int32_t (&cls)[KSIM_MAX_USES],
+                                          const PreemptVol& vm, uint64_t ufam,
+                                          const int64_t (&own)[KSIM_MAX_VOL_FAMILIES]) {
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
+    if (!((vm.fams >> k) & 1u)) continue;
+    int64_t add = own[k];
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++)
+      if (((vm.uses >> i) & 1u) && cls[i] >= 0 && (int)((ufam >> (4 * i)) & 15u) == k) add += h.held[i] == 0;
+    const bool csi = (vm.csi >> k) & 1u;
+    if (v.lim[k] != 2147483647 && v.att[k] + add > (int64_t)v.lim[k] && (!csi || add > 0)) bad = true;
+  }
+  return bad;
 }
 
 // The preemptor's filter-read uses in the domain form (kernel argument, bit i =
@@ -174,12 +283,20 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
 // is the status pass's.  A node that failed PodTopologySpread is a potential
 // node only for the skew reason, re-derived from the row like
 // InterPodAffinity's.
-template <bool PORTS, bool DOM = false, bool PDB = false, bool SPREAD = false, typename DM = PreemptDom>
+// VOL (the volume form; PORTS with it): the dry run also re-runs the node
+// volume limit plugins of the profile.  The thread keeps the node's attached
+// count per family of the preemptor's (VolRow) and, in held[], the node's count
+// of each shared volume the preemptor mounts, beside its port classes (the ids
+// are disjoint; a classless volume use keeps kNoPortClass).  Both move with
+// the rows' holdings (vm.voff / vols); bit 0 of a row's flag says "out of the
+// trial state" from the first removal on, which is what it says at the end.
+template <bool PORTS, bool DOM = false, bool PDB = false, bool SPREAD = false, typename DM = PreemptDom,
+          bool VOL = false, typename VM = NoVol>
 __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
                                                const ksim_pod& p, const PodPlan& plan, const ksim_topo_use* U,
                                                const DevPreempt& pre, int32_t node, int32_t prio, bool fit,
                                                uint32_t port_mask, const DM& dm, bool at_ipa, bool at_pts,
-                                               PreemptNode& out) {
+                                               PreemptNode& out, const VM& vm = VM{}) {
   const int32_t a = pre.off[node], b = pre.off[node + 1];
   int32_t j0 = a;
   while (j0 < b && pre.prio[j0] >= prio) j0++;       // lower priorities: the suffix [j0, b)
@@ -196,6 +313,9 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
   TopoRow t;
   UseMasks mm{};                                        // the roles the dry run's filters read
   bool outside = false;
+  VolRow vr;                                            // VOL: the families' moved counts and limits
+  uint64_t ufam = 0;                                    // VOL: the family of each volume use, four bits each
+  int64_t own[KSIM_MAX_VOL_FAMILIES];                   // VOL: per family, the preemptor's classless volumes
   uint32_t elig = 0, over = 0;                          // SPREAD: the hard uses this node's pods move; spread_filter
   int64_t thr[KSIM_MAX_USES];                           // SPREAD: per hard use, the count the row may reach
   if (DOM) {
@@ -257,11 +377,51 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
         h.held[i] = (int32_t)class_count(c, cls[i], node);
       }
     }
-    if (g >= 0) hold_add(h, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
+    if constexpr (VOL) {
+      ufam = 0;
+#pragma unroll
+      for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
+        own[k] = 0;
+        vr.att[k] = 0;
+        vr.lim[k] = 2147483647;
+        if ((vm.fams >> k) & 1u) {
+          vr.att[k] = c.vol_attached[(size_t)k * c.n + node];
+          vr.lim[k] = c.vol_limit[(size_t)k * c.n + node];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < KSIM_MAX_USES; i++) {
+        if (!((vm.uses >> i) & 1u)) continue;
+        const ksim_topo_use u = load_use(U, i);          // the device copy: family in _pad
+        ufam |= (uint64_t)(u._pad & 15) << (4 * i);
+        if (u.cls >= 0) {
+          cls[i] = u.cls;
+          h.held[i] = (int32_t)class_count(c, u.cls, node);
+        } else {
+#pragma unroll
+          for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
+            if (k == u._pad) own[k] += u.arg;
+        }
+      }
+    }
+    if (g >= 0 && (!VOL || port_mask)) hold_add(h, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
+    if constexpr (VOL) {
+      if (g >= 0) {                                      // the group's volumes, each pod after the ones before it
+        const int32_t g0 = vm.gvoff[g];
+        vol_add(vr, h, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
+          return class_count(c, x, node) + vol_class_entries(vm.gvols, g0, e, x);
+        });
+      }
+      for (int32_t j = j0; j < b; j++) pre.vflag[j] = 0; // nobody is out yet
+    }
   }
   for (int32_t j = j0; j < b; j++) {
     row_add_req(r, pre.req + (size_t)j * KSIM_PREEMPT_REQ, -1, c.n_scalar);
-    if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+    if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+    if constexpr (VOL) {
+      vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
+      pre.vflag[j] = 1;
+    }
     if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
   }
   // the filters the dry run re-runs: 0 = the pod passes
@@ -271,6 +431,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
       if (spread_fails(dm.hard, over, thr, t)) return true;
     }
     if (DOM) return node_port_conflict(mm, t) || ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t) != 0;
+    if constexpr (VOL) return hold_conflict(h, port_mask) || vol_fails(vr, h, cls, vm, ufam, own);
     return PORTS && hold_conflict(h);
   };
   if (!fails()) {
@@ -284,7 +445,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
           for (int32_t e2 = pre.poff[j0]; e2 < pre.poff[j + 1]; e2++) used += pre.pids[e2] == id;
           if (used > pre.pallowed[id]) viol = true;
         }
-        pre.vflag[j] = viol ? kPreemptViolating : 0;
+        pre.vflag[j] = (viol ? kPreemptViolating : 0) | (VOL ? 1 : 0);
       }
     }
     int32_t nv = 0, nviol = 0, high = 0, top = INT32_MIN;
@@ -298,14 +459,18 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
         }
         const int64_t* q = pre.req + (size_t)j * KSIM_PREEMPT_REQ;
         row_add_req(r, q, 1, c.n_scalar);
-        if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
+        if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
         if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
+        if constexpr (VOL)
+          vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], 1, VolOthers{c, pre, vm, node, g, j0, b, j});
         const bool victim = fails();
         pre.vflag[j] = (uint8_t)victim | mark;
         if (victim) {
           row_add_req(r, q, -1, c.n_scalar);
-          if (PORTS) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+          if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
           if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+          if constexpr (VOL)
+            vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
           if (nv == 0) high = pre.prio[j];
           sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
           if (PDB) {                                     // GetEarliestPodStartTime on an unsorted list
@@ -383,6 +548,36 @@ __global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, 
                                           out);
     }
   }
+  pre.res[node] = out;
+}
+
+// k_preempt_nodes for a preemptor with KSIM_USE_VOLUME uses (ksim_preempt_volumes):
+// the volume form, kernels of their own with an argument of their own, so the
+// forms above keep theirs.  The four limit plugins return Unschedulable, so a
+// node whose first failing filter is one of them (vm.at: their places in the
+// profile) is a potential node beside Fit's and NodePorts'.
+template <bool PDB>
+__global__ __launch_bounds__(256) void k_preempt_nodes_vol(DevCluster c, DevPods P, const DevState* __restrict__ st,
+                                                           DevScratch s, DevPreempt pre, int32_t fit_index,
+                                                           int32_t prio, int32_t port_index, uint32_t port_mask,
+                                                           PreemptVol vm) {
+  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= c.n) return;
+  PreemptNode out{};
+  out.cand = 0;
+  const uint32_t f = s.fail[node];
+  const ksim_pod& p = P.pods[st->cursor];
+  bool potential = (fit_index >= 0 && f == (uint32_t)fit_index) || (port_mask && f == (uint32_t)port_index);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t at = (vm.at >> (8 * k)) & 255u;      // 0xff: absent (KSIM_PASSED is no plugin's place)
+    if (at != 255u && f == at) potential = true;
+  }
+  out.potential = potential;
+  if (potential)
+    select_victims<true, false, PDB, false, PreemptDom, true, PreemptVol>(
+        c, P, s, p, P.plans[st->cursor], P.uses + p.use_first, pre, node, prio, fit_index >= 0, port_mask, PreemptDom{},
+        false, false, out, vm);
   pre.res[node] = out;
 }
 
@@ -627,6 +822,15 @@ void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_inde
                      : (pdb ? k_preempt_nodes<false, true> : k_preempt_nodes<false, false>);
     nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
   }
+  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+}
+
+void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
+                            hipStream_t stream, int32_t port_index, uint32_t port_mask, const PreemptVol& vm) {
+  const int blocks = (a.c.n + 255) / 256;
+  if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
+  auto nodes = pre.poff != nullptr ? k_preempt_nodes_vol<true> : k_preempt_nodes_vol<false>;
+  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, vm);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

@@ -435,10 +435,14 @@ class BoundPods:
     (ksim_set_bound_pod_adds; the host-port holdings a dry run for a pod with
     host ports reads).  ``pdb_allowed`` / ``pdb_off`` / ``pdb_ids`` (optional,
     likewise): the PodDisruptionBudgets' disruptionsAllowed and, as a CSR over
-    the rows, the budgets each row matches (ksim_set_bound_pod_pdbs)."""
+    the rows, the budgets each row matches (ksim_set_bound_pod_pdbs).
+    ``vol_off`` / ``vols`` (optional, likewise): the rows' counted volumes as a
+    CSR, ``vols`` = [[class or -1, count, family], ...], kept as
+    ``vol_uses`` (TOPO_USE_DTYPE rows of kind USE_VOLUME;
+    ksim_set_bound_pod_volumes)."""
 
     def __init__(self, node, priority, start_time, req, adds_off=None, adds=None, pdb_allowed=None, pdb_off=None,
-                 pdb_ids=None):
+                 pdb_ids=None, vol_off=None, vols=None):
         self.node = np.ascontiguousarray(node, np.int32)
         self.priority = np.ascontiguousarray(priority, np.int32)
         self.start_time = np.ascontiguousarray(start_time, np.int64)
@@ -462,6 +466,17 @@ class BoundPods:
             self.pdb_ids = np.ascontiguousarray(pdb_ids, np.int32)
             if self.pdb_off.size != self.n + 1:
                 raise ValueError("pdb_off has one entry per row plus one")
+        if (vol_off is None) != (vols is None):
+            raise ValueError("vol_off and vols go together")
+        self.vol_off = self.vol_uses = None
+        if vol_off is not None:
+            self.vol_off = np.ascontiguousarray(vol_off, np.int32)
+            v = np.asarray(vols, np.int32).reshape(-1, 3)
+            self.vol_uses = np.zeros(len(v), TOPO_USE_DTYPE)
+            self.vol_uses["cls"], self.vol_uses["arg"], self.vol_uses["col"] = v[:, 0], v[:, 1], v[:, 2]
+            self.vol_uses["kind"] = USE_VOLUME
+            if self.vol_off.size != self.n + 1:
+                raise ValueError("vol_off has one entry per row plus one")
 
 
 class _PreemptOutC(ctypes.Structure):

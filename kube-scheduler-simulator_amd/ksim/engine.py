@@ -32,6 +32,7 @@ EXPORTS = [
     "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_set_bound_pod_pdbs", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
+    "ksim_set_bound_pod_volumes", "ksim_preempt_volumes",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -114,6 +115,9 @@ def _load(path):
     L.ksim_preempt_nominated.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     if hasattr(L, "ksim_preempt_spread"):       # likewise
         L.ksim_preempt_spread.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    if hasattr(L, "ksim_preempt_volumes"):      # likewise
+        L.ksim_set_bound_pod_volumes.argtypes = [vp, vp, vp]
+        L.ksim_preempt_volumes.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -430,6 +434,22 @@ class Engine:
             self.set_bound_pod_adds(bound.adds_off, bound.adds)
         if getattr(bound, "pdb_off", None) is not None:
             self.set_bound_pod_pdbs(bound.pdb_allowed, bound.pdb_off, bound.pdb_ids)
+        if getattr(bound, "vol_off", None) is not None:
+            self.set_bound_pod_volumes(bound.vol_off, bound.vol_uses)
+
+    def set_bound_pod_volumes(self, off, uses):
+        """The counted volumes the last set_bound_pods' rows hold (CSR: ``off``
+        [n + 1], ``uses`` abi.TOPO_USE_DTYPE rows of kind USE_VOLUME: col =
+        family, cls = the shared volume's class or -1, arg = count), which a
+        dry run for a pod with counted volumes reads (ksim_set_bound_pod_volumes;
+        the engine needs its volume table first)."""
+        off = np.ascontiguousarray(off, np.int32)
+        uses = np.ascontiguousarray(uses, abi.TOPO_USE_DTYPE)
+        n = getattr(self, "_bound_n", None)         # None: no table yet, the library refuses the call
+        if n is not None and off.size != n + 1:
+            raise ValueError("one offset per bound-pod row plus one")
+        self._chk(self.L.ksim_set_bound_pod_volumes(self.h, off.ctypes.data_as(ctypes.c_void_p),
+                                                    uses.ctypes.data_as(ctypes.c_void_p)))
 
     def set_bound_pod_adds(self, off, adds):
         """The count-class contributions of the last set_bound_pods' rows (CSR:
@@ -459,7 +479,7 @@ class Engine:
                                                                               for a in (allowed, off, ids))))
 
     def preempt(self, pods, index: int, priority: int, groups=None, with_pdb: bool = False,
-                hard_spread: bool = False) -> tuple:
+                hard_spread: bool = False, volumes: bool = False) -> tuple:
         """DefaultPreemption PostFilter dry run: (nominated node or -1, victim
         indices into the bound-pod table in the dry run's list order, potential
         nodes, candidates kept); ``with_pdb`` appends the nominated node's
@@ -469,16 +489,25 @@ class Engine:
         ``hard_spread``: the dry run through ksim_preempt_spread, which also
         takes a pod with DoNotSchedule spread constraints (the table then
         needs every class of its rows: ``bound_table(..., full_adds=True)``);
-        off, such a pod is refused (KSIM_E_UNSUPPORTED)."""
+        off, such a pod is refused (KSIM_E_UNSUPPORTED).
+        ``volumes``: the dry run through ksim_preempt_volumes, which also takes
+        a pod with counted volumes (the table then needs the rows' holdings:
+        ``bound_table(..., vol_limits=)``); off, such a pod is refused likewise.
+        Not together with ``hard_spread``: the engine refuses a pod that
+        carries both kinds."""
+        if volumes and hard_spread:
+            raise KsimError(abi.E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use and a KSIM_USE_PTS_HARD "
+                                               "use (the volume form moves no domain counts)")
         self._sync()
         self._ran = True
         out = abi.PreemptOut(max(getattr(self, "_bound_n", 1), 1))
         result = out.result_with_pdb if with_pdb else out.result
         ps = pods.pod_set()
-        if not groups and not hard_spread:
+        if not groups and not hard_spread and not volumes:
             self._chk(self.L.ksim_preempt(self.h, ctypes.byref(ps), index, priority, ctypes.byref(out.c)))
             return result()
-        call = self.L.ksim_preempt_spread if hard_spread else self.L.ksim_preempt_nominated
+        call = self.L.ksim_preempt_volumes if volumes else \
+            self.L.ksim_preempt_spread if hard_spread else self.L.ksim_preempt_nominated
         if not groups:
             self._chk(call(self.h, ctypes.byref(ps), index, priority, None, 0, None, None, None, ctypes.byref(out.c)))
             return result()

@@ -217,7 +217,7 @@ class EnginePlugins:
             self.b.forget(a[0], a[1], a[2])
 
     def post_filter(self, priority: int, bound=None, nominated_node: int = -1, nominated_status=None,
-                    terminating_lower=None, pdbs=None, hard_spread: bool = False
+                    terminating_lower=None, pdbs=None, hard_spread: bool = False, volumes: bool = False
                     ) -> Tuple[Status, int, List[int], bool]:
         """DefaultPreemption.PostFilter (default_preemption.go v1.26):
         PodEligibleToPreemptOthers, then the dry run over this cycle's
@@ -237,7 +237,11 @@ class EnginePlugins:
         goes through ksim_preempt_spread, which re-runs PodTopologySpread on
         each node's moved domain counts (the ``full_adds=True`` table).  ``pdbs``: (allowed, off, ids), the
         PodDisruptionBudgets over the table's rows, set on the engine before
-        the dry run (Engine.set_bound_pod_pdbs)."""
+        the dry run (Engine.set_bound_pod_pdbs).  Pods with counted volumes
+        (KSIM_USE_VOLUME uses) are refused likewise unless ``volumes`` is set:
+        the dry run then goes through ksim_preempt_volumes, which re-runs the
+        node volume limit plugins on each node's moved attachment counts (the
+        table built with ``vol_limits=cluster.vol_limits``)."""
         if nominated_node >= 0 and (nominated_status is None or
                                     nominated_status.code != UNSCHEDULABLE_AND_UNRESOLVABLE):
             if terminating_lower is not None and terminating_lower(nominated_node, priority):
@@ -246,6 +250,8 @@ class EnginePlugins:
         if pdbs is not None:
             self.b.set_bound_pod_pdbs(*pdbs)
         kw = {"hard_spread": True} if hard_spread else {}
+        if volumes:
+            kw["volumes"] = True
         if bound is None:
             node, victims = self.b.preempt(self._pods, self._idx, priority, groups=self._groups, **kw)[:2]
         else:

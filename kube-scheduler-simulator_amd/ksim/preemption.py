@@ -32,7 +32,8 @@ def pdb_matches(rows: Sequence[Pod], pdbs: Sequence[PodDisruptionBudget]) -> Lis
 
 
 def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None,
-                full_adds: bool = False, pdbs: Optional[Sequence[PodDisruptionBudget]] = None) -> abi.BoundPods:
+                full_adds: bool = False, pdbs: Optional[Sequence[PodDisruptionBudget]] = None,
+                vol_limits=None) -> abi.BoundPods:
     """ksim_bound_pods for ``bound`` (pods whose node is in ``cluster``), in list order.
     With ``topo`` (the cluster's ksim.topology.TopologyIndex) the table also
     carries each row's host-port holdings (``topo.port_adds``, over the port
@@ -43,7 +44,12 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=
     run of a pod with required pod (anti-)affinity reads.
     ``pdbs``: the cluster's PodDisruptionBudgets; the table then carries their
     disruptionsAllowed and the budgets each row matches (``pdb_matches``;
-    ksim_set_bound_pod_pdbs).  None or empty: no budgets."""
+    ksim_set_bound_pod_pdbs).  None or empty: no budgets.
+    ``vol_limits``: the cluster's ksim.volumes.VolumeLimits (``cluster.vol_limits``,
+    with ``topo``); the table then carries the rows' counted volumes
+    (``bound_uses``: families by index, class ids from ``topo.volume_class``),
+    which the dry run of a pod with counted volumes reads
+    (ksim_set_bound_pod_volumes)."""
     pos = {n: i for i, n in enumerate(cluster.node_names)}
     rows = [p for p in bound if p.node_name in pos]
     node = np.array([pos[p.node_name] for p in rows], np.int32)
@@ -63,6 +69,16 @@ def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=
         budgets = dict(pdb_allowed=np.array([b.disruptions_allowed for b in pdbs], np.int32),
                        pdb_off=np.cumsum([0] + [len(h) for h in hits]).astype(np.int32),
                        pdb_ids=np.array([k for h in hits for k in h], np.int32))
+    if vol_limits is not None:
+        if topo is None:
+            raise ValueError("vol_limits needs topo (the shared volumes' classes)")
+        voff, vols = [0], []
+        for p in rows:
+            for f, shared, count in vol_limits.bound_uses.get((p.namespace, p.name), ()):
+                cls = -1 if shared is None else topo.volume_class(vol_limits.families[f], shared)
+                vols.append((cls, count, f))
+            voff.append(len(vols))
+        budgets.update(vol_off=np.array(voff, np.int32), vols=np.array(vols, np.int32).reshape(-1, 3))
     if topo is None:
         return abi.BoundPods(node, prio, start, req, **budgets)
     off, adds = [0], []

@@ -211,6 +211,9 @@ class VolumeLimits:
     pod_uses: Dict[Tuple[str, str], List[Tuple[int, Optional[str], int]]] = field(default_factory=dict)
     # volumes two or more pods (bound or pending) hold: (family, unique name) -> pods per node [N] int32
     shared: Dict[Tuple[int, str], np.ndarray] = field(default_factory=dict)
+    # the bound pods' holdings in the form of pod_uses (ksim_set_bound_pod_volumes, through
+    # ksim.preemption.bound_table): what a preemption dry run takes off the node with the pod
+    bound_uses: Dict[Tuple[str, str], List[Tuple[int, Optional[str], int]]] = field(default_factory=dict)
 
     def reordered(self, node_names: Sequence[str]) -> "VolumeLimits":
         """The same tables with the nodes in another order (the encoded cluster's)."""
@@ -220,7 +223,8 @@ class VolumeLimits:
         idx = np.array([pos[n] for n in node_names], np.int64)
         return VolumeLimits(list(node_names), self.families, self.family_plugin,
                             np.ascontiguousarray(self.limit[:, idx]), np.ascontiguousarray(self.attached[:, idx]),
-                            self.pod_uses, {k: np.ascontiguousarray(v[idx]) for k, v in self.shared.items()})
+                            self.pod_uses, {k: np.ascontiguousarray(v[idx]) for k, v in self.shared.items()},
+                            self.bound_uses)
 
 
 def in_tree_limit(source: str, node) -> int:
@@ -316,14 +320,14 @@ class VolumeIndex:
                 vols = self.counted_volumes(p)
             except VolumeUnsupported:
                 continue                                         # an existing pod nobody can count: ignored, as today
-            bound_vols.append((pos[p.node_name], vols))
+            bound_vols.append((pos[p.node_name], vols, p))
         for p in pending:
             try:
                 vols = self.counted_volumes(p)
             except VolumeUnsupported:
                 continue
             pend_vols.append((p, vols))
-        for _, vols in bound_vols + pend_vols:
+        for vols in [b[1] for b in bound_vols] + [q[1] for q in pend_vols]:
             for v in vols:
                 held[v] = held.get(v, 0) + 1
         in_tree_keys = {f[0]: src for src, f in IN_TREE_FAMILIES.items()}
@@ -346,7 +350,7 @@ class VolumeIndex:
         for v, k in held.items():
             if k >= 2:
                 shared[(fidx[v[0]], v[1])] = np.zeros(N, np.int32)
-        for i, vols in bound_vols:
+        for i, vols, _ in bound_vols:
             for v in vols:
                 on_node[i].add(v)
                 if held[v] >= 2:
@@ -355,10 +359,7 @@ class VolumeIndex:
         for i in range(N):
             for v in on_node[i]:
                 attached[fidx[v[0]], i] += 1
-        uses: Dict[Tuple[str, str], List[Tuple[int, Optional[str], int]]] = {}
-        for p, vols in pend_vols:
-            if not vols:
-                continue
+        def entries(vols) -> List[Tuple[int, Optional[str], int]]:
             u: List[Tuple[int, Optional[str], int]] = []
             own = [0] * F
             for v in vols:
@@ -367,8 +368,11 @@ class VolumeIndex:
                 else:
                     own[fidx[v[0]]] += 1
             u.extend((f, None, c) for f, c in enumerate(own) if c)
-            uses[(p.namespace, p.name)] = u
-        return VolumeLimits(names, families, plugin, limit, attached, uses, shared)
+            return u
+
+        uses = {(p.namespace, p.name): entries(vols) for p, vols in pend_vols if vols}
+        bound_uses = {(p.namespace, p.name): entries(vols) for _, vols, p in bound_vols if vols}
+        return VolumeLimits(names, families, plugin, limit, attached, uses, shared, bound_uses)
 
     # ---- the PV controller (Immediate claims) ---------------------------------
     def _class_of(self, pvc: PersistentVolumeClaim) -> str:

@@ -178,7 +178,8 @@ def record_cycle(store: Store, cluster: EncodedCluster, prof: SchedulerProfile, 
 
 
 def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: SchedulerProfile, pods, index: int,
-                 priority: int = 0, bound=None, pdbs=None, hard_spread: bool = False) -> Dict:
+                 priority: int = 0, bound=None, pdbs=None, hard_spread: bool = False,
+                 volumes: bool = False) -> Dict:
     """One deterministic compat cycle as the wrapped plugins see it: the cycle
     (ksim_eval_pod), then for an unschedulable pod DefaultPreemption's
     PostFilter dry run (ksim_preempt over the bound-pod table set with
@@ -191,7 +192,11 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     count into (``full_adds=True``).  A pod with DoNotSchedule spread is refused
     (KSIM_E_UNSUPPORTED) unless ``hard_spread`` is set: the dry run then goes
     through ksim_preempt_spread (``Engine.preempt(..., hard_spread=True)``),
-    which re-runs PodTopologySpread too and needs the ``full_adds=True`` table."""
+    which re-runs PodTopologySpread too and needs the ``full_adds=True`` table.
+    A pod with counted volumes is refused likewise unless ``volumes`` is set:
+    the dry run then goes through ksim_preempt_volumes
+    (``Engine.preempt(..., volumes=True)``), which re-runs the node volume limit
+    plugins and needs the table built with ``vol_limits=cluster.vol_limits``."""
     res = backend.eval_pod(pods, index) if hasattr(backend, "eval_pod") else backend.cycle(pods, index)
     nominated = -1
     post = [original_name(p.name) for p in prof.plugins["postFilter"].enabled]
@@ -201,6 +206,8 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
             if pdbs is not None:
                 backend.set_bound_pod_pdbs(*pdbs)
             kw = {"hard_spread": True} if hard_spread else {}
+            if volumes:
+                kw["volumes"] = True
             out = backend.preempt(pods, index, priority, **kw) if bound is None else \
                 backend.preempt(pods, index, priority, bound, **kw)
             nominated = int(out[0])

@@ -19,17 +19,25 @@ constraint (maxSkew 1 on the zone over app=x): every node is a potential node
 ksim_preempt_spread (one more small launch, k_preempt_spread_mins), and every
 node is a candidate.
 
+--volumes: the use-free cluster where every bound pod holds one EBS volume of
+its own (limit 4 a node, so every node is full) and one bound pod in eight
+shares a CSI volume with its neighbour on the node; the preemptor brings one
+new EBS volume and mounts node 0's shared CSI volume.  Every node is a
+potential node (Fit fails first) and a candidate, and each runs the volume
+form of the dry run through ksim_preempt_volumes.  The table carries every
+row's holdings.
+
 --pdbs K: K PodDisruptionBudgets with disruptionsAllowed 1 over the table,
 the bound pods of node v in budget v % K (ksim_set_bound_pod_pdbs), so all but
 the most important lower-priority pod of a node violate: the call takes the
-PDB form of the kernels.  With --anti or --spread too.
+PDB form of the kernels.  With --anti, --spread or --volumes too.
 
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread] [--pdbs K]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread | --volumes] [--pdbs K]
 """
 import argparse
 import json
@@ -47,7 +55,8 @@ import numpy as np  # noqa: E402
 
 from ksim import abi, engine, profile  # noqa: E402
 from ksim.encode import encode_cluster, encode_pods  # noqa: E402
-from ksim.model import Container, LabelSelector, Node, Pod, PodAffinityTerm, TopologySpreadConstraint  # noqa: E402
+from ksim.model import (Container, LabelSelector, Node, PersistentVolume, PersistentVolumeClaim, Pod,  # noqa: E402
+                        PodAffinityTerm, TopologySpreadConstraint)
 
 ZONE, N_ZONES = "topology.kubernetes.io/zone", 50
 
@@ -104,6 +113,48 @@ def build_anti(n_nodes: int, spread: bool = False):
     return cluster, table, enc, prof
 
 
+def build_volumes(n_nodes: int):
+    """build()'s load with counted volumes on every bound pod and the preemptor."""
+    from ksim.preemption import bound_table
+    from ksim.volumes import VolumeIndex
+    rng = np.random.default_rng(7)
+    ebs, csi = "attachable-volumes-aws-ebs", "attachable-volumes-csi-x"
+    nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}"},
+                  allocatable={"cpu": "10", "memory": "64Gi", "pods": "110", ebs: "4", csi: "8"}) for i in range(n_nodes)]
+    pvs, pvcs = [], []
+
+    def claim(name, **source):
+        pv = PersistentVolume(name="pv-" + name, **source)
+        pv.claim_ref = ("default", name)
+        pvs.append(pv)
+        pvcs.append(PersistentVolumeClaim(name=name, namespace="default", volume_name=pv.name))
+        return name
+    bound, start = [], {}
+    for v in range(n_nodes):
+        for k in range(4):
+            g = 4 * v + k
+            claims = [claim(f"e{g}", source="awsElasticBlockStore", source_id=f"vol-{g}")]
+            if g % 8 == 0:                               # shared with the next pod of the node
+                claim(f"s{g}", source="csi", source_id=f"h{g}", csi_driver="x")
+            if g % 8 < 2:
+                claims.append(f"s{g - g % 8}")
+            bound.append(Pod(f"b{v}-{k}", node_name=nodes[v].name, priority=int(rng.choice([0, 10, 100, 500])),
+                             containers=[Container({"cpu": "2400m"})], pvc_claims=claims))
+            start[bound[-1].name] = int(rng.integers(0, 1000))
+    pod = Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})],
+              pvc_claims=[claim("mine", source="awsElasticBlockStore", source_id="vol-mine"), "s0"])
+    index = VolumeIndex.from_nodes(nodes, pvs, pvcs)
+    cluster, _ = encode_cluster(nodes, bound)
+    cluster.set_volume_limits(index.volume_limits(nodes, bound, [pod]))
+    enc = encode_pods(cluster, [pod], volumes=index)
+    kinds = [int(k) for k in enc.uses["kind"][:int(enc.pods[0]["use_count"])]]
+    assert kinds == [abi.USE_VOLUME, abi.USE_VOLUME] and sorted(int(c) >= 0 for c in enc.uses["cls"][:2]) == [False, True]
+    table = bound_table(cluster, bound, start, cluster.topo, vol_limits=cluster.vol_limits)
+    assert int(table.vol_off[-1]) == len(bound) + 2 * ((len(bound) + 7) // 8)
+    prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
+    return cluster, table, enc, prof
+
+
 def pct(xs, q):
     xs = sorted(xs)
     return xs[min(len(xs) - 1, int(q * len(xs)))]
@@ -122,12 +173,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
     ap.add_argument("--spread", action="store_true", help="a preemptor with a DoNotSchedule zone spread constraint")
+    ap.add_argument("--volumes", action="store_true", help="counted volumes on every bound pod and the preemptor")
     ap.add_argument("--pdbs", type=int, default=0, help="this many budgets (disruptionsAllowed 1), each bound pod in one")
     args = ap.parse_args()
-    if args.anti and args.spread:
-        ap.error("--anti or --spread, not both")
-    cluster, table, enc, prof = build_anti(args.nodes, args.spread) if args.anti or args.spread else build(args.nodes)
-    kw = dict(hard_spread=True) if args.spread else {}
+    if args.anti + args.spread + args.volumes > 1:
+        ap.error("--anti, --spread or --volumes, not two of them")
+    cluster, table, enc, prof = build_anti(args.nodes, args.spread) if args.anti or args.spread else \
+        build_volumes(args.nodes) if args.volumes else build(args.nodes)
+    kw = dict(hard_spread=True) if args.spread else dict(volumes=True) if args.volumes else {}
     budgets = None
     if args.pdbs > 0:
         budgets = (np.ones(args.pdbs, np.int32), np.arange(table.n + 1, dtype=np.int32),
@@ -150,7 +203,8 @@ def main():
         eng.close()
         runs.append(summary(us))
         every += us
-    name = ("preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else "preempt_use_free") + ("_pdb" if budgets is not None else "")
+    name = ("preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else
+            "preempt_volumes" if args.volumes else "preempt_use_free") + ("_pdb" if budgets is not None else "")
     extra = dict(pdbs=args.pdbs, pdb_violations=result[4]) if budgets is not None else {}
     print(json.dumps(dict(bench=name, library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
                           bound_pods=table.n, calls=args.calls, repeats=args.repeats,
