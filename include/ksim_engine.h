@@ -1055,6 +1055,49 @@ int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_i
                          const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
                          const int32_t* first, const int32_t* count, ksim_preempt_out* out);
 
+/* The full dry run: ksim_preempt_nominated for every preemptor the per-pod
+ * cycle accepts (n_groups = 0 is allowed).  One preemptor may carry any mix of
+ * KSIM_USE_NODE_PORT, KSIM_USE_IPA_AFFINITY / IPA_ANTI / IPA_EXISTING_ANTI,
+ * KSIM_USE_PTS_HARD and KSIM_USE_VOLUME uses (and the score-only kinds, which
+ * are ignored), and volume groups (vb_count / vz_count).  It re-runs every
+ * Filter of the profile whose verdict eviction can change or that is ordered
+ * after the failing plugin: NodeResourcesFit, NodePorts, the four volume limit
+ * plugins, VolumeBinding, VolumeZone, PodTopologySpread and InterPodAffinity.
+ *   dispatch    a preemptor without volume uses, or with volume uses and
+ *               neither InterPodAffinity nor DoNotSchedule spread uses the
+ *               profile filters on, runs the form ksim_preempt_nominated,
+ *               ksim_preempt_spread or ksim_preempt_volumes runs for it and,
+ *               without volume groups, returns exactly what that call returns;
+ *   the full form  volume uses beside (anti-)affinity or DoNotSchedule spread
+ *               uses: the thread moves the node's row by the class adds
+ *               (ksim_preempt_spread's rules) and the attached counts by the
+ *               holdings (ksim_preempt_volumes' rules); the two tables are
+ *               disjoint, no add names a volume class.  A nominated group's
+ *               adds and volumes both go onto the node before the first trial.
+ *               The pod passes a trial when NodeResourcesFit, NodePorts,
+ *               PodTopologySpread, InterPodAffinity and every limit plugin of
+ *               the filter list pass.  A potential node failed first at Fit, at
+ *               NodePorts, at a limit plugin, at InterPodAffinity for an
+ *               anti-affinity reason or at PodTopologySpread for the skew
+ *               reason.  A use whose plugin the filter list lacks is not read;
+ *   volume groups  VolumeBinding's and VolumeZone's verdicts depend on the node
+ *               and the pod's groups alone.  For a preemptor with groups, a
+ *               potential node that fails either (the plugin being in the
+ *               filter list) is no candidate whatever its victims; it counts in
+ *               n_potential and does not count toward the numCandidates cut.  A
+ *               node whose first failing filter is one of the two is no
+ *               potential node, as in every call.
+ * KSIM_E_INVALID, the message naming the call to make: the bound table lacks
+ * the class adds (ksim_set_bound_pod_adds, every class) for a pod with a port,
+ * (anti-)affinity or DoNotSchedule spread use, or the holdings
+ * (ksim_set_bound_pod_volumes) for a pod with a volume use.
+ * KSIM_E_UNSUPPORTED, as in the other calls: shard handles, NetworkBandwidth in
+ * the filter list, KSIM_POD_NODE_NAMES pods.  Pass 2 of
+ * RunFilterPluginsWithNominatedPods is not re-run inside the dry run. */
+int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
+                      const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
+                      const int32_t* first, const int32_t* count, ksim_preempt_out* out);
+
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's
  * PreFilter / PreScore: upstream countPodsMatchSelector,

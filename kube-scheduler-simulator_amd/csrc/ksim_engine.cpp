@@ -5420,10 +5420,13 @@ extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_
 
 // The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
 // DoNotSchedule spread uses are refused), ksim_preempt_spread and
-// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted).
+// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted) and
+// ksim_preempt_full (full = true: every mix of uses is accepted, and a
+// preemptor with volume groups has VolumeBinding / VolumeZone re-run).
 static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                        const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
-                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false) {
+                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false,
+                       bool full = false) {
   int rc = ensure_ready(h);
   if (rc) return rc;
   if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
@@ -5431,7 +5434,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
     return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
   const bool vol_form = has_volume_use(ps, pod_index);   // the volume form of k_preempt_nodes
-  if (vol_form && !volumes)
+  if (vol_form && !volumes && !full)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
                                           "re-run the node volume limit plugins)");
   {
@@ -5468,7 +5471,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   const ksim_pod& pp = ps->pods[pod_index];
   const bool topo = pp.use_count > 0;
   uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
-  for (int32_t k = 0; k < pp.use_count && vol_form; k++) {
+  for (int32_t k = 0; k < pp.use_count && vol_form && !full; k++) {
     const uint8_t kind = ps->uses[pp.use_first + k].kind;
     static const char* const kNames[] = {"KSIM_USE_PTS_HARD", nullptr, "KSIM_USE_IPA_EXISTING_ANTI",
                                          "KSIM_USE_IPA_AFFINITY", "KSIM_USE_IPA_ANTI"};
@@ -5476,7 +5479,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_VOLUME use and a ") +
                                                 kNames[kind] + " use (the volume form moves no domain counts)");
   }
-  for (int32_t k = 0; k < pp.use_count && !spread; k++)
+  for (int32_t k = 0; k < pp.use_count && !spread && !full; k++)
     if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
       return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
                                             "victims' domains: ksim_preempt_spread)");
@@ -5609,13 +5612,21 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
     }
   }
-  if (vol_form) {
-    vm.voff = h->pre_voff;
-    vm.vols = h->pre_vols;
-    launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
+  // ksim_preempt_full: the static volume filters of a preemptor with groups
+  const bool vb = full && pp.vb_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_BINDING);
+  const bool vz = full && pp.vz_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_ZONE);
+  vm.voff = h->pre_voff;
+  vm.vols = h->pre_vols;
+  if (vol_form && dom_form && vm.uses) {                   // only ksim_preempt_full gets here: the full form
+    launch_preempt_full(a, pre, fit, priority, h->stream, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
+                        hard_mask, h->pre_smin, vm, vb, vz);
   } else {
-    launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
-                   hard_mask, h->pre_smin);
+    if (vol_form && !dom_form)
+      launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
+    else
+      launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask,
+                     pts, hard_mask, h->pre_smin);
+    if (vb || vz) launch_preempt_veto(a, pre, h->stream, vb, vz);
   }
   HIPCHK(h, hipGetLastError());
   if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
@@ -5657,6 +5668,12 @@ extern "C" int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* ps, int3
                                     const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                     const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
   return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false, true);
+}
+
+extern "C" int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                 const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                 const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true, true, true);
 }
 
 extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,

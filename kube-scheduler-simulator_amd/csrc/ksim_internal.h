@@ -377,6 +377,18 @@ struct PreemptVol {
 // volume uses (and possibly NodePorts uses); a.c carries the volume table.
 void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
                             hipStream_t stream, int32_t port_index, uint32_t port_mask, const PreemptVol& vm);
+// The full form (ksim_preempt_full): a preemptor with volume uses beside
+// required pod (anti-)affinity or DoNotSchedule spread uses; launch_preempt's
+// and launch_preempt_volumes' arguments together.  vb / vz: the preemptor has
+// volume groups and VolumeBinding / VolumeZone is in the filter list; the
+// nodes either fails leave the candidates before the pick.
+void launch_preempt_full(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
+                         hipStream_t stream, int32_t port_index, uint32_t port_mask, int32_t ipa_index, uint32_t aff,
+                         uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin,
+                         const PreemptVol& vm, bool vb, bool vz);
+// The same veto after one of the older forms' launches, and the pick again on
+// the candidates that are left.
+void launch_preempt_veto(const LaunchArgs& a, const DevPreempt& pre, hipStream_t stream, bool vb, bool vz);
 
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);

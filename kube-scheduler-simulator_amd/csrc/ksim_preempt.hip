@@ -27,7 +27,11 @@
 // volumes (ksim_preempt_volumes) takes the volume form, k_preempt_nodes_vol:
 // the ports form plus the node volume limit plugins on the node's attached
 // count per family, moved with the rows' holdings (ksim_set_bound_pod_volumes);
-// a node that failed one of those plugins is a potential node too.  One
+// a node that failed one of those plugins is a potential node too.  A pod with
+// counted volumes beside (anti-)affinity or spread uses (ksim_preempt_full)
+// takes the full form, k_preempt_nodes_full: the spread form and the volume
+// form in one thread; for a pod with volume groups k_preempt_static_veto then
+// takes the nodes VolumeBinding or VolumeZone fails out of the candidates.  One
 // block then keeps candidates in nodeTree order (upstream scans from a random
 // offset; offset 0 here) until numCandidates were found and one of them has
 // no PDB violation, and picks one by pickOneNodeForPreemption's criteria.
@@ -85,6 +89,18 @@ struct VolRow {
   int32_t lim[KSIM_MAX_VOL_FAMILIES];
 };
 struct NoVol {};                                         // the other forms' (empty) volume argument
+// The full form's holder counts: the TopoRow's own entries (load_topo_row put a
+// volume use's class count there), under the name the volume form reads.
+struct RowHold {
+  int64_t (&held)[KSIM_MAX_USES];
+};
+// The volume side's holder counts of a form: the row's in the full form (ROW),
+// held[] in the volume form.
+template <bool ROW>
+__device__ __forceinline__ decltype(auto) vol_holder(PortHold& h, TopoRow& t) {
+  if constexpr (ROW) return RowHold{t.x};
+  else return (h);
+}
 // nodeports Filter on the holdings of the volume form: only the port uses
 // conflict (a held volume class is no conflict)
 __device__ __forceinline__ bool hold_conflict(const PortHold& h, uint32_t port_mask) {
@@ -134,8 +150,8 @@ struct VolOthers {
 // preemptor's that is held[i] (moved here too), for any other class
 // others(cls, e) counts the other holders.  Families the preemptor has no use
 // of are not read.
-template <typename OTHERS>
-__device__ __forceinline__ void vol_add(VolRow& v, PortHold& h, const int32_t (&cls)[KSIM_MAX_USES],
+template <typename OTHERS, typename HOLD>
+__device__ __forceinline__ void vol_add(VolRow& v, HOLD&& h, const int32_t (&cls)[KSIM_MAX_USES],
                                         const PreemptVol& vm, const VolHold* __restrict__ ents, int32_t e0,
                                         int32_t e1, int sign, OTHERS others) {
   for (int32_t e = e0; e < e1; e++) {
@@ -149,7 +165,7 @@ __device__ __forceinline__ void vol_add(VolRow& v, PortHold& h, const int32_t (&
       for (int i = 0; i < KSIM_MAX_USES; i++)
         if (((vm.uses >> i) & 1u) && cls[i] == x.cls) {
           mine = true;
-          rest = sign < 0 ? h.held[i] - 1 : h.held[i];
+          rest = (int32_t)(sign < 0 ? h.held[i] - 1 : h.held[i]);
           h.held[i] += sign;
         }
       if (!mine) rest = others(x.cls, e);
@@ -164,7 +180,8 @@ __device__ __forceinline__ void vol_add(VolRow& v, PortHold& h, const int32_t (&
 // sums): per family of the preemptor's, new = its classless volumes (own[f])
 // plus its class volumes no pod left on the node holds.  ufam: four bits per
 // use, the family of volume use i.
-__device__ __forceinline__ bool vol_fails(const VolRow& v, const PortHold& h, const int32_t (&cls)[KSIM_MAX_USES],
+template <typename HOLD>
+__device__ __forceinline__ bool vol_fails(const VolRow& v, const HOLD& h, const int32_t (&cls)[KSIM_MAX_USES],
                                           const PreemptVol& vm, uint64_t ufam,
                                           const int64_t (&own)[KSIM_MAX_VOL_FAMILIES]) {
   bool bad = false;
@@ -290,6 +307,10 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
 // are disjoint; a classless volume use keeps kNoPortClass).  Both move with
 // the rows' holdings (vm.voff / vols); bit 0 of a row's flag says "out of the
 // trial state" from the first removal on, which is what it says at the end.
+// VOL with DOM and SPREAD (the full form): both sides at once.  Ports, affinity
+// and spread counts move in the TopoRow by the class adds; VolRow moves by the
+// holdings, and a shared volume's holder count is the row's own entry of the
+// volume use (RowHold) instead of held[], which the full form does not keep.
 template <bool PORTS, bool DOM = false, bool PDB = false, bool SPREAD = false, typename DM = PreemptDom,
           bool VOL = false, typename VM = NoVol>
 __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
@@ -367,6 +388,40 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
     }
     out.potential = 1;
   }
+  decltype(auto) hv = vol_holder<VOL && DOM>(h, t);      // VOL: the shared volumes' holder counts
+  if constexpr (VOL && DOM) {                           // the full form's volume side, as the volume form's below
+    ufam = 0;
+#pragma unroll
+    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
+      own[k] = 0;
+      vr.att[k] = 0;
+      vr.lim[k] = 2147483647;
+      if ((vm.fams >> k) & 1u) {
+        vr.att[k] = c.vol_attached[(size_t)k * c.n + node];
+        vr.lim[k] = c.vol_limit[(size_t)k * c.n + node];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      if (!((vm.uses >> i) & 1u)) continue;
+      const ksim_topo_use u = load_use(U, i);            // the device copy: family in _pad
+      ufam |= (uint64_t)(u._pad & 15) << (4 * i);
+      if (u.cls >= 0) {
+        cls[i] = u.cls;                                  // t.x[i]: the node's holders (load_topo_row); no add names it
+      } else {
+#pragma unroll
+        for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
+          if (k == u._pad) own[k] += u.arg;
+      }
+    }
+    if (g >= 0) {                                        // the group's volumes, each pod after the ones before it
+      const int32_t g0 = vm.gvoff[g];
+      vol_add(vr, hv, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
+        return class_count(c, x, node) + vol_class_entries(vm.gvols, g0, e, x);
+      });
+    }
+    for (int32_t j = j0; j < b; j++) pre.vflag[j] = 0;   // nobody is out yet
+  }
   if (PORTS) {
 #pragma unroll
     for (int i = 0; i < KSIM_MAX_USES; i++) {
@@ -408,7 +463,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
     if constexpr (VOL) {
       if (g >= 0) {                                      // the group's volumes, each pod after the ones before it
         const int32_t g0 = vm.gvoff[g];
-        vol_add(vr, h, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
+        vol_add(vr, hv, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
           return class_count(c, x, node) + vol_class_entries(vm.gvols, g0, e, x);
         });
       }
@@ -419,7 +474,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
     row_add_req(r, pre.req + (size_t)j * KSIM_PREEMPT_REQ, -1, c.n_scalar);
     if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
     if constexpr (VOL) {
-      vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
+      vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
       pre.vflag[j] = 1;
     }
     if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
@@ -430,8 +485,11 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
     if constexpr (SPREAD) {
       if (spread_fails(dm.hard, over, thr, t)) return true;
     }
+    if constexpr (VOL && DOM) {
+      if (vol_fails(vr, hv, cls, vm, ufam, own)) return true;
+    }
     if (DOM) return node_port_conflict(mm, t) || ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t) != 0;
-    if constexpr (VOL) return hold_conflict(h, port_mask) || vol_fails(vr, h, cls, vm, ufam, own);
+    if constexpr (VOL) return hold_conflict(h, port_mask) || vol_fails(vr, hv, cls, vm, ufam, own);
     return PORTS && hold_conflict(h);
   };
   if (!fails()) {
@@ -462,7 +520,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
         if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
         if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
         if constexpr (VOL)
-          vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], 1, VolOthers{c, pre, vm, node, g, j0, b, j});
+          vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], 1, VolOthers{c, pre, vm, node, g, j0, b, j});
         const bool victim = fails();
         pre.vflag[j] = (uint8_t)victim | mark;
         if (victim) {
@@ -470,7 +528,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
           if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
           if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
           if constexpr (VOL)
-            vol_add(vr, h, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
+            vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
           if (nv == 0) high = pre.prio[j];
           sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
           if (PDB) {                                     // GetEarliestPodStartTime on an unsorted list
@@ -579,6 +637,61 @@ __global__ __launch_bounds__(256) void k_preempt_nodes_vol(DevCluster c, DevPods
         c, P, s, p, P.plans[st->cursor], P.uses + p.use_first, pre, node, prio, fit_index >= 0, port_mask, PreemptDom{},
         false, false, out, vm);
   pre.res[node] = out;
+}
+
+// k_preempt_nodes for a preemptor with KSIM_USE_VOLUME uses beside required pod
+// (anti-)affinity or DoNotSchedule spread uses (ksim_preempt_full): the full
+// form, the spread form and the volume form in one thread, kernels of their
+// own again with both arguments.  The thread keeps one TopoRow, moved by
+// topo_add over the rows' class adds (ports, affinity and spread counts), and
+// VolRow, moved by vol_add over the rows' holdings; a shared volume's holder
+// count lives in the row's own entry (no add names a volume class, so only
+// vol_add moves it).  ds.hard may be empty (volumes beside affinity alone):
+// then no use is a spread use and PodTopologySpread's place is not read.
+template <bool PDB>
+__global__ __launch_bounds__(256) void k_preempt_nodes_full(DevCluster c, DevPods P, const DevState* __restrict__ st,
+                                                            DevScratch s, DevPreempt pre, int32_t fit_index,
+                                                            int32_t prio, int32_t port_index, uint32_t port_mask,
+                                                            PreemptSpread ds, PreemptVol vm) {
+  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= c.n) return;
+  PreemptNode out{};
+  out.cand = 0;
+  const uint32_t f = s.fail[node];
+  const ksim_pod& p = P.pods[st->cursor];
+  const bool at_ipa = (ds.aff | ds.anti | ds.exist) != 0 && f == (uint32_t)ds.ipa_index;
+  const bool at_pts = ds.hard != 0 && f == (uint32_t)ds.pts_index;
+  bool enter = (fit_index >= 0 && f == (uint32_t)fit_index) || (port_mask && f == (uint32_t)port_index) || at_ipa ||
+               at_pts;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t at = (vm.at >> (8 * k)) & 255u;      // 0xff: absent (KSIM_PASSED is no plugin's place)
+    if (at != 255u && f == at) enter = true;
+  }
+  if (enter)
+    select_victims<false, true, PDB, true, PreemptSpread, true, PreemptVol>(
+        c, P, s, p, P.plans[st->cursor], P.uses + p.use_first, pre, node, prio, fit_index >= 0, port_mask, ds, at_ipa,
+        at_pts, out, vm);
+  pre.res[node] = out;
+}
+
+// VolumeBinding and VolumeZone after the removals (ksim_preempt_full, for a
+// preemptor with volume groups): both verdicts depend on the node and the
+// pod's groups alone, so a potential node either check fails is no candidate
+// whatever its victims.  It stays a potential node (upstream counts it before
+// the dry run) but leaves the candidates before k_preempt_pick scans them, so
+// it does not count toward the numCandidates cut.  vb / vz: the plugin is in
+// the filter list.
+__global__ __launch_bounds__(256) void k_preempt_static_veto(DevCluster c, DevPods P,
+                                                             const DevState* __restrict__ st, DevPreempt pre,
+                                                             int32_t vb, int32_t vz) {
+  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= c.n || pre.res[node].cand == 0) return;
+  const ksim_pod& p = P.pods[st->cursor];
+  bool bad = false;
+  if (vb && p.vb_count) bad = volume_binding_fails(c, P, p.vb_first, p.vb_count, node) != 0;
+  if (!bad && vz && p.vz_count) bad = !volume_groups_match(c, P, p.vz_first, p.vz_count, node);
+  if (bad) pre.res[node].cand = 0;                       // the violations above bit 0 go with it
 }
 
 // The cluster-wide total of each required-affinity use over the nodes that
@@ -831,6 +944,36 @@ void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t 
   if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
   auto nodes = pre.poff != nullptr ? k_preempt_nodes_vol<true> : k_preempt_nodes_vol<false>;
   nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, vm);
+  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+}
+
+void launch_preempt_full(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
+                         hipStream_t stream, int32_t port_index, uint32_t port_mask, int32_t ipa_index, uint32_t aff,
+                         uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin,
+                         const PreemptVol& vm, bool vb, bool vz) {
+  const int blocks = (a.c.n + 255) / 256;
+  if (port_index < 0) port_mask = 0;                     // as launch_preempt: a use whose filter the profile lacks
+  if (ipa_index < 0) aff = anti = exist = 0;             // is in none of the masks
+  if (pts_index < 0) hard = 0;
+  PreemptSpread ds{};
+  ds.aff = aff;
+  ds.anti = anti;
+  ds.exist = exist;
+  ds.ipa_index = ipa_index;
+  ds.hard = hard;
+  ds.pts_index = pts_index;
+  ds.smin = smin;
+  if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
+  if (hard) k_preempt_spread_mins<<<__builtin_popcount(hard), 256, 0, stream>>>(a.c, a.P, a.st, a.s, smin, hard);
+  auto nodes = pre.poff != nullptr ? k_preempt_nodes_full<true> : k_preempt_nodes_full<false>;
+  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, ds, vm);
+  if (vb || vz) k_preempt_static_veto<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, pre, vb, vz);
+  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+}
+
+void launch_preempt_veto(const LaunchArgs& a, const DevPreempt& pre, hipStream_t stream, bool vb, bool vz) {
+  const int blocks = (a.c.n + 255) / 256;
+  k_preempt_static_veto<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, pre, vb, vz);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

@@ -32,7 +32,7 @@ EXPORTS = [
     "ksim_set_bound_pods", "ksim_set_bound_pod_adds", "ksim_set_bound_pod_pdbs", "ksim_preempt", "ksim_upsert_nodes", "ksim_remove_node",
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
-    "ksim_set_bound_pod_volumes", "ksim_preempt_volumes",
+    "ksim_set_bound_pod_volumes", "ksim_preempt_volumes", "ksim_preempt_full",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -118,6 +118,8 @@ def _load(path):
     if hasattr(L, "ksim_preempt_volumes"):      # likewise
         L.ksim_set_bound_pod_volumes.argtypes = [vp, vp, vp]
         L.ksim_preempt_volumes.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    if hasattr(L, "ksim_preempt_full"):         # likewise
+        L.ksim_preempt_full.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -479,7 +481,7 @@ class Engine:
                                                                               for a in (allowed, off, ids))))
 
     def preempt(self, pods, index: int, priority: int, groups=None, with_pdb: bool = False,
-                hard_spread: bool = False, volumes: bool = False) -> tuple:
+                hard_spread: bool = False, volumes: bool = False, full: bool = False) -> tuple:
         """DefaultPreemption PostFilter dry run: (nominated node or -1, victim
         indices into the bound-pod table in the dry run's list order, potential
         nodes, candidates kept); ``with_pdb`` appends the nominated node's
@@ -494,8 +496,14 @@ class Engine:
         a pod with counted volumes (the table then needs the rows' holdings:
         ``bound_table(..., vol_limits=)``); off, such a pod is refused likewise.
         Not together with ``hard_spread``: the engine refuses a pod that
-        carries both kinds."""
-        if volumes and hard_spread:
+        carries both kinds.
+        ``full``: the dry run through ksim_preempt_full, whatever the other two
+        say: it takes every mix of host ports, required pod (anti-)affinity,
+        DoNotSchedule spread and counted volumes on one pod (the table then
+        needs both: ``bound_table(..., full_adds=True, vol_limits=)``), and for
+        a pod with volume groups it re-runs VolumeBinding and VolumeZone on
+        the candidates."""
+        if volumes and hard_spread and not full:
             raise KsimError(abi.E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use and a KSIM_USE_PTS_HARD "
                                                "use (the volume form moves no domain counts)")
         self._sync()
@@ -503,10 +511,10 @@ class Engine:
         out = abi.PreemptOut(max(getattr(self, "_bound_n", 1), 1))
         result = out.result_with_pdb if with_pdb else out.result
         ps = pods.pod_set()
-        if not groups and not hard_spread and not volumes:
+        if not groups and not hard_spread and not volumes and not full:
             self._chk(self.L.ksim_preempt(self.h, ctypes.byref(ps), index, priority, ctypes.byref(out.c)))
             return result()
-        call = self.L.ksim_preempt_volumes if volumes else \
+        call = self.L.ksim_preempt_full if full else self.L.ksim_preempt_volumes if volumes else \
             self.L.ksim_preempt_spread if hard_spread else self.L.ksim_preempt_nominated
         if not groups:
             self._chk(call(self.h, ctypes.byref(ps), index, priority, None, 0, None, None, None, ctypes.byref(out.c)))

@@ -217,8 +217,8 @@ class EnginePlugins:
             self.b.forget(a[0], a[1], a[2])
 
     def post_filter(self, priority: int, bound=None, nominated_node: int = -1, nominated_status=None,
-                    terminating_lower=None, pdbs=None, hard_spread: bool = False, volumes: bool = False
-                    ) -> Tuple[Status, int, List[int], bool]:
+                    terminating_lower=None, pdbs=None, hard_spread: bool = False, volumes: bool = False,
+                    full: bool = False) -> Tuple[Status, int, List[int], bool]:
         """DefaultPreemption.PostFilter (default_preemption.go v1.26):
         PodEligibleToPreemptOthers, then the dry run over this cycle's
         nominated groups.  Returns (status, nominated node or -1, victim
@@ -241,7 +241,11 @@ class EnginePlugins:
         (KSIM_USE_VOLUME uses) are refused likewise unless ``volumes`` is set:
         the dry run then goes through ksim_preempt_volumes, which re-runs the
         node volume limit plugins on each node's moved attachment counts (the
-        table built with ``vol_limits=cluster.vol_limits``)."""
+        table built with ``vol_limits=cluster.vol_limits``).  ``full``: the
+        dry run goes through ksim_preempt_full, which takes every mix of
+        these kinds on one pod and re-runs VolumeBinding and VolumeZone for a
+        pod with volume groups (the table built with both ``full_adds=True``
+        and ``vol_limits=``)."""
         if nominated_node >= 0 and (nominated_status is None or
                                     nominated_status.code != UNSCHEDULABLE_AND_UNRESOLVABLE):
             if terminating_lower is not None and terminating_lower(nominated_node, priority):
@@ -252,6 +256,8 @@ class EnginePlugins:
         kw = {"hard_spread": True} if hard_spread else {}
         if volumes:
             kw["volumes"] = True
+        if full:
+            kw["full"] = True
         if bound is None:
             node, victims = self.b.preempt(self._pods, self._idx, priority, groups=self._groups, **kw)[:2]
         else:

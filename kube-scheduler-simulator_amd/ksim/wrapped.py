@@ -179,7 +179,7 @@ def record_cycle(store: Store, cluster: EncodedCluster, prof: SchedulerProfile, 
 
 def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: SchedulerProfile, pods, index: int,
                  priority: int = 0, bound=None, pdbs=None, hard_spread: bool = False,
-                 volumes: bool = False) -> Dict:
+                 volumes: bool = False, full: bool = False) -> Dict:
     """One deterministic compat cycle as the wrapped plugins see it: the cycle
     (ksim_eval_pod), then for an unschedulable pod DefaultPreemption's
     PostFilter dry run (ksim_preempt over the bound-pod table set with
@@ -196,7 +196,11 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
     A pod with counted volumes is refused likewise unless ``volumes`` is set:
     the dry run then goes through ksim_preempt_volumes
     (``Engine.preempt(..., volumes=True)``), which re-runs the node volume limit
-    plugins and needs the table built with ``vol_limits=cluster.vol_limits``."""
+    plugins and needs the table built with ``vol_limits=cluster.vol_limits``.
+    ``full``: the dry run goes through ksim_preempt_full
+    (``Engine.preempt(..., full=True)``), which takes every mix of these kinds
+    on one pod, re-runs VolumeBinding and VolumeZone for a pod with volume
+    groups, and needs the table built with both."""
     res = backend.eval_pod(pods, index) if hasattr(backend, "eval_pod") else backend.cycle(pods, index)
     nominated = -1
     post = [original_name(p.name) for p in prof.plugins["postFilter"].enabled]
@@ -208,6 +212,8 @@ def compat_cycle(backend, store: Store, cluster: EncodedCluster, prof: Scheduler
             kw = {"hard_spread": True} if hard_spread else {}
             if volumes:
                 kw["volumes"] = True
+            if full:
+                kw["full"] = True
             out = backend.preempt(pods, index, priority, **kw) if bound is None else \
                 backend.preempt(pods, index, priority, bound, **kw)
             nominated = int(out[0])

@@ -27,17 +27,24 @@ potential node (Fit fails first) and a candidate, and each runs the volume
 form of the dry run through ksim_preempt_volumes.  The table carries every
 row's holdings.
 
+--full: --volumes' cluster spread over 50 zones, and a preemptor (app=x) that
+also carries a required hostname anti-affinity term against app=x and one
+DoNotSchedule constraint (maxSkew 1 on the zone over app=x); no bound pod is an
+x pod.  Every node is a potential node (Fit fails first) and a candidate, and
+each runs the full form of the dry run through ksim_preempt_full.  The table
+carries every row's class contributions and holdings.
+
 --pdbs K: K PodDisruptionBudgets with disruptionsAllowed 1 over the table,
 the bound pods of node v in budget v % K (ksim_set_bound_pod_pdbs), so all but
 the most important lower-priority pod of a node violate: the call takes the
-PDB form of the kernels.  With --anti, --spread or --volumes too.
+PDB form of the kernels.  With --anti, --spread, --volumes or --full too.
 
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread | --volumes] [--pdbs K]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread | --volumes | --full] [--pdbs K]
 """
 import argparse
 import json
@@ -113,14 +120,19 @@ def build_anti(n_nodes: int, spread: bool = False):
     return cluster, table, enc, prof
 
 
-def build_volumes(n_nodes: int):
-    """build()'s load with counted volumes on every bound pod and the preemptor."""
+def build_volumes(n_nodes: int, full: bool = False):
+    """build()'s load with counted volumes on every bound pod and the preemptor
+    (``full``: on N_ZONES zones, the preemptor with hostname anti-affinity and a
+    DoNotSchedule zone constraint as well)."""
     from ksim.preemption import bound_table
     from ksim.volumes import VolumeIndex
     rng = np.random.default_rng(7)
     ebs, csi = "attachable-volumes-aws-ebs", "attachable-volumes-csi-x"
     nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}"},
                   allocatable={"cpu": "10", "memory": "64Gi", "pods": "110", ebs: "4", csi: "8"}) for i in range(n_nodes)]
+    if full:
+        for i, n in enumerate(nodes):
+            n.labels[ZONE] = f"z{i % N_ZONES:02d}"
     pvs, pvcs = [], []
 
     def claim(name, **source):
@@ -143,13 +155,21 @@ def build_volumes(n_nodes: int):
             start[bound[-1].name] = int(rng.integers(0, 1000))
     pod = Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})],
               pvc_claims=[claim("mine", source="awsElasticBlockStore", source_id="vol-mine"), "s0"])
+    if full:
+        sel = LabelSelector({"app": "x"})
+        pod.labels = {"app": "x"}
+        pod.pod_anti_affinity_required = [PodAffinityTerm("kubernetes.io/hostname", sel)]
+        pod.topology_spread = [TopologySpreadConstraint(1, ZONE, "DoNotSchedule", sel)]
     index = VolumeIndex.from_nodes(nodes, pvs, pvcs)
     cluster, _ = encode_cluster(nodes, bound)
     cluster.set_volume_limits(index.volume_limits(nodes, bound, [pod]))
     enc = encode_pods(cluster, [pod], volumes=index)
     kinds = [int(k) for k in enc.uses["kind"][:int(enc.pods[0]["use_count"])]]
-    assert kinds == [abi.USE_VOLUME, abi.USE_VOLUME] and sorted(int(c) >= 0 for c in enc.uses["cls"][:2]) == [False, True]
-    table = bound_table(cluster, bound, start, cluster.topo, vol_limits=cluster.vol_limits)
+    vol = [int(c) >= 0 for c, k in zip(enc.uses["cls"], kinds) if k == abi.USE_VOLUME]
+    assert sorted(vol) == [False, True]
+    assert {k for k in kinds if k != abi.USE_VOLUME} >= ({abi.USE_PTS_HARD, abi.USE_IPA_ANTI} if full else set())
+    assert full or len(kinds) == 2
+    table = bound_table(cluster, bound, start, cluster.topo, full_adds=full, vol_limits=cluster.vol_limits)
     assert int(table.vol_off[-1]) == len(bound) + 2 * ((len(bound) + 7) // 8)
     prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
     return cluster, table, enc, prof
@@ -174,13 +194,16 @@ def main():
     ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
     ap.add_argument("--spread", action="store_true", help="a preemptor with a DoNotSchedule zone spread constraint")
     ap.add_argument("--volumes", action="store_true", help="counted volumes on every bound pod and the preemptor")
+    ap.add_argument("--full", action="store_true", help="--volumes' load, and hostname anti-affinity and a zone spread "
+                                                        "constraint on the preemptor (ksim_preempt_full)")
     ap.add_argument("--pdbs", type=int, default=0, help="this many budgets (disruptionsAllowed 1), each bound pod in one")
     args = ap.parse_args()
-    if args.anti + args.spread + args.volumes > 1:
-        ap.error("--anti, --spread or --volumes, not two of them")
+    if args.anti + args.spread + args.volumes + args.full > 1:
+        ap.error("--anti, --spread, --volumes or --full, not two of them")
     cluster, table, enc, prof = build_anti(args.nodes, args.spread) if args.anti or args.spread else \
-        build_volumes(args.nodes) if args.volumes else build(args.nodes)
-    kw = dict(hard_spread=True) if args.spread else dict(volumes=True) if args.volumes else {}
+        build_volumes(args.nodes, args.full) if args.volumes or args.full else build(args.nodes)
+    kw = dict(hard_spread=True) if args.spread else dict(volumes=True) if args.volumes else \
+        dict(full=True) if args.full else {}
     budgets = None
     if args.pdbs > 0:
         budgets = (np.ones(args.pdbs, np.int32), np.arange(table.n + 1, dtype=np.int32),
@@ -204,7 +227,7 @@ def main():
         runs.append(summary(us))
         every += us
     name = ("preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else
-            "preempt_volumes" if args.volumes else "preempt_use_free") + ("_pdb" if budgets is not None else "")
+            "preempt_volumes" if args.volumes else "preempt_full" if args.full else "preempt_use_free") + ("_pdb" if budgets is not None else "")
     extra = dict(pdbs=args.pdbs, pdb_violations=result[4]) if budgets is not None else {}
     print(json.dumps(dict(bench=name, library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
                           bound_pods=table.n, calls=args.calls, repeats=args.repeats,
