@@ -953,7 +953,9 @@ __global__ __launch_bounds__(kBatchPods) void k_adapt_pairs(DevCluster c, DevPod
         // stops fitting; one that scans every node keeps its span, and for
         // kPodNormVaries pods (k_adapt_top's maxima) its scored list loses
         // the node: the maxima change once every holder has left
-        const bool normv = pnorm && (P.bflags[base + j] & kPodNormVaries) != 0;
+        // (a deferred-commit run holds no such pod: lazy_ok takes run_fast's
+        // runs only, and its launch passes no pnorm)
+        const bool normv = !LAZY && pnorm && (P.bflags[base + j] & kPodNormVaries) != 0;
         if (was && !now) {
           if (cut >= 0) {
             brk = true;

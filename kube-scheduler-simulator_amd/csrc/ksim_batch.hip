@@ -834,7 +834,8 @@ __global__ __launch_bounds__(256) void k_static_table(DevCluster c, DevPods P, c
   const ksim_pod& p = P.pods[rep[blockIdx.y]];
   const NodeRow r = load_row(c, node);
   const bool pass = static_filters_pass(c, P, *bp_p, p, r);
-  stab[(size_t)blockIdx.y * c.n + node] = stab_word(pass, count_intolerable_prefer(c, p, r), pref_term_mask(c, P, p, node));
+  stab[(size_t)blockIdx.y * c.n + node] = stab_word(pass, count_intolerable_prefer(c, p, r), pref_term_mask(c, P, p, node),
+                                                        image_raw(c, P, p, node));
 }
 
 void launch_static_table(const LaunchArgs& a, const int32_t* rep, int32_t n_cls, uint64_t* stab, hipStream_t stream) {

@@ -121,8 +121,9 @@ struct DevPods {
   int32_t n_pods, n_exprs, n_terms, n_uses, n_adds, n_nn, n_ptab, _pad;
   // Static classes (P100 batch keys of non-trivial and kPodNormVaries pods):
   // pods whose static-filter and normalized-score inputs are identical share a
-  // class; stab[cls][node] holds the class's static verdict on the node and
-  // its two raw normalized scores (stab_word).  Null: no table (the keys
+  // class; stab[cls][node] holds the class's static verdict on the node, its
+  // two raw normalized scores and its ImageLocality score (stab_word; an
+  // image pod's class includes its image class).  Null: no table (the keys
   // evaluate every static plugin per node).  stab_fast: the handle meets
   // run_fast's cluster conditions, so the keys take the FAST arithmetic.
   const int32_t* sclass = nullptr;   // [n_pods] class or -1
@@ -130,14 +131,24 @@ struct DevPods {
   int32_t stab_fast = 0, _pad2 = 0;
 };
 
-// A static-table word: bit 63 every static filter passes; bits 32..62
-// countIntolerableTaintsPreferNoSchedule; bit k < 32: the pod's preferred
-// node-affinity term k (weight != 0) matches the node.  The weights stay
+// A static-table word: bit 63 every static filter passes; bits 56..62 the
+// class's ImageLocality score (kStabIlBits = 7: the image class's count
+// column holds the finished score, 0..kMaxNodeScore = 100 < 2^7); bits 32..55
+// countIntolerableTaintsPreferNoSchedule (kStabTtBits = 24: a node carries at
+// most KSIM_MAX_NODE_TAINTS = 8 taints, so the count is at most 8 < 2^24); bit
+// k < 32: the pod's preferred node-affinity term k (weight != 0) matches the
+// node.  1 + 7 + 24 + 32 = 64: the fields do not overlap, and each value is
+// masked to its width, so none can spill into its neighbour.  The weights stay
 // with the pod (a class is the terms' expressions, so pods that differ only
 // in weights share it); stab_raw sums them.  The host admits a class only
 // with at most 32 preferred terms, all weights >= 0.
-__host__ __device__ __forceinline__ uint64_t stab_word(bool pass, int64_t tt, uint32_t match) {
-  return (pass ? (1ull << 63) : 0ull) | ((uint64_t)(tt & 0x7fffffff) << 32) | (uint64_t)match;
+constexpr int kStabIlShift = 56, kStabIlBits = 7, kStabTtShift = 32, kStabTtBits = 24;
+static_assert(kMaxNodeScore < (1 << kStabIlBits) && KSIM_MAX_NODE_TAINTS < (1 << kStabTtBits) &&
+                  kStabTtShift + kStabTtBits == kStabIlShift && kStabIlShift + kStabIlBits == 63,
+              "static-table word fields");
+__host__ __device__ __forceinline__ uint64_t stab_word(bool pass, int64_t tt, uint32_t match, int64_t il) {
+  return (pass ? (1ull << 63) : 0ull) | ((uint64_t)(il & ((1 << kStabIlBits) - 1)) << kStabIlShift) |
+         ((uint64_t)(tt & ((1 << kStabTtBits) - 1)) << kStabTtShift) | (uint64_t)match;
 }
 __host__ __device__ __forceinline__ bool stab_pass(uint64_t w) { return (w >> 63) != 0; }
 
@@ -1649,6 +1660,8 @@ struct BatchProg {
   // per-pod cycle (plan_profile): filter position / score slot per plugin id
   uint64_t rank_lo, rank_hi, slot;
   uint32_t slot_hi, _pad2;
+  // last, so the fields the FAST keys read keep their offsets
+  int64_t w_il;                            // summed weights of the ImageLocality slots (norm_part; 0: not scored)
 };
 
 // The FAST key with the default profile's shape compiled in (dyn_key_fast_t<true>):
@@ -1663,7 +1676,7 @@ __host__ __device__ inline bool fast_def(const BatchProg& bp) {
 // DevPods.bflags (batch path, per pod)
 constexpr int32_t kBatchStaticTrivial = 1; // every static filter passes on every node (host-proven)
 constexpr int32_t kPodRegistersValues = 2; // has a ScheduleAnyway spread keyed by a non-hostname column
-constexpr int32_t kPodNormVaries = 4;      // batch path: TaintToleration / NodeAffinity vary over nodes (norm_part)
+constexpr int32_t kPodNormVaries = 4;      // batch path: TaintToleration / NodeAffinity / ImageLocality vary over nodes (norm_part)
 constexpr int32_t kPodTopoBatch = 8;       // topology batch path (ksim_tbatch.hip)
 constexpr int32_t kPodTbCross = 16;       // topology batch run from this pod crosses a class conflict (node-local)
 constexpr int kTlenShift = 8;              // (bflags >> kTlenShift) & kTlenMask: topology batch run length from this pod
@@ -2028,20 +2041,25 @@ __device__ __forceinline__ uint64_t dyn_key(const ksim_profile& prof, const Batc
   return tb_key(tot, prof.tiebreak_seed, seq, base + r.node);
 }
 
-// kPodNormVaries pods (P100 batch path): the raw scores of the two normalized
-// plugins that can vary over nodes for a batchable pod.  Both depend on the
-// node's taints and labels only, never on what is bound there.
+// kPodNormVaries pods (batch paths): the raw scores of the static plugins
+// that can vary over nodes for a batchable pod: the two normalized ones, and
+// ImageLocality, whose raw score is the finished one (no NormalizeScore).
+// They depend on the node's taints, labels and images only, never on what is
+// bound there (an image class has no adds).
 struct NormRaw {
   int64_t tt, na;   // countIntolerableTaintsPreferNoSchedule, preferred NodeAffinity weight sum
+  int64_t il;       // ImageLocality score, 0..kMaxNodeScore (0 for a pod without an image use)
 };
-// The raw normalized scores of pod p from a static-table word of its class
-// (DevPods::stab): the taint count, and the weights of the matching terms
-// (preferred_node_affinity_score; the term count and weights are uniform).
+// The raw static scores of pod p from a static-table word of its class
+// (DevPods::stab): the taint count, the image score, and the weights of the
+// matching terms (preferred_node_affinity_score; the term count and weights
+// are uniform).
 __device__ __forceinline__ NormRaw stab_raw(uint64_t w, const DevPods& P, const ksim_pod& p) {
   int64_t na = 0;
   for (int k = 0; k < p.pref_term_count; k++)
     na += ((w >> k) & 1ull) ? (int64_t)P.terms[p.pref_term_first + k].weight : 0;
-  return NormRaw{(int64_t)((w >> 32) & 0x7fffffffull), na};
+  return NormRaw{(int64_t)((w >> kStabTtShift) & ((1ull << kStabTtBits) - 1)), na,
+                 (int64_t)((w >> kStabIlShift) & ((1ull << kStabIlBits) - 1))};
 }
 // The static-table word's match bits of pod p's preferred terms on a node.
 __device__ __forceinline__ uint32_t pref_term_mask(const DevCluster& c, const DevPods& P, const ksim_pod& p,
@@ -2053,17 +2071,30 @@ __device__ __forceinline__ uint32_t pref_term_mask(const DevCluster& c, const De
   }
   return m;
 }
+// A batch pod's ImageLocality score on a node: the count column of its one
+// use's image class (a batch pod carries no use, or exactly one KSIM_USE_IMAGE
+// use: pod_batchable).  The column is static: no pod adds to an image class.
+__device__ __forceinline__ int64_t image_raw(const DevCluster& c, const DevPods& P, const ksim_pod& p, int32_t node) {
+  if (p.use_count != 1) return 0;
+  const ksim_topo_use u = P.uses[p.use_first];
+  return u.kind == KSIM_USE_IMAGE && u.cls >= 0 ? (int64_t)c.cnt[(size_t)u.cls * c.n + node] : 0;
+}
 __device__ __forceinline__ NormRaw norm_raw(const DevCluster& c, const DevPods& P, const ksim_pod& p,
                                             const NodeRow& r) {
-  return NormRaw{count_intolerable_prefer(c, p, r), p.pref_term_count ? preferred_node_affinity_score(c, P, p, r.node) : 0};
+  return NormRaw{count_intolerable_prefer(c, p, r), p.pref_term_count ? preferred_node_affinity_score(c, P, p, r.node) : 0,
+                 image_raw(c, P, p, r.node)};
 }
-// Their weighted NormalizeScore over the pod's S0 maxima (mx): added to the
-// batch key's total.  Exact while the maxima hold: a node's raw scores never
-// change with binds, and the maxima only change when a node holding one
-// leaves the pod's feasible set (pairs_block flags that pod, pinv).
+// Their weighted scores, the two normalized ones by NormalizeScore over the
+// pod's S0 maxima (mx): added to the batch key's total.  Exact while the
+// maxima hold: a node's raw scores never change with binds, and the maxima
+// only change when a node holding one leaves the pod's feasible set
+// (pairs_block flags that pod, pinv).  With no intolerable taint on any
+// feasible node (mx.tt = 0) TaintToleration scores kMaxNodeScore everywhere:
+// a constant, left out of the key like the other constant parts, so a pod
+// flagged for its image alone stays within 100 * (w_fit + w_ba + w_il).
 __device__ __forceinline__ int64_t norm_part(const BatchProg& bp, const NormRaw& v, const NormRaw& mx) {
-  return bp.w_tt * normalize_value(kNormDefaultReverse, v.tt, mx.tt, 0, false) +
-         bp.w_na * normalize_value(kNormDefault, v.na, mx.na, 0, false);
+  return (mx.tt > 0 ? bp.w_tt * normalize_value(kNormDefaultReverse, v.tt, mx.tt, 0, false) : 0) +
+         bp.w_na * normalize_value(kNormDefault, v.na, mx.na, 0, false) + bp.w_il * v.il;
 }
 
 // norm_part of a static-table word for the FAST keys of a static class
@@ -2077,9 +2108,9 @@ __device__ __forceinline__ int64_t norm_part_fast(const BatchProg& bp, const Nor
                                                   double y_tt, double y_na) {
   const int64_t qt = (int64_t)div_rn((double)(kMaxNodeScore * v.tt), (double)mx.tt, y_tt);
   const int64_t qa = (int64_t)div_rn((double)(kMaxNodeScore * v.na), (double)mx.na, y_na);
-  const int64_t nt = mx.tt > 0 ? (int64_t)kMaxNodeScore - qt : (int64_t)kMaxNodeScore;
+  const int64_t nt = mx.tt > 0 ? (int64_t)kMaxNodeScore - qt : 0;   // mx.tt = 0: a constant (norm_part)
   const int64_t na = mx.na > 0 ? qa : v.na;
-  return bp.w_tt * nt + bp.w_na * na;
+  return bp.w_tt * nt + bp.w_na * na + bp.w_il * v.il;
 }
 __device__ __forceinline__ double recip_or_zero(int64_t m) { return m > 0 ? 1.0 / (double)m : 0.0; }
 

@@ -559,8 +559,11 @@ int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i) {
 //   NodeAffinity:    no preferred terms -> raw 0 -> 0
 //   PodTopologySpread: no constraints -> 100
 //   InterPodAffinity:  no uses -> topologyScore empty -> 0
+//   ImageLocality:     no image use -> 0
 // A pod with topology uses reads the count classes, which binds of earlier
-// pods of a batch change, so it always takes the per-pod path.
+// pods of a batch change, so it takes the per-pod path (or the topology
+// batches).  An image class is static, so a pod whose only use is its image
+// stays here with the score in its keys (pod_batchable).
 // Every static filter of the batch path passes on every node for this pod:
 // no spec.nodeName, no nodeSelector / required node affinity, every
 // NoSchedule/NoExecute taint in the cluster tolerated, no unschedulable node
@@ -591,7 +594,7 @@ constexpr size_t kStabMaxEntries = (size_t)1 << 26;   // 512 MB of table
 
 // The static inputs of a batch pod's keys, as bytes: what static_filters_pass
 // (NodeUnschedulable, NodeName, TaintToleration, NodeAffinity) and norm_raw
-// read of the pod, the selector and affinity expressions expanded, the
+// read of the pod (its image class among them), the selector and affinity expressions expanded, the
 // preferred terms without their weights (two pods with equal signatures have
 // equal verdicts, taint counts and preferred-term matches on every node;
 // stab_word).  False past 32 preferred terms or for a negative weight.
@@ -619,6 +622,10 @@ bool stab_signature(const ksim_pod_set* ps, const ksim_pod& q, std::string& s) {
     put(&q.added_term_count, sizeof q.added_term_count);
     for (int32_t k = 0; k < q.added_term_count; k++) put_term(q.added_term_first + k, false);
   }
+  // the image class of an image pod's one use (-1: none): the word's image
+  // field is that class's count column, so image sets never share a class
+  const int32_t ic = q.use_count == 1 && ps->uses[q.use_first].kind == KSIM_USE_IMAGE ? ps->uses[q.use_first].cls : -1;
+  put(&ic, sizeof ic);
   put(&q.node_name, sizeof q.node_name);
   put(q.tol_filter, sizeof q.tol_filter);
   put(q.tol_prefer, sizeof q.tol_prefer);
@@ -709,19 +716,30 @@ bool profile_nb(const ksim_profile& p) {
 }
 
 // The batch keys carry a pod's total minus its constant normalized part in
-// 20 bits (tb_key): 100 * (w_fit + w_ba), plus w_tt + w_na for the pods
-// whose normalized scores vary, must stay below kKeyTotalLimit, or the pods
+// 20 bits (tb_key): 100 * (w_fit + w_ba), plus w_il for a pod with an image
+// use and w_tt + w_na for the pods whose normalized scores vary, must stay
+// below kKeyTotalLimit, or the pods
 // take the per-pod path, whose (total, TB) pairs are exact for any int64 total.  Pods that NodeAffinity's PreFilterResult
 // restricts scan a node list of their own: per-pod path.
+// A pod's topology uses read count classes that binds of earlier pods of a
+// batch change: per-pod path (or the topology batches, tbatch_admit).  The
+// exception is a pod whose uses are exactly one KSIM_USE_IMAGE: its
+// ImageLocality score is the image class's count column, which no bind
+// changes (image classes have no adds) and which needs no NormalizeScore, so
+// the keys carry w_il * score as a third static part beside the two
+// normalized ones (norm_part; the static-table word holds it, stab_word).
 // Returns 0 (per-pod path), 1 (every batch path) or 2 (the unsharded P100
-// batch path only): pods whose TaintToleration / NodeAffinity scores vary
+// batch path, and the unsharded ADAPT one without scalar requests:
+// pod_on_batch): pods whose TaintToleration / NodeAffinity scores vary
 // over nodes (kPodNormVaries: the keys carry them, normalized over the pod's
-// S0 maxima) and pods with scalar requests (the ADAPT repair's compact rows
-// carry no scalars).
-int pod_batchable(const ksim_handle* h, const ksim_pod& p, bool* norm_varies = nullptr) {
+// S0 maxima), pods with an image use (kPodNormVaries too: the same key sites
+// add the image part, and maxima of 0 / 0 never cut such a pod) and pods with
+// scalar requests (the ADAPT repair's compact rows carry no scalars).
+int pod_batchable(const ksim_handle* h, const ksim_pod& p, const ksim_topo_use* uses, bool* norm_varies = nullptr) {
   const ksim_profile& prof = h->prof;
   if (norm_varies) *norm_varies = false;
-  if (p.use_count > 0) return 0;
+  const bool image = p.use_count == 1 && uses && uses[p.use_first].kind == KSIM_USE_IMAGE;
+  if (p.use_count > 0 && !image) return 0;
   if (p.flags & KSIM_POD_NODE_NAMES) return 0;
   if (p.vb_count > 0 || p.vz_count > 0) return 0;       // volume groups: the per-pod filter chain
   // NetworkBandwidth runs on the per-pod path (its error statuses end cycles),
@@ -745,7 +763,9 @@ int pod_batchable(const ksim_handle* h, const ksim_pod& p, bool* norm_varies = n
         break;
     }
   }
-  if (varies && (int64_t)kMaxNodeScore * (w_dyn + h->bp.w_tt + h->bp.w_na) >= kKeyTotalLimit) return 0;
+  const int64_t w_img = image ? h->bp.w_il : 0;
+  if ((int64_t)kMaxNodeScore * (w_dyn + w_img + (varies ? h->bp.w_tt + h->bp.w_na : 0)) >= kKeyTotalLimit) return 0;
+  varies = varies || image;
   if (varies) cls = 2;
   if (norm_varies) *norm_varies = varies;
   return cls;
@@ -1748,9 +1768,12 @@ int for_each_run(ksim_handle* h, int32_t first, int32_t count, F&& fn, bool adap
   while (i < end) {
     const bool batch_ok = !(adapt_mode(h) && is_sharded(h)) || adapt_sharded;
     const bool b = batch_ok && pod_on_batch(h, i);
-    const bool t = h->topo[i] != 0;
+    // a class-2 pod on the batch path with a use is an image pod (pod_batchable):
+    // its one use is a static score part of its keys, not a topology input
+    auto topo_of = [&](int32_t x) { return b && h->batchable[x] == 2 ? (uint8_t)0 : h->topo[x]; };
+    const bool t = topo_of(i) != 0;
     int32_t j = i + 1;
-    while (j < end && (batch_ok && pod_on_batch(h, j)) == b && h->topo[j] == h->topo[i]) j++;
+    while (j < end && (batch_ok && pod_on_batch(h, j)) == b && topo_of(j) == topo_of(i)) j++;
     int rc = fn(i, j, b, t);
     if (rc) return rc;
     i = j;
@@ -2542,6 +2565,7 @@ static BatchProg compile_batch_prog(const ksim_profile* p) {
     if (p->score[k] == KSIM_PL_BALANCED_ALLOCATION) bp.w_ba += w;
     if (p->score[k] == KSIM_PL_TAINT_TOLERATION) bp.w_tt += w;
     if (p->score[k] == KSIM_PL_NODE_AFFINITY) bp.w_na += w;
+    if (p->score[k] == KSIM_PL_IMAGE_LOCALITY) bp.w_il += w;
   }
   plan_profile(*p, bp.rank_lo, bp.rank_hi, bp.slot, bp.slot_hi);
   return bp;
@@ -4512,9 +4536,19 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
   h->hard_small.assign((size_t)ps->n_pods, 1);
   h->soft_le1.assign((size_t)ps->n_pods, 1);
   h->xreg_len.assign((size_t)ps->n_pods, 0);
+  // classes some pod of the queue adds to: an image use of one would not be
+  // static (the encoders never emit that; a hand-built queue may)
+  std::vector<uint8_t> added((size_t)std::max(h->dc.n_classes, 1), 0);
+  for (int32_t k = 0; k < ps->n_adds; k++)
+    if (ps->adds[k].cls >= 0 && ps->adds[k].cls < h->dc.n_classes) added[(size_t)ps->adds[k].cls] = 1;
   for (int32_t i = 0; i < ps->n_pods; i++) {
     bool nv = false;
-    batchable[i] = (uint8_t)pod_batchable(h, ps->pods[i], &nv);
+    batchable[i] = (uint8_t)pod_batchable(h, ps->pods[i], ps->uses, &nv);
+    if (batchable[i] && ps->pods[i].use_count == 1 && ps->uses[ps->pods[i].use_first].cls >= 0 &&
+        added[(size_t)ps->uses[ps->pods[i].use_first].cls]) {
+      batchable[i] = 0;
+      nv = false;
+    }
     if (nv) bf[i] |= kPodNormVaries;
     h->topo[i] = ps->pods[i].use_count > 0 ? (R.pod[i] ? 2 : 1) : 0;
     // sharded-cycle exchange sizes, laid out as k_dom_pack / k_window_sh do
