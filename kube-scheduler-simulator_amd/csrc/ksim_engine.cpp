@@ -24,9 +24,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "ksim_internal.h"
+#include "ksim_host.h"
 
-using namespace ksim;
+using namespace ksim_host;
 
 namespace {
 
@@ -66,313 +66,9 @@ const Rccl& rccl() {
 }
 constexpr int kGraphBatches = 16;      // speculative batches per captured graph
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-// A device buffer reused across calls, grown (never shrunk) on demand: the
-// per-call uploads of the framework-driven calls (one pod, its terms and uses)
-// without a hipMalloc / hipFree pair per call.
-struct DevArena {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 }  // namespace
 
-// One pod (re-based) as a device pod set of its own, packed the way it is
-// uploaded: every piece at a 64-byte aligned offset of one blob.
-struct PodBlob {
-  std::vector<char> bytes;
-  size_t off[8];
-  int32_t n_nn, n_exprs, n_terms, n_uses, n_adds;
-};
-
-struct ksim_handle {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::string err;
-
-  bool has_profile = false;
-  ksim_profile prof{};
-  BatchProg bp{};
-  // device copies of prof / bp, read by the batch-path kernels: a captured
-  // batch graph then survives a weight change (ksim_set_profile)
-  ksim_profile* d_prof = nullptr;
-  BatchProg* d_bp = nullptr;
-  std::vector<size_t> pod_buf_bytes;    // sizes of pod_bufs (ksim_load_pods reuses same-sized buffers)
-
-  bool has_cluster = false;
-  DevCluster dc{};
-  std::vector<DevBuf> cluster_bufs;
-  std::vector<uint8_t> taint_effect;    // host copy (batchability analysis)
-  std::vector<uint16_t> hard_taints;    // taint ids with effect NoSchedule/NoExecute on some node
-  bool any_unschedulable = false;       // some node has spec.unschedulable
-  bool alloc_narrow = false;            // every allocatable cpu / memory in [0, 2^46) (dyn_key_fast)
-
-  // device copy of the uploaded dynamic columns (ksim_reset_cluster)
-  struct {
-    int64_t *req_cpu, *req_mem, *req_eph, *req_scalar, *nz_cpu, *nz_mem;
-    int32_t *num_pods, *cnt;
-    int64_t* nb_alloc;
-  } init{};
-  // node volume limits (ksim_set_volume_limits): limit, attached and the copy
-  // of attached that ksim_reset_cluster restores
-  std::vector<DevBuf> vol_bufs;
-  int32_t* vol_init = nullptr;
-  std::vector<int32_t> col_nvals;       // host copy (pod validation)
-  std::vector<uint8_t> col_unique;      // host copy of DevCluster.col_unique (kUseUniqueCol on upload)
-  std::vector<uint8_t> col_total;       // per label column: every node carries the key
-
-  DevScratch sc{};
-  DevEvalOut eo{};
-  std::vector<DevBuf> scratch_bufs;
-
-  DevState* st = nullptr;
-  int32_t run_hdr[2] = {0, 0};
-
-  // loaded pod queue (batch mode)
-  DevPods dp{};
-  int32_t* d_chosen = nullptr;
-  std::vector<DevBuf> pod_bufs;
-  std::vector<uint8_t> batchable;       // per loaded pod
-  std::vector<uint8_t> topo;            // per loaded pod: 0 no topology uses, 1 uses (k_topo_prefilter), 2 uses
-                                        // read from persistent tables (kPlanPtab)
-  std::vector<uint8_t> trivial;         // per loaded pod: kBatchStaticTrivial
-  std::vector<uint8_t> noadd;           // per loaded pod: no count-class adds (deferred-commit batches)
-  std::vector<uint8_t> noscalar;        // ... and no scalar requests (generic deferred-commit batches)
-  // static classes (DevPods::stab, ensure_stab): per loaded pod its class or
-  // -1 (d_sclass), each class's representative pod (d_srep); the table is
-  // rebuilt after any change of pods, cluster or profile (stab_dirty)
-  int32_t* d_sclass = nullptr;
-  int32_t* d_srep = nullptr;
-  int32_t stab_ncls = 0;
-  bool stab_dirty = true, stab_ready = false;
-  std::vector<DevBuf> stab_bufs;
-  size_t stab_bytes = 0;
-  std::vector<int32_t> sclass;          // host copy of d_sclass
-  std::vector<uint8_t> hard_small;      // per loaded pod: every hard spread key column has <= kFuseMinValues values
-  std::vector<uint8_t> soft_le1;        // per loaded pod: at most one ScheduleAnyway spread constraint
-  std::vector<int32_t> tlen;            // per loaded pod: topology batch run length from it (tbatch_runs)
-  std::vector<int32_t> tlen_plain;      // ... without zone variants (replicated topology batches)
-  std::vector<int64_t> xdom_len;        // per loaded pod: sharded cycle, packed domain words
-  std::vector<int64_t> xreg_len;        // per loaded pod: sharded cycle, registration words (0: no soft spread)
-
-  // compat-mode single pod
-  DevArena pod1_arena;                  // the single-pod uploads (upload_single)
-  DevArena nom_arena;                   // a nominated pod (ksim_fw_filter_nominated)
-  // Reserve / Unreserve calls that arrive while a framework cycle sits between
-  // its PreFilter and Score (the binding goroutine's Unreserve):
-  // upstream's running cycle keeps its snapshot, so the engine applies them
-  // once that cycle has scored (flush_deferred_binds), in call order
-  struct DeferredBind {
-    ksim_pod pod;
-    std::vector<ksim_label_expr> ex;
-    std::vector<ksim_term> tm;
-    std::vector<ksim_topo_use> us;
-    std::vector<ksim_class_add> ad;
-    std::vector<int32_t> nn;
-    int32_t node;
-    int sign;
-  };
-  std::vector<DeferredBind> deferred_binds;
-  // pinned, coherent host staging for the per-call uploads / results, and the
-  // device's addresses of it (copy kernels read / write it directly)
-  void* pin = nullptr;
-  void* pin_d = nullptr;
-  size_t pin_cap = 0;
-  // the last pod upload's copy out of the staging (upload_blob waits on it
-  // instead of the whole stream); the pod last uploaded into pod1_arena (its
-  // bytes and device address: a Reserve / Unreserve of the same pod binds
-  // from there, no upload)
-  // upload_blob's pinned staging ring: consecutive pod uploads (an informer's
-  // pod deltas, another pod's Reserve, the next cycle's pod) do not wait for
-  // each other's copies; a slot is reused once its copy has run (its event)
-  struct PinSlot {
-    void* p = nullptr;
-    void* d = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-  };
-  static constexpr int kPinRing = 4;
-  PinSlot ring[kPinRing];
-  int ring_next = 0;
-  std::vector<char> pod1_blob;
-  char* pod1_base = nullptr;
-  // build_pod_blob's pieces and the framework-driven pass's blob, kept so the
-  // per-cycle calls reuse their capacity
-  std::vector<ksim_label_expr> bs_ex;
-  std::vector<ksim_term> bs_tm;
-  std::vector<ksim_topo_use> bs_us;
-  std::vector<ksim_class_add> bs_ad;
-  std::vector<int32_t> bs_nn;
-  PodBlob fw_blob;
-  // the framework-driven filter passes alternate two arenas, so the Reserve of
-  // cycle i (binding from cycle i's arena) can wait, queued, and run inside
-  // cycle i+1's upload launch (pend_bind); any other call launches it first
-  DevArena fw_arena[2];
-  int fw_flip = 0;
-  struct PendBind {
-    bool on = false;
-    DevPods P{};
-    int32_t node = 0;
-    int sign = 0;
-  } pend_bind;
-  int64_t pend_reuse = 0;                      // upload_blob found the queued Reserve's arena reused (flushed)
-  void* pout = nullptr;
-  void* pout_d = nullptr;
-  size_t pout_cap = 0;
-  // DefaultPreemption: bound pods per node in importance order
-  std::vector<DevBuf> pre_bufs;
-  std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
-  int64_t* pre_smin = nullptr;          // ksim_preempt_spread's per-use minima (in pre_bufs; k_preempt_spread_mins)
-  std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
-  std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
-  std::vector<DevBuf> pre_vol_bufs;     // ksim_set_bound_pod_volumes (likewise, and by ksim_set_volume_limits)
-  const int32_t* pre_voff = nullptr;    // [pre_n + 1] CSR order: the rows' volume holdings (null: none set)
-  const VolHold* pre_vols = nullptr;
-  DevPreempt pre{};
-  std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
-  int32_t pre_n = 0;
-  // extender round trip (ksim_eval_pod_filter -> ksim_eval_pod_finish)
-  DevPods pod1{};
-  bool ext_pending = false;
-  uint8_t* ext_fail = nullptr;     // device [n]
-  int64_t* ext_score = nullptr;    // device [n]
-  // framework-driven compat cycle (ksim_fw_prefilter -> ksim_fw_score ->
-  // ksim_fw_normalize): the pod in h->pod1, its filter pass on the host for
-  // list validation, the scan-set size
-  bool fw_pending = false, fw_scored = false, fw_dom_dirty = false, fw_topo = false;
-  int32_t fw_ns = 0;
-  std::vector<uint8_t> fw_fail;
-  // ksim_fw_score's list and answers, host side: a NormalizeScore over that
-  // list with the raw scores it returned is answered from here
-  std::vector<int32_t> fw_list;
-  std::vector<int64_t> fw_raw, fw_norm;         // [slot][list position]
-  // host-answered Score (fw_host): ksim_fw_prefilter also copies every node's
-  // raw scores, the weighted sum of the plugins without NormalizeScore and the
-  // topology flags into pinned memory, and ksim_fw_score normalizes over the
-  // framework's list on the host (no second device round trip) when no
-  // PreScore of the pod depends on that list
-  bool fw_host = false;
-  int64_t fw_counts[4] = {0, 0, 0, 0};   // Score on the host / device, NormalizeScore cached / device
-  std::vector<uint8_t> fw_seen;    // list validation (all zero between calls)
-  std::vector<int64_t> fw_tot;
-  void* fwh = nullptr;             // pinned: [S][n] raw, [n] part
-  void* fwh_d = nullptr;
-  size_t fwh_cap = 0;
-  uint32_t fw_tflags = 0;
-  size_t fw_oraw = 0, fw_opart = 0;  // fwh offsets of the raw scores and the weighted part
-  bool fw_raw32 = false;             // ... as int32 (the filter kernel's own copy) or int64 (a copy launch)
-  int32_t* fw_nodes = nullptr;     // device [n]
-  int64_t* fw_vals = nullptr;      // device [n]
-  int64_t* fw_out = nullptr;       // device [n]
-
-  // node sharding: this handle holds [shard_base, shard_base + n) of shard_total
-  int32_t shard_base = 0, shard_total = 0;
-  // replicated handle (ksim_set_eval_range): holds every node, evaluates
-  // [eval_lo, eval_hi) in the P100 batch top-T and keeps its replica by
-  // binding every placement: one exchange per batch (the records' all-gather)
-  bool replicated = false;
-  int32_t eval_lo = 0, eval_hi = 0;
-  bool rep_primary = true;              // replicated: this replica counts the whole-run evaluations
-  int32_t rank = 0, world = 1;
-  ncclComm_t comm = nullptr;
-
-  // per-pod cycles, by variant: topology kernels (1) | critical paths in the
-  // filter pass (2) | NormalizeScore extrema in the filter pass (4)
-  hipGraphExec_t graph_cycle[16] = {};   // | persistent tables (8)
-  hipGraphExec_t graph_batch = nullptr;
-  hipGraphExec_t graph_batch_fast = nullptr;   // k_batch_top<true> runs
-  hipGraphExec_t graph_batch_stab = nullptr;   // static-class runs (LaunchArgs::stab)
-  hipGraphExec_t graph_tbatch = nullptr;       // topology batches (ksim_tbatch.hip)
-  // deferred-commit FAST batches (ksim_internal.h): the second snapshot buffer
-  // X[1] and state st[1], the ring of chain + pairs outputs, kGraphBatches
-  // batches as one graph (starting at a batch index divisible by kLazySlots)
-  std::vector<DevBuf> lazy_bufs;
-  int32_t lazy_n = -1;
-  DynCols lazy_x1{};
-  DevState* lazy_st1 = nullptr;
-  uint64_t *lazy_g = nullptr, *lazy_m = nullptr;   // [kLazySlots][kBatchPods]
-  int32_t* lazy_e = nullptr;                        // [kLazySlots] prefix length, -1 = empty slot
-  int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
-  hipGraphExec_t graph_lazy = nullptr;
-  hipGraphExec_t graph_lazy_adapt = nullptr;
-  // the tail graphs: kLazySlots batches of the same flavour, captured with and
-  // dropped with the kGraphBatches graph beside them (run_lazy's top-ups of
-  // fewer than kGraphBatches batches)
-  hipGraphExec_t graph_lazy4 = nullptr, graph_lazy4_adapt = nullptr, graph_lazy4_rt = nullptr;
-  // run_lazy's progress words (host-mapped pinned, alloc_lazy): [0] the last
-  // state writer's lazy_progress, [1] the batch counter the run started from
-  unsigned long long* prog = nullptr;
-  unsigned long long* prog_d = nullptr;
-  // ksim_schedule_loaded leaves the zeroing of the call's counters to its first
-  // run (run_range: run_lazy's begin launch takes it, every other run calls
-  // reset_counters first)
-  bool counters_pending = false;
-  // deferred-commit runs since ksim_create (ksim_get_diag out[28..32]): host
-  // synchronisations inside them, batches enqueued past the end of their run,
-  // stretches ended by a flush and a state read instead of the progress word,
-  // top-ups (batches enqueued after a run's first stretch, by the word or a
-  // read), runs whose last flush had an odd ring index (the end launch copied
-  // X[1] and st[1] back)
-  int64_t feed_syncs = 0, feed_past_end = 0, feed_fallbacks = 0, feed_topups = 0, feed_odd_ends = 0;
-  // request classes of the loaded queue (ksim_internal.h ReqTab): per loaded
-  // pod its class (0xffff: none), the classes' requests, and the table's two
-  // halves [2][rq_ncls][dc.n] with the ring's patch entries
-  // [kLazySlots][rq_ncls][kBatchPods] behind them (ensure_rtab; a reallocation
-  // drops graph_lazy_rt, the deferred-commit graph of the runs that take the table)
-  std::vector<uint16_t> rq_cls;
-  uint16_t* d_rcls = nullptr;
-  PodReq* d_rreq = nullptr;
-  int32_t rq_ncls = 0;                             // > kReqMaxClasses: too many, no table
-  std::vector<DevBuf> rtab_bufs;
-  size_t rtab_bytes = 0;
-  hipGraphExec_t graph_lazy_rt = nullptr;
-  int64_t rtab_runs = 0;                           // runs that took the table (ksim_get_diag out[27])
-  int32_t rt_graph_ncls = 0;                       // the class count graph_lazy_rt was captured with
-  // node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and
-  // the global bitmap (allocated at the first such run)
-  std::vector<DevBuf> ash_bufs;
-  uint64_t *ash_send = nullptr, *ash_recv = nullptr, *ash_gmask = nullptr;
-  int32_t ash_world = 0, ash_w = 0;
-  // packed policy sweep (ksim_sweep_loaded, run_sweep): the lanes' buffers as
-  // one slab sized by (dc.n, lanes), the lane table [kLazySlots][kSweepMaxLanes]
-  // (its address is all a sweep graph holds of them), the vectors' profile
-  // copies, the lanes' placement rows, one graph per (lanes, fast_def)
-  struct SweepLaneBufs {
-    DynCols x[2];
-    uint64_t *g, *m;                             // [kLazySlots][kBatchPods]
-    int32_t* e;                                  // [kLazySlots]
-    uint64_t* topk;
-    int32_t *topk_cnt, *topk_complete, *pinv;
-    int64_t* pnorm;
-  };
-  void* sweep_slab = nullptr;
-  int32_t sweep_n = -1, sweep_lanes = 0;
-  std::vector<SweepLaneBufs> sweep_lane;
-  DevState* sweep_st = nullptr;                  // [sweep_lanes][2]
-  SweepLane* sweep_tab = nullptr;
-  DevArena sweep_profs, sweep_rows;
-  std::map<std::pair<int32_t, bool>, hipGraphExec_t> sweep_graphs;
-  // deferred-commit batches end at their first pair cut (KSIM_ONE_CUT=1 at the
-  // last run's start): the setting the handle's deferred-commit graphs hold
-  bool one_cut = false;
-  int64_t graph_captures = 0;                  // graphs captured since ksim_create (ksim_get_diag)
-  // node-sharded per-pod cycles (group leader): graphs of kGraphCycles cycles
-  // per shape (topology, exchange lengths), valid while every handle of the
-  // group keeps the graph generation it had at capture
-  int64_t graph_gen = 0;                       // bumped whenever this handle's cycle graphs are dropped
-  std::vector<std::pair<const ksim_handle*, int64_t>> sg_sig;
-  std::map<std::tuple<bool, int64_t, int64_t>, hipGraphExec_t> sg_graphs;
-  bool sg_off = false;                         // capture failed once (e.g. a collective that cannot be captured)
-  int64_t match_ns = 0;                        // device time of the last ksim_match_terms (HIP events)
-};
-
-namespace {
+namespace ksim_host {
 
 int set_err(ksim_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;
@@ -384,17 +80,11 @@ int hip_fail(ksim_handle* h, hipError_t e, const char* what) {
   return set_err(h, code, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-#define HIPCHK(h, expr)                                    \
-  do {                                                     \
-    hipError_t _e = (expr);                                \
-    if (_e != hipSuccess) return hip_fail((h), _e, #expr); \
-  } while (0)
-
 // Blocking copies on the handle's own non-blocking stream.  A hipMemcpy on the
 // legacy stream is refused while another host thread captures a graph (several
 // engines in one process: bench config 5's concurrent sweep), and stream order
 // is the order the engine relies on anyway.
-static hipError_t hcopy(ksim_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+hipError_t hcopy(ksim_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
   return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
 }
@@ -427,6 +117,10 @@ int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t b
   return KSIM_OK;
 }
 
+}  // namespace ksim_host
+
+namespace {
+
 // The per-pod cycle graphs (their kernels take the profile by value).
 void drop_cycle_graphs(ksim_handle* h) {
   for (auto& g : h->graph_cycle) {
@@ -451,6 +145,10 @@ void drop_lazy_graphs(ksim_handle* h) {
   drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
 }
 
+}  // namespace
+
+namespace ksim_host {
+
 void drop_graphs(ksim_handle* h) {
   drop_cycle_graphs(h);
   for (auto& kv : h->sweep_graphs)               // they hold the static columns and the queue
@@ -467,8 +165,31 @@ void drop_graphs(ksim_handle* h) {
   h->graph_tbatch = nullptr;
 }
 
-bool plugin_supported(int id) { return id >= 0 && id < KSIM_PL_COUNT; }
-bool is_sharded(const ksim_handle* h);
+// The loaded queue, with everything compiled against the rows it was loaded
+// on (its buffers are not kept for reuse: ksim_set_profile's narrower form is).
+void drop_loaded_pods(ksim_handle* h) {
+  free_bufs(h->pod_bufs);
+  h->pod_buf_bytes.clear();
+  h->dp = DevPods{};
+  h->batchable.clear();
+  h->topo.clear();
+}
+
+// The bound-pod table (ksim_set_bound_pods) and every list set on its rows.
+void drop_bound_pods(ksim_handle* h) {
+  free_bufs(h->pre_bufs);
+  free_bufs(h->pre_nom_bufs);
+  free_bufs(h->pre_add_bufs);
+  free_bufs(h->pre_pdb_bufs);
+  free_bufs(h->pre_vol_bufs);
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
+  h->pre = DevPreempt{};
+  h->pre_index.clear();
+  h->pre_n = 0;
+}
+
+bool is_sharded(const ksim_handle* h) { return h->comm != nullptr || h->shard_total != 0; }
 
 int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i) {
   const ksim_pod& p = ps->pods[i];
@@ -551,6 +272,12 @@ int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i) {
   return KSIM_OK;
 }
 
+}  // namespace ksim_host
+
+namespace {
+
+bool plugin_supported(int id) { return id >= 0 && id < KSIM_PL_COUNT; }
+
 // Batch-path eligibility of a pod and the constant it adds to every total.
 // The batch path needs P100 (every feasible node is kept, so no window) and
 // every normalized plugin constant over nodes:
@@ -576,8 +303,6 @@ bool static_trivial(const ksim_handle* h, const ksim_pod& p) {
     if (!((p.tol_filter[id >> 6] >> (id & 63)) & 1ull)) return false;
   return true;
 }
-
-bool is_sharded(const ksim_handle* h) { return h->comm != nullptr || h->shard_total != 0; }
 
 // The FAST batch kernels (dyn_key_fast): trivial pods, {cpu, memory}
 // strategies with weights in [1, 2^31), allocatable cpu / memory below 2^46.
@@ -648,8 +373,6 @@ bool stab_enabled() {
   return !off;
 }
 
-LaunchArgs make_args(ksim_handle* h, const DevPods& P, int32_t* chosen);
-
 // The static table of the loaded queue's classes on the current snapshot and
 // profile, rebuilt in place when stale (in stream order: a graph captured with
 // the table replays on the new contents, so a weight sweep keeps its graphs);
@@ -674,8 +397,7 @@ int ensure_stab(ksim_handle* h) {
     free_bufs(h->stab_bufs);
     h->stab_bytes = 0;
     void* p = nullptr;
-    int rc;
-    if ((rc = upload(h, h->stab_bufs, nullptr, 8 * entries, &p))) return rc;
+    if (const int rc = dev_alloc(h, h->stab_bufs, p, 8 * entries)) return rc;
     h->stab_bytes = 8 * entries;
   } else if (!was_ready) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -823,9 +545,8 @@ int fw_abandon(ksim_handle* h) {
 
 }  // namespace
 static int flush_deferred_binds(ksim_handle* h);
-static int flush_idle(ksim_handle* h);
 // The queued Reserve of the last framework cycle (pend_bind), launched now.
-static int flush_pend_bind(ksim_handle* h) {
+int ksim_host::flush_pend_bind(ksim_handle* h) {
   if (!h || !h->pend_bind.on) return KSIM_OK;
   h->pend_bind.on = false;
   HIPCHK(h, hipSetDevice(h->device));
@@ -833,9 +554,9 @@ static int flush_pend_bind(ksim_handle* h) {
   HIPCHK(h, hipGetLastError());
   return KSIM_OK;
 }
-namespace {
+namespace ksim_host {
 
-int ensure_ready(ksim_handle* h, bool fw = false, bool keep_pend = false) {
+int ensure_ready(ksim_handle* h, bool fw, bool keep_pend) {
   if (!h) return KSIM_E_INVALID;
   if (!keep_pend) {
     const int rc = flush_pend_bind(h);
@@ -886,6 +607,10 @@ int set_run(ksim_handle* h, int32_t first, int32_t end) {
   HIPCHK(h, hipMemsetAsync(h->sc.win, 0, sizeof(WinState), h->stream));
   return KSIM_OK;
 }
+
+}  // namespace ksim_host
+
+namespace {
 
 int read_state(ksim_handle* h, DevState& st) {
   HIPCHK(h, hipMemcpyAsync(&st, h->st, sizeof(st), hipMemcpyDeviceToHost, h->stream));
@@ -1028,27 +753,18 @@ int alloc_lazy(ksim_handle* h) {
   }
   const size_t n = (size_t)h->dc.n;
   int rc;
-  void* p = nullptr;
   int64_t** cols[5] = {&h->lazy_x1.req_cpu, &h->lazy_x1.req_mem, &h->lazy_x1.req_eph, &h->lazy_x1.nz_cpu,
                        &h->lazy_x1.nz_mem};
-  for (auto* c : cols) {
-    if ((rc = upload(h, h->lazy_bufs, nullptr, 8 * n, &p))) return rc;
-    *c = (int64_t*)p;
-  }
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 4 * n, &p))) return rc;
-  h->lazy_x1.num_pods = (int32_t*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, sizeof(DevState), &p))) return rc;
-  h->lazy_st1 = (DevState*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 8 * (size_t)kLazySlots * kBatchPods, &p))) return rc;
-  h->lazy_g = (uint64_t*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 8 * (size_t)kLazySlots * kBatchPods, &p))) return rc;
-  h->lazy_m = (uint64_t*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 4 * (size_t)kLazySlots, &p))) return rc;
-  h->lazy_e = (int32_t*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 4 * (size_t)kLazySlots * kBatchPods, &p))) return rc;
-  h->lazy_ab = (int32_t*)p;
-  if ((rc = upload(h, h->lazy_bufs, nullptr, 8 * (size_t)kLazySlots * kBatchPods, &p))) return rc;
-  h->lazy_aw = (int32_t*)p;
+  for (auto* c : cols)
+    if ((rc = dev_alloc(h, h->lazy_bufs, *c, 8 * n))) return rc;
+  if ((rc = dev_alloc(h, h->lazy_bufs, h->lazy_x1.num_pods, 4 * n)) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_st1, sizeof(DevState))) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_g, 8 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_m, 8 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_e, 4 * (size_t)kLazySlots)) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_ab, 4 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_aw, 8 * (size_t)kLazySlots * kBatchPods)))
+    return rc;
   h->lazy_n = h->dc.n;
   return KSIM_OK;
 }
@@ -1108,8 +824,7 @@ int ensure_rtab(ksim_handle* h) {
   free_bufs(h->rtab_bufs);
   h->rtab_bytes = 0;
   void* p = nullptr;
-  int rc;
-  if ((rc = upload(h, h->rtab_bufs, nullptr, need, &p))) return rc;
+  if (const int rc = dev_alloc(h, h->rtab_bufs, p, need)) return rc;
   h->rtab_bytes = need;
   return KSIM_OK;
 }
@@ -2251,14 +1966,11 @@ int adapt_shard_buffers(ksim_handle* h, int32_t world, int32_t W) {
   drop_cycle_graphs(h);                           // shard batch graphs captured over the old buffers
   free_bufs(h->ash_bufs);
   const size_t nw = (size_t)(h->dc.n_total + 63) / 64;
-  void* p = nullptr;
   int rc;
-  if ((rc = upload(h, h->ash_bufs, nullptr, 8 * (size_t)kBatchPods * W, &p))) return rc;
-  h->ash_send = (uint64_t*)p;
-  if ((rc = upload(h, h->ash_bufs, nullptr, 8 * (size_t)world * kBatchPods * W, &p))) return rc;
-  h->ash_recv = (uint64_t*)p;
-  if ((rc = upload(h, h->ash_bufs, nullptr, 8 * (size_t)kBatchPods * nw, &p))) return rc;
-  h->ash_gmask = (uint64_t*)p;
+  if ((rc = dev_alloc(h, h->ash_bufs, h->ash_send, 8 * (size_t)kBatchPods * W)) ||
+      (rc = dev_alloc(h, h->ash_bufs, h->ash_recv, 8 * (size_t)world * kBatchPods * W)) ||
+      (rc = dev_alloc(h, h->ash_bufs, h->ash_gmask, 8 * (size_t)kBatchPods * nw)))
+    return rc;
   h->ash_world = world;
   h->ash_w = W;
   return KSIM_OK;
@@ -2381,8 +2093,6 @@ int reset_counters(ksim_handle* h, hipStream_t stream) {
 
 }  // namespace
 
-extern "C" {
-
 int ksim_abi_version(void) { return KSIM_ABI_VERSION; }
 
 size_t ksim_abi_sizeof(int which) {
@@ -2464,7 +2174,7 @@ void ksim_destroy(ksim_handle* h) {
   if (h->sweep_rows.p) (void)hipFree(h->sweep_rows.p);
   free_bufs(h->stab_bufs);
   free_bufs(h->rtab_bufs);
-  free_bufs(h->pod_bufs);
+  drop_loaded_pods(h);
   if (h->pod1_arena.p) (void)hipFree(h->pod1_arena.p);
   if (h->nom_arena.p) (void)hipFree(h->nom_arena.p);
   for (auto& a : h->fw_arena)
@@ -2473,11 +2183,7 @@ void ksim_destroy(ksim_handle* h) {
   if (h->prog) (void)hipHostFree(h->prog);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->pout) (void)hipHostFree(h->pout);
-  free_bufs(h->pre_bufs);
-  free_bufs(h->pre_nom_bufs);
-  free_bufs(h->pre_add_bufs);
-  free_bufs(h->pre_pdb_bufs);
-  free_bufs(h->pre_vol_bufs);
+  drop_bound_pods(h);
   if (h->d_chosen) (void)hipFree(h->d_chosen);
   if (h->st) (void)hipFree(h->st);
   if (h->d_prof) (void)hipFree(h->d_prof);
@@ -2611,730 +2317,6 @@ int ksim_set_profile(ksim_handle* h, const ksim_profile* p) {
   return KSIM_OK;
 }
 
-int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab* v) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !t || !v) return KSIM_E_INVALID;
-  h->stab_dirty = true;
-  HIPCHK(h, hipSetDevice(h->device));
-  const int32_t n = t->n_nodes;
-  if (n < 0 || n > KSIM_MAX_NODES) return set_err(h, KSIM_E_INVALID, "n_nodes out of range");
-  if (t->n_scalar < 0 || t->n_scalar > KSIM_MAX_SCALAR) return set_err(h, KSIM_E_INVALID, "n_scalar out of range");
-  if (t->n_label_cols < 0 || t->n_label_cols > KSIM_MAX_LABEL_COLS)
-    return set_err(h, KSIM_E_INVALID, "n_label_cols out of range");
-  if (v->n_taints < 1 || v->n_taints > 64 * KSIM_TAINT_WORDS || !v->taint_effect)
-    return set_err(h, KSIM_E_INVALID, "n_taints out of range");
-  if (n > 0 && (!t->alloc_cpu || !t->alloc_mem || !t->alloc_eph || !t->alloc_pods || !t->req_cpu || !t->req_mem ||
-                !t->req_eph || !t->nz_cpu || !t->nz_mem || !t->num_pods || !t->flags || !t->taints ||
-                (t->n_label_cols > 0 && !t->labels) || (t->n_scalar > 0 && (!t->alloc_scalar || !t->req_scalar))))
-    return set_err(h, KSIM_E_INVALID, "null node column");
-  for (size_t i = 0; i < (size_t)n * KSIM_MAX_NODE_TAINTS; i++)
-    if (t->taints[i] >= v->n_taints) return set_err(h, KSIM_E_INVALID, "taint id out of vocabulary");
-  if (t->n_label_cols > 0 && (!v->label_col_offset || (v->n_label_values > 0 && (!v->label_num || !v->label_num_ok))))
-    return set_err(h, KSIM_E_INVALID, "null label vocabulary");
-  // value ids per label column: every label id must index its column's domain
-  // tables (device atomics use it as an address)
-  std::vector<int32_t> col_nvals((size_t)t->n_label_cols, 0);
-  int32_t vmax = 1;
-  for (int k = 0; k < t->n_label_cols; k++) {
-    const int32_t end = k + 1 < t->n_label_cols ? v->label_col_offset[k + 1] : v->n_label_values;
-    col_nvals[k] = end - v->label_col_offset[k];
-    if (v->label_col_offset[k] < 0 || col_nvals[k] < 1 || end > v->n_label_values)
-      return set_err(h, KSIM_E_INVALID, "label_col_offset not increasing within n_label_values");
-    if (col_nvals[k] > KSIM_MAX_NODES + 1) return set_err(h, KSIM_E_INVALID, "label column vocabulary too large");
-    vmax = std::max(vmax, col_nvals[k]);
-    for (int32_t i = 0; i < n; i++)
-      if (t->labels[(size_t)k * n + i] >= (uint32_t)col_nvals[k])
-        return set_err(h, KSIM_E_INVALID, "label value id out of its column's vocabulary");
-  }
-  if (t->n_classes < 0 || t->n_classes > KSIM_MAX_CLASSES || (t->n_classes > 0 && n > 0 && !t->class_count))
-    return set_err(h, KSIM_E_INVALID, "n_classes out of range / null class_count");
-  if (v->n_topo_log < 0 || (v->n_topo_log > 0 && !v->topo_log))
-    return set_err(h, KSIM_E_INVALID, "bad topo_log");
-  (void)hipStreamSynchronize(h->stream);
-  // the inputs are valid: the old snapshot goes, and with it the evaluation
-  // range (a replica calls ksim_set_eval_range again)
-  h->replicated = false;
-  drop_graphs(h);
-  free_bufs(h->cluster_bufs);
-  free_bufs(h->vol_bufs);               // the volume table belongs to the old snapshot (DevCluster c{} below)
-  h->vol_init = nullptr;
-  free_bufs(h->scratch_bufs);
-  free_bufs(h->ash_bufs);
-  free_bufs(h->lazy_bufs);
-  h->lazy_n = -1;
-  h->ash_send = h->ash_recv = h->ash_gmask = nullptr;
-  h->ash_world = h->ash_w = 0;
-  free_bufs(h->pod_bufs);
-  h->pod_buf_bytes.clear();
-  h->dp = DevPods{};
-  h->batchable.clear();
-  h->topo.clear();
-  h->has_cluster = false;
-  // node positions of the old snapshot: the bound-pod table and a pending
-  // extender round trip do not carry over
-  free_bufs(h->pre_bufs);
-  free_bufs(h->pre_nom_bufs);
-  free_bufs(h->pre_add_bufs);
-  free_bufs(h->pre_pdb_bufs);
-  free_bufs(h->pre_vol_bufs);
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  h->pre = DevPreempt{};
-  h->pre_index.clear();
-  h->pre_n = 0;
-  h->ext_pending = false;
-  h->fw_pending = h->fw_scored = h->fw_dom_dirty = false;   // fresh scratch below
-  h->deferred_binds.clear();           // Reserve / Unreserve queued against the old node positions
-
-  const int32_t n_total = h->shard_total ? h->shard_total : n;
-  if (h->shard_base < 0 || h->shard_base + n > n_total || n_total > KSIM_MAX_NODES)
-    return set_err(h, KSIM_E_INVALID, "shard range outside the cluster (ksim_set_shard)");
-  DevCluster c{};
-  c.count_whole = 1;
-  c.base = h->shard_base;
-  c.n_total = n_total;
-  c.n_classes = t->n_classes;
-  c.n_topo_log = v->n_topo_log;
-  c.vmax = vmax;
-  c.n = n;
-  c.n_scalar = t->n_scalar;
-  c.n_label_cols = t->n_label_cols;
-  c.n_taints = v->n_taints;
-  c.n_label_values = v->n_label_values;
-  const size_t N = (size_t)n;
-  int rc;
-#define UP(field, src, bytes)                                                         \
-  do {                                                                                \
-    void* _p = nullptr;                                                               \
-    if ((rc = upload(h, h->cluster_bufs, (src), (bytes), &_p)) != KSIM_OK) return rc; \
-    c.field = reinterpret_cast<decltype(c.field)>(_p);                                \
-  } while (0)
-  UP(alloc_cpu, t->alloc_cpu, 8 * N);
-  UP(alloc_mem, t->alloc_mem, 8 * N);
-  UP(alloc_eph, t->alloc_eph, 8 * N);
-  UP(alloc_pods, t->alloc_pods, 4 * N);
-  UP(alloc_scalar, t->alloc_scalar, 8 * N * t->n_scalar);
-  UP(req_cpu, t->req_cpu, 8 * N);
-  UP(req_mem, t->req_mem, 8 * N);
-  UP(req_eph, t->req_eph, 8 * N);
-  UP(req_scalar, t->req_scalar, 8 * N * t->n_scalar);
-  UP(nz_cpu, t->nz_cpu, 8 * N);
-  UP(nz_mem, t->nz_mem, 8 * N);
-  UP(num_pods, t->num_pods, 4 * N);
-  UP(flags, t->flags, 4 * N);
-  UP(taints, t->taints, 2 * N * KSIM_MAX_NODE_TAINTS);
-  UP(labels, t->labels, 4 * N * t->n_label_cols);
-  UP(taint_effect, v->taint_effect, (size_t)v->n_taints);
-  UP(label_col_offset, v->label_col_offset, 4 * (size_t)t->n_label_cols);
-  UP(label_num, v->label_num, 8 * (size_t)std::max(v->n_label_values, 0));
-  UP(label_num_ok, v->label_num_ok, (size_t)std::max(v->n_label_values, 0));
-  UP(cnt, t->class_count, 4 * N * (size_t)t->n_classes);
-  UP(topo_log, v->topo_log, 8 * (size_t)v->n_topo_log);
-  UP(col_nvals, col_nvals.data(), 4 * col_nvals.size());
-  {
-    // label columns whose every value sits on at most one node (hostname):
-    // InterPodAffinity reads the node's own count there (kUseUniqueCol); off
-    // on shard handles, whose domain sums are exchanged as tables
-    std::vector<uint8_t> uniq((size_t)t->n_label_cols, 0);
-    if (!h->shard_total) {
-      std::vector<uint8_t> seen;
-      for (int k = 0; k < t->n_label_cols; k++) {
-        seen.assign((size_t)col_nvals[k], 0);
-        bool u = true;
-        for (int32_t i = 0; i < n && u; i++) {
-          const uint32_t v = t->labels[(size_t)k * n + i];
-          if (v && seen[v]++) u = false;
-        }
-        uniq[k] = u;
-      }
-    }
-    UP(col_unique, uniq.data(), uniq.size());
-    h->col_unique = uniq;
-    h->col_total.assign((size_t)t->n_label_cols, 1);
-    for (int k = 0; k < t->n_label_cols; k++)
-      for (int32_t i = 0; i < n && h->col_total[k]; i++)
-        if (!t->labels[(size_t)k * n + i]) h->col_total[k] = 0;
-  }
-  UP(nb_limit, t->nb_limit, 8 * N);                      // zeros when no node has the annotation
-  UP(nb_alloc, t->nb_alloc, 8 * N);
-  {
-    std::vector<double> ic(N), im(N);                  // RN(1 / allocatable): IEEE division on the host
-    for (size_t i = 0; i < N; i++) {
-      ic[i] = t->alloc_cpu[i] ? 1.0 / (double)t->alloc_cpu[i] : 0.0;
-      im[i] = t->alloc_mem[i] ? 1.0 / (double)t->alloc_mem[i] : 0.0;
-    }
-    UP(inv_cpu, ic.data(), 8 * N);
-    UP(inv_mem, im.data(), 8 * N);
-  }
-#undef UP
-  h->col_nvals = col_nvals;
-  c.fit_ignore = h->has_profile ? h->prof.fit_ignored_scalar : 0u;
-  h->dc = c;
-  h->taint_effect.assign(v->taint_effect, v->taint_effect + v->n_taints);
-  {
-    std::vector<uint8_t> seen((size_t)v->n_taints, 0);
-    for (size_t i = 0; i < (size_t)n * KSIM_MAX_NODE_TAINTS; i++) seen[t->taints[i]] = 1;
-    h->hard_taints.clear();
-    for (int id = 1; id < v->n_taints; id++)
-      if (seen[id] && (v->taint_effect[id] == KSIM_EFFECT_NO_SCHEDULE || v->taint_effect[id] == KSIM_EFFECT_NO_EXECUTE))
-        h->hard_taints.push_back((uint16_t)id);
-    h->any_unschedulable = false;
-    for (int32_t i = 0; i < n; i++) h->any_unschedulable = h->any_unschedulable || (t->flags[i] & KSIM_NODE_UNSCHEDULABLE);
-    c.cflags = h->any_unschedulable ? kClusterUnschedulable : 0u;
-    if (!h->hard_taints.empty()) c.cflags |= kClusterHardTaints;
-    for (size_t i = 0; i < (size_t)n * KSIM_MAX_NODE_TAINTS; i++)
-      if (t->taints[i] && v->taint_effect[t->taints[i]] == KSIM_EFFECT_PREFER_NO_SCHEDULE) c.cflags |= kClusterPreferTaints;
-    h->dc.cflags = c.cflags;
-    h->alloc_narrow = true;
-    for (int32_t i = 0; i < n; i++)
-      h->alloc_narrow = h->alloc_narrow && t->alloc_cpu[i] >= 0 && t->alloc_cpu[i] < (1ll << 46) &&
-                        t->alloc_mem[i] >= 0 && t->alloc_mem[i] < (1ll << 46);
-    if (h->alloc_narrow) h->dc.cflags |= kClusterNarrow;
-  }
-  {
-    void* q = nullptr;
-#define SNAP(field, bytes)                                                                 \
-  do {                                                                                     \
-    if ((rc = upload(h, h->cluster_bufs, nullptr, (bytes), &q)) != KSIM_OK) return rc;     \
-    h->init.field = reinterpret_cast<decltype(h->init.field)>(q);                          \
-    HIPCHK(h, hipMemcpyAsync(q, c.field, (bytes), hipMemcpyDeviceToDevice, h->stream));     \
-  } while (0)
-    SNAP(req_cpu, 8 * N);
-    SNAP(req_mem, 8 * N);
-    SNAP(req_eph, 8 * N);
-    SNAP(req_scalar, 8 * N * t->n_scalar);
-    SNAP(nz_cpu, 8 * N);
-    SNAP(nz_mem, 8 * N);
-    SNAP(num_pods, 4 * N);
-    SNAP(cnt, 4 * N * (size_t)t->n_classes);
-    SNAP(nb_alloc, 8 * N);
-#undef SNAP
-  }
-
-  DevScratch s{};
-  DevEvalOut o{};
-  void* p = nullptr;
-#define SCR(dst, type, bytes)                                                         \
-  do {                                                                                \
-    if ((rc = upload(h, h->scratch_bufs, nullptr, (bytes), &p)) != KSIM_OK) return rc; \
-    dst = (type)p;                                                                    \
-  } while (0)
-  SCR(s.fail, uint8_t*, N);
-  SCR(s.ign, uint8_t*, N);
-  SCR(s.win, WinState*, sizeof(WinState));
-  SCR(s.bbest, uint64_t*, 16 * ((N + 255) / 256));
-  SCR(s.regbm, uint32_t*, 4 * (size_t)KSIM_MAX_USES * ((vmax + 31) / 32));
-  SCR(h->ext_fail, uint8_t*, N);
-  SCR(h->ext_score, int64_t*, 8 * N);
-  SCR(h->fw_nodes, int32_t*, 4 * N);
-  SCR(h->fw_vals, int64_t*, 8 * N);
-  SCR(h->fw_out, int64_t*, 8 * N);
-  SCR(s.detail, uint32_t*, 4 * N);
-  SCR(s.raw, int64_t*, 8 * N * KSIM_MAX_SCORE);
-  SCR(s.part, int64_t*, 8 * N);
-  // [B][kMaxListRecords] list records: the node-stationary evaluation writes one per node slice
-  SCR(s.topk, uint64_t*, 8 * (size_t)kBatchPods * kMaxListRecords * kTopT);
-  SCR(s.topk_cnt, int32_t*, 4 * (size_t)kBatchPods * kMaxListRecords);
-  SCR(s.topk_complete, int32_t*, 4 * (size_t)kBatchPods * kMaxListRecords);
-  SCR(s.gkey, uint64_t*, 8 * (size_t)kBatchPods);
-  SCR(s.chain_end, int32_t*, 4);
-  SCR(s.pmax, uint64_t*, 8 * 2 * (size_t)kBatchPods);   // [M | sharded ADAPT broken flags]
-  SCR(s.pnorm, int64_t*, 8 * 4 * (size_t)kBatchPods);
-  const size_t NT = N <= (size_t)kTbMaxBlocks * 256 ? N : 0;   // topology batches (tbatch_admit)
-  SCR(s.tb_fail, uint8_t*, (size_t)kTbPods * NT);
-  SCR(s.tb_ign, uint8_t*, (size_t)kTbPods * NT);
-  SCR(s.tb_part, int64_t*, 8 * (size_t)kTbPods * NT);
-  SCR(s.tb_raw, int64_t*, 8 * (size_t)kTbPods * KSIM_MAX_SCORE * NT);
-  SCR(s.tb_stat, int32_t*, 4 * (size_t)kTbPods * kVarSlots * NT);   // per zone-variant slot
-  SCR(s.tb_win, WinState*, sizeof(WinState) * (size_t)kTbPods);
-  SCR(s.tb_var, TbVar*, sizeof(TbVar) * (size_t)kTbPods);
-  SCR(s.tb_dom, TbDom*, sizeof(TbDom) * (size_t)kTbPods * kVarDom);
-  SCR(s.tb_vhold, int32_t*, 4 * (size_t)kTbPods * kVarSlots * 2 * KSIM_MAX_SCORE);
-  SCR(s.tb_slot, int32_t*, 4 * (size_t)kTbPods);
-  SCR(s.tb_vdom, uint8_t*, (size_t)kTbPods * NT);
-  SCR(s.tb_cdom, uint8_t*, (size_t)kTbPods * kVarSlots * kTbMaxBlocks * kTopT);
-  SCR(s.tb_kdom, uint8_t*, (size_t)kTbPods * kVarSlots * kTopT);
-  SCR(s.tb_vnf, int32_t*, 4 * (size_t)kTbPods * kVarSlots);
-  SCR(s.tb_vpods, unsigned long long*, 8);
-  SCR(s.tb_clist, uint64_t*, 8 * (size_t)kTbPods * kVarSlots * kTbMaxBlocks * kTopT);
-  SCR(s.tb_ccnt, int32_t*, 4 * (size_t)kTbPods * kVarSlots * kTbMaxBlocks);
-  SCR(s.tb_xrecv, uint8_t*, sizeof(WinState) * (size_t)kMaxShards * kTbPods);
-  SCR(s.tb_pp, uint64_t*, 8 * 2 * (size_t)kTbPods);
-  SCR(s.pinv, int32_t*, 4 * (size_t)kBatchPods);
-  SCR(s.dom, int64_t*, 8 * (size_t)KSIM_MAX_USES * vmax);
-  SCR(s.dbg, unsigned long long*, 8 * 16);
-  SCR(s.xsend, uint64_t*, 8 * (size_t)kBatchPods * kXRec);
-  SCR(s.xrecv, uint64_t*, 8 * (size_t)kMaxShards * kBatchPods * kXRec);
-  SCR(s.min_match, int64_t*, 8 * (size_t)KSIM_MAX_USES);
-  SCR(s.xdom, int64_t*, 8 * (size_t)KSIM_MAX_USES * vmax);
-  SCR(s.amask, uint64_t*, 8 * (size_t)kBatchPods * ((N + 63) / 64));
-  SCR(s.awin, int32_t*, 4 * 2 * (size_t)kBatchPods);
-  SCR(s.aexact, int32_t*, 4);
-  SCR(s.acut, int32_t*, 4 * 2 * (size_t)kBatchPods);
-  {                                      // the doubling window's tables (clusters of <= 128 bitmap words)
-    const size_t NW = (N + 63) / 64 <= 128 ? N : 0;
-    SCR(s.wtab, uint16_t*, 2 * 3 * (size_t)kBatchPods * std::max<size_t>(NW, 1));
-    SCR(s.wtot, int32_t*, 4 * (size_t)kBatchPods);
-  }
-  SCR(s.abroken, int32_t*, 4 * (size_t)kBatchPods);
-  SCR(s.xreg, int64_t*, 8 * (1 + (size_t)KSIM_MAX_USES * vmax));
-  SCR(o.scored, uint8_t*, N);
-  SCR(o.raw, int64_t*, 8 * N * KSIM_MAX_SCORE);
-  SCR(o.norm, int64_t*, 8 * N * KSIM_MAX_SCORE);
-  SCR(o.total, int64_t*, 8 * N);
-#undef SCR
-  h->sc = s;
-  h->eo = o;
-  DevState zero{};
-  HIPCHK(h, hipMemcpyAsync(h->st, &zero, sizeof(zero), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->has_cluster = true;
-  if (h->d_chosen) (void)hipFree(h->d_chosen);
-  h->d_chosen = nullptr;
-  return KSIM_OK;
-}
-
-// Node informer deltas: the new table in nodeTree order, old_pos[i] = the
-// current position of new node i or -1 (added).  The table is the new
-// snapshot (static columns, vocabulary and the dynamic columns of the bound
-// pods); on a kept node the binds the cycles made since the last snapshot
-// (device column - snapshot column at old_pos) are replayed on top of it, for
-// every scalar column / count class the handle already has.  nextStartNodeIndex
-// carries over mod the new node count (upstream keeps the index and scans
-// nodes[(index + i) % numAllNodes]), and so does the tie-break sequence.
-// Loaded pods, the bound-pod table and captured graphs are dropped (node
-// positions changed).
-int ksim_upsert_nodes(ksim_handle* h, const ksim_node_table* t, const ksim_vocab* v, const int32_t* old_pos) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  // (a replica keeps its flag when the delta is refused; the new snapshot
-  // below clears it: ksim_set_eval_range again)
-  if (!h || !t || !v) return KSIM_E_INVALID;
-  h->stab_dirty = true;
-  if (!h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_upsert_nodes before ksim_set_cluster");
-  if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_upsert_nodes on a shard handle");
-  if (h->dc.vol_nf)
-    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_upsert_nodes while a volume table is set (send the snapshot and "
-                                          "ksim_set_volume_limits again)");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int32_t n = t->n_nodes, n0 = h->dc.n;
-  if (n < 0 || n > KSIM_MAX_NODES) return set_err(h, KSIM_E_INVALID, "n_nodes out of range");
-  if (n > 0 && !old_pos) return set_err(h, KSIM_E_INVALID, "null old_pos");
-  const int32_t s0 = h->dc.n_scalar, c0 = h->dc.n_classes;
-  if (t->n_scalar < s0 || t->n_scalar > KSIM_MAX_SCALAR)
-    return set_err(h, KSIM_E_INVALID, "scalar columns may only be appended");
-  if (t->n_classes < c0 || t->n_classes > KSIM_MAX_CLASSES)
-    return set_err(h, KSIM_E_INVALID, "count classes may only be appended");
-  if (n > 0 && (!t->req_cpu || !t->req_mem || !t->req_eph || !t->nz_cpu || !t->nz_mem || !t->num_pods ||
-                (t->n_scalar > 0 && !t->req_scalar) || (t->n_classes > 0 && !t->class_count)))
-    return set_err(h, KSIM_E_INVALID, "null node column");
-  {
-    std::vector<uint8_t> seen((size_t)n0, 0);
-    for (int32_t i = 0; i < n; i++) {
-      const int32_t op = old_pos[i];
-      if (op < -1 || op >= n0 || (op >= 0 && seen[op]++))
-        return set_err(h, KSIM_E_INVALID, "old_pos: out of range or repeated");
-    }
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  DevState st{};
-  HIPCHK(h, hcopy(h, &st, h->st, sizeof(st), hipMemcpyDeviceToHost));
-  const size_t N = (size_t)n, N0 = (size_t)n0;
-  // out = table + (device - snapshot) at old_pos, rows of n0 -> rows of n
-  auto replay = [&](auto& out, const auto* dev, const auto* snap, const auto* tab, int rows, int rows0) -> int {
-    using T = typename std::remove_reference<decltype(out)>::type::value_type;
-    std::vector<T> a(N0 * (size_t)rows0), b(N0 * (size_t)rows0);
-    if (!a.empty()) {
-      HIPCHK(h, hcopy(h, a.data(), dev, sizeof(T) * a.size(), hipMemcpyDeviceToHost));
-      HIPCHK(h, hcopy(h, b.data(), snap, sizeof(T) * b.size(), hipMemcpyDeviceToHost));
-    }
-    out.assign(N * (size_t)rows, 0);
-    for (int k = 0; k < rows; k++)
-      for (size_t i = 0; i < N; i++) {
-        T x = tab ? tab[k * N + i] : 0;
-        if (k < rows0 && old_pos[i] >= 0) x += a[k * N0 + old_pos[i]] - b[k * N0 + old_pos[i]];
-        out[k * N + i] = x;
-      }
-    return KSIM_OK;
-  };
-  std::vector<int64_t> rc_, rm, re, rs, zc, zm, nb;
-  std::vector<int32_t> np, cnt;
-  int rc;
-  const DevCluster& c = h->dc;
-  if ((rc = replay(rc_, c.req_cpu, h->init.req_cpu, t->req_cpu, 1, 1)) ||
-      (rc = replay(rm, c.req_mem, h->init.req_mem, t->req_mem, 1, 1)) ||
-      (rc = replay(re, c.req_eph, h->init.req_eph, t->req_eph, 1, 1)) ||
-      (rc = replay(rs, c.req_scalar, h->init.req_scalar, t->req_scalar, t->n_scalar, s0)) ||
-      (rc = replay(zc, c.nz_cpu, h->init.nz_cpu, t->nz_cpu, 1, 1)) ||
-      (rc = replay(zm, c.nz_mem, h->init.nz_mem, t->nz_mem, 1, 1)) ||
-      (rc = replay(nb, c.nb_alloc, h->init.nb_alloc, t->nb_alloc, 1, 1)) ||
-      (rc = replay(np, c.num_pods, h->init.num_pods, t->num_pods, 1, 1)) ||
-      (rc = replay(cnt, c.cnt, h->init.cnt, t->class_count, t->n_classes, c0)))
-    return rc;
-  // the table becomes the snapshot (ksim_set_cluster copies it to h->init)
-  if ((rc = ksim_set_cluster(h, t, v)) != KSIM_OK) return rc;
-  const DevCluster& d = h->dc;
-  auto put = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (bytes) HIPCHK(h, hcopy(h, dst, src, bytes, hipMemcpyHostToDevice));
-    return KSIM_OK;
-  };
-  if ((rc = put(d.req_cpu, rc_.data(), 8 * N)) || (rc = put(d.req_mem, rm.data(), 8 * N)) ||
-      (rc = put(d.req_eph, re.data(), 8 * N)) || (rc = put(d.req_scalar, rs.data(), 8 * rs.size())) ||
-      (rc = put(d.nz_cpu, zc.data(), 8 * N)) || (rc = put(d.nz_mem, zm.data(), 8 * N)) ||
-      (rc = put(d.num_pods, np.data(), 4 * N)) || (rc = put(d.cnt, cnt.data(), 4 * cnt.size())) ||
-      (rc = put(d.nb_alloc, nb.data(), 8 * N)))
-    return rc;
-  DevState s2{};
-  s2.next_start = n > 0 ? st.next_start % n : 0;
-  s2.pod_seq = st.pod_seq;
-  HIPCHK(h, hcopy(h, h->st, &s2, sizeof(s2), hipMemcpyHostToDevice));
-  return KSIM_OK;
-}
-
-// DeleteNode: the node at `pos` leaves; later positions move down by one.  The
-// table handed to ksim_upsert_nodes is the current snapshot without it, so the
-// replay keeps every other node's state.
-static int pin_reserve(ksim_handle* h, size_t bytes);
-
-// UpdateNode in place: the changed rows' static columns through one launch
-// from the pinned staging; the cluster facts the filter plans read (hard
-// taints, unschedulable nodes, narrow allocatable, unique / total label
-// columns) recomputed from the whole table on the host.
-int ksim_update_node_rows(ksim_handle* h, const ksim_node_table* t, const ksim_vocab* v, const int32_t* rows,
-                          int32_t n_rows) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !t || !v || n_rows < 0 || (n_rows > 0 && !rows)) return KSIM_E_INVALID;
-  if (!h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_update_node_rows before ksim_set_cluster");
-  if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_update_node_rows on a shard handle");
-  if (h->dc.vol_nf)
-    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_update_node_rows while a volume table is set (send the snapshot and "
-                                          "ksim_set_volume_limits again)");
-  const DevCluster& c = h->dc;
-  const int32_t n = c.n;
-  if (t->n_nodes != n || t->n_scalar != c.n_scalar || t->n_label_cols != c.n_label_cols ||
-      t->n_classes != c.n_classes || v->n_taints != c.n_taints || v->n_label_values != c.n_label_values)
-    return set_err(h, KSIM_E_INVALID, "ksim_update_node_rows: the table's layout or vocabulary differs (ksim_upsert_nodes)");
-  if (n > 0 && (!t->alloc_cpu || !t->alloc_mem || !t->alloc_eph || !t->alloc_pods || !t->flags || !t->taints ||
-                (t->n_label_cols > 0 && !t->labels) || (t->n_scalar > 0 && !t->alloc_scalar)))
-    return set_err(h, KSIM_E_INVALID, "null node column");
-  for (int k = 0; k < c.n_label_cols; k++)
-    if (!v->label_col_offset || (k + 1 < c.n_label_cols ? v->label_col_offset[k + 1] : v->n_label_values) -
-                                        v->label_col_offset[k] != h->col_nvals[k])
-      return set_err(h, KSIM_E_INVALID, "ksim_update_node_rows: a label column's vocabulary changed (ksim_upsert_nodes)");
-  if (!v->taint_effect || !std::equal(h->taint_effect.begin(), h->taint_effect.end(), v->taint_effect))
-    return set_err(h, KSIM_E_INVALID, "ksim_update_node_rows: the taint vocabulary changed (ksim_upsert_nodes)");
-  const size_t N = (size_t)n;
-  std::vector<uint8_t> seen_row((size_t)n, 0);
-  for (int32_t q = 0; q < n_rows; q++) {
-    const int32_t r = rows[q];
-    if (r < 0 || r >= n || seen_row[r]++) return set_err(h, KSIM_E_INVALID, "rows: out of range or repeated");
-    for (int k = 0; k < KSIM_MAX_NODE_TAINTS; k++)
-      if (t->taints[(size_t)k * N + r] >= v->n_taints) return set_err(h, KSIM_E_INVALID, "taint id out of vocabulary");
-    for (int k = 0; k < c.n_label_cols; k++)
-      if (t->labels[(size_t)k * N + r] >= (uint32_t)h->col_nvals[k])
-        return set_err(h, KSIM_E_INVALID, "label value id out of its column's vocabulary");
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));     // the pinned staging is free
-  const int32_t words = 1 + 8 + KSIM_MAX_NODE_TAINTS + c.n_scalar + c.n_label_cols;
-  int rc;
-  if ((rc = pin_reserve(h, 8 * (size_t)words * (size_t)std::max(n_rows, 1)))) return rc;
-  int64_t* rec = (int64_t*)h->pin;
-  for (int32_t q = 0; q < n_rows; q++) {
-    const int32_t r = rows[q];
-    int64_t* w = rec + (size_t)q * words;
-    const double ic = t->alloc_cpu[r] ? 1.0 / (double)t->alloc_cpu[r] : 0.0;   // as ksim_set_cluster
-    const double im = t->alloc_mem[r] ? 1.0 / (double)t->alloc_mem[r] : 0.0;
-    w[0] = r;
-    w[1] = t->alloc_cpu[r];
-    w[2] = t->alloc_mem[r];
-    w[3] = t->alloc_eph[r];
-    w[4] = t->alloc_pods[r];
-    w[5] = t->flags[r];
-    w[6] = t->nb_limit ? t->nb_limit[r] : 0;
-    std::memcpy(&w[7], &ic, 8);
-    std::memcpy(&w[8], &im, 8);
-    for (int k = 0; k < KSIM_MAX_NODE_TAINTS; k++) w[9 + k] = t->taints[(size_t)k * N + r];
-    for (int k = 0; k < c.n_scalar; k++) w[9 + KSIM_MAX_NODE_TAINTS + k] = t->alloc_scalar[(size_t)k * N + r];
-    for (int k = 0; k < c.n_label_cols; k++)
-      w[9 + KSIM_MAX_NODE_TAINTS + c.n_scalar + k] = t->labels[(size_t)k * N + r];
-  }
-  launch_node_rows(c, (const int64_t*)h->pin_d, n_rows, words, h->stream);
-  HIPCHK(h, hipGetLastError());
-  // the cluster facts, from the whole table (as ksim_set_cluster)
-  {
-    std::vector<uint8_t> seen((size_t)v->n_taints, 0);
-    for (size_t i = 0; i < N * KSIM_MAX_NODE_TAINTS; i++) seen[t->taints[i]] = 1;
-    h->hard_taints.clear();
-    for (int id = 1; id < v->n_taints; id++)
-      if (seen[id] && (h->taint_effect[id] == KSIM_EFFECT_NO_SCHEDULE || h->taint_effect[id] == KSIM_EFFECT_NO_EXECUTE))
-        h->hard_taints.push_back((uint16_t)id);
-    h->any_unschedulable = false;
-    for (int32_t i = 0; i < n; i++) h->any_unschedulable = h->any_unschedulable || (t->flags[i] & KSIM_NODE_UNSCHEDULABLE);
-    uint32_t cf = h->any_unschedulable ? kClusterUnschedulable : 0u;
-    if (!h->hard_taints.empty()) cf |= kClusterHardTaints;
-    for (size_t i = 0; i < N * KSIM_MAX_NODE_TAINTS; i++)
-      if (t->taints[i] && h->taint_effect[t->taints[i]] == KSIM_EFFECT_PREFER_NO_SCHEDULE) cf |= kClusterPreferTaints;
-    h->alloc_narrow = true;
-    for (int32_t i = 0; i < n; i++)
-      h->alloc_narrow = h->alloc_narrow && t->alloc_cpu[i] >= 0 && t->alloc_cpu[i] < (1ll << 46) &&
-                        t->alloc_mem[i] >= 0 && t->alloc_mem[i] < (1ll << 46);
-    if (h->alloc_narrow) cf |= kClusterNarrow;
-    h->dc.cflags = cf;
-    std::vector<uint8_t> uniq((size_t)c.n_label_cols, 0);
-    std::vector<uint8_t> vs;
-    for (int k = 0; k < c.n_label_cols; k++) {
-      vs.assign((size_t)h->col_nvals[k], 0);
-      bool u = true;
-      for (int32_t i = 0; i < n && u; i++) {
-        const uint32_t x = t->labels[(size_t)k * N + i];
-        if (x && vs[x]++) u = false;
-      }
-      uniq[k] = u;
-      h->col_total[k] = 1;
-      for (int32_t i = 0; i < n && h->col_total[k]; i++)
-        if (!t->labels[(size_t)k * N + i]) h->col_total[k] = 0;
-    }
-    if (uniq != h->col_unique && c.n_label_cols > 0) {
-      HIPCHK(h, hcopy(h, const_cast<uint8_t*>(c.col_unique), uniq.data(), uniq.size(), hipMemcpyHostToDevice));
-      h->col_unique = uniq;
-    }
-  }
-  // what was compiled against the old rows: graphs, the static-class table, loaded pods
-  drop_graphs(h);
-  h->stab_dirty = true;
-  free_bufs(h->pod_bufs);
-  h->pod_buf_bytes.clear();
-  h->dp = DevPods{};
-  h->batchable.clear();
-  h->topo.clear();
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return KSIM_OK;
-}
-
-int ksim_remove_node(ksim_handle* h, int32_t pos) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "cluster not set");
-  h->stab_dirty = true;
-  if (h->shard_total || h->world > 1) return set_err(h, KSIM_E_UNSUPPORTED, "ksim_remove_node on a shard handle");
-  if (h->dc.vol_nf)
-    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_remove_node while a volume table is set (send the snapshot and "
-                                          "ksim_set_volume_limits again)");
-  const int32_t n0 = h->dc.n;
-  if (pos < 0 || pos >= n0) return set_err(h, KSIM_E_INVALID, "node position out of range");
-  h->replicated = false;                        // a new snapshot: ksim_set_eval_range again
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const DevCluster& c = h->dc;
-  const int32_t n = n0 - 1;
-  const size_t N0 = (size_t)n0;
-  // the static columns and vocabulary, read back and compacted
-  auto pull = [&](auto& out, const auto* dev, size_t rows) -> int {
-    using T = typename std::remove_reference<decltype(out)>::type::value_type;
-    std::vector<T> all(N0 * rows);
-    if (!all.empty()) HIPCHK(h, hcopy(h, all.data(), dev, sizeof(T) * all.size(), hipMemcpyDeviceToHost));
-    out.clear();
-    for (size_t k = 0; k < rows; k++)
-      for (size_t i = 0; i < N0; i++)
-        if ((int32_t)i != pos) out.push_back(all[k * N0 + i]);
-    return KSIM_OK;
-  };
-  std::vector<int64_t> ac, am, ae, as, rc_, rm, re, rs, zc, zm, nbl, nba;
-  std::vector<int32_t> ap, np, cnt;
-  std::vector<uint32_t> fl, lb;
-  std::vector<uint16_t> tn;
-  int rc;
-  if ((rc = pull(ac, c.alloc_cpu, 1)) || (rc = pull(am, c.alloc_mem, 1)) || (rc = pull(ae, c.alloc_eph, 1)) ||
-      (rc = pull(as, c.alloc_scalar, (size_t)c.n_scalar)) || (rc = pull(ap, c.alloc_pods, 1)) ||
-      (rc = pull(rc_, h->init.req_cpu, 1)) || (rc = pull(rm, h->init.req_mem, 1)) ||
-      (rc = pull(re, h->init.req_eph, 1)) || (rc = pull(rs, h->init.req_scalar, (size_t)c.n_scalar)) ||
-      (rc = pull(zc, h->init.nz_cpu, 1)) || (rc = pull(zm, h->init.nz_mem, 1)) ||
-      (rc = pull(np, h->init.num_pods, 1)) || (rc = pull(fl, c.flags, 1)) ||
-      (rc = pull(tn, c.taints, KSIM_MAX_NODE_TAINTS)) || (rc = pull(lb, c.labels, (size_t)c.n_label_cols)) ||
-      (rc = pull(cnt, h->init.cnt, (size_t)c.n_classes)) || (rc = pull(nbl, c.nb_limit, 1)) ||
-      (rc = pull(nba, h->init.nb_alloc, 1)))
-    return rc;
-  std::vector<uint8_t> te(h->taint_effect);
-  std::vector<int32_t> lco((size_t)c.n_label_cols);
-  std::vector<int64_t> lnum((size_t)std::max(c.n_label_values, 0));
-  std::vector<uint8_t> lok((size_t)std::max(c.n_label_values, 0));
-  std::vector<double> tlog((size_t)c.n_topo_log);
-  if (!lco.empty()) HIPCHK(h, hcopy(h, lco.data(), c.label_col_offset, 4 * lco.size(), hipMemcpyDeviceToHost));
-  if (!lnum.empty()) {
-    HIPCHK(h, hcopy(h, lnum.data(), c.label_num, 8 * lnum.size(), hipMemcpyDeviceToHost));
-    HIPCHK(h, hcopy(h, lok.data(), c.label_num_ok, lok.size(), hipMemcpyDeviceToHost));
-  }
-  if (!tlog.empty()) HIPCHK(h, hcopy(h, tlog.data(), c.topo_log, 8 * tlog.size(), hipMemcpyDeviceToHost));
-  ksim_node_table t{};
-  t.n_nodes = n;
-  t.n_scalar = c.n_scalar;
-  t.n_label_cols = c.n_label_cols;
-  t.alloc_cpu = ac.data();
-  t.alloc_mem = am.data();
-  t.alloc_eph = ae.data();
-  t.alloc_pods = ap.data();
-  t.alloc_scalar = as.data();
-  t.req_cpu = rc_.data();
-  t.req_mem = rm.data();
-  t.req_eph = re.data();
-  t.req_scalar = rs.data();
-  t.nz_cpu = zc.data();
-  t.nz_mem = zm.data();
-  t.num_pods = np.data();
-  t.flags = fl.data();
-  t.taints = tn.data();
-  t.labels = lb.data();
-  t.n_classes = c.n_classes;
-  t.class_count = cnt.data();
-  t.nb_limit = nbl.data();
-  t.nb_alloc = nba.data();
-  ksim_vocab v{};
-  v.n_taints = (int32_t)te.size();
-  v.n_label_values = c.n_label_values;
-  v.taint_effect = te.data();
-  v.label_col_offset = lco.data();
-  v.label_num = lnum.data();
-  v.label_num_ok = lok.data();
-  v.n_topo_log = c.n_topo_log;
-  v.topo_log = tlog.data();
-  std::vector<int32_t> old_pos((size_t)std::max(n, 1));
-  for (int32_t i = 0; i < n; i++) old_pos[i] = i < pos ? i : i + 1;
-  return ksim_upsert_nodes(h, &t, &v, old_pos.data());
-}
-
-int ksim_get_node_state(ksim_handle* h, int64_t* req_cpu, int64_t* req_mem, int64_t* req_eph, int64_t* nz_cpu,
-                        int64_t* nz_mem, int32_t* num_pods) {
-  if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "cluster not set");
-  if (int rc = flush_idle(h)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t N = (size_t)h->dc.n;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (req_cpu) HIPCHK(h, hcopy(h, req_cpu, h->dc.req_cpu, 8 * N, hipMemcpyDeviceToHost));
-  if (req_mem) HIPCHK(h, hcopy(h, req_mem, h->dc.req_mem, 8 * N, hipMemcpyDeviceToHost));
-  if (req_eph) HIPCHK(h, hcopy(h, req_eph, h->dc.req_eph, 8 * N, hipMemcpyDeviceToHost));
-  if (nz_cpu) HIPCHK(h, hcopy(h, nz_cpu, h->dc.nz_cpu, 8 * N, hipMemcpyDeviceToHost));
-  if (nz_mem) HIPCHK(h, hcopy(h, nz_mem, h->dc.nz_mem, 8 * N, hipMemcpyDeviceToHost));
-  if (num_pods) HIPCHK(h, hcopy(h, num_pods, h->dc.num_pods, 4 * N, hipMemcpyDeviceToHost));
-  return KSIM_OK;
-}
-
-int ksim_get_nb_alloc(ksim_handle* h, int64_t* out) {
-  if (!h || !h->has_cluster || !out) return set_err(h, KSIM_E_INVALID, "cluster not set / null out");
-  if (int rc = flush_idle(h)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hcopy(h, out, h->dc.nb_alloc, 8 * (size_t)h->dc.n, hipMemcpyDeviceToHost));
-  return KSIM_OK;
-}
-
-// A pod's KSIM_USE_VOLUME uses (host arrays, the ABI form).
-static bool has_volume_use(const ksim_pod_set* ps, int32_t i) {
-  if (!ps || !ps->pods || !ps->uses || i < 0 || i >= ps->n_pods) return false;
-  const ksim_pod& p = ps->pods[i];
-  if (p.use_first < 0 || p.use_count < 0 || (int64_t)p.use_first + p.use_count > ps->n_uses) return false;
-  for (int32_t k = 0; k < p.use_count; k++)
-    if (ps->uses[p.use_first + k].kind == KSIM_USE_VOLUME) return true;
-  return false;
-}
-
-int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* family_plugin, const int32_t* limit,
-                           const int32_t* attached) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "ksim_set_volume_limits before ksim_set_cluster");
-  if (is_sharded(h) || h->replicated || h->world > 1)
-    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_set_volume_limits on a shard or replicated handle");
-  if (n_families < 0 || n_families > KSIM_MAX_VOL_FAMILIES)
-    return set_err(h, KSIM_E_INVALID, "n_families out of range");
-  const size_t N = (size_t)h->dc.n;
-  if (n_families > 0 && (!family_plugin || (N > 0 && (!limit || !attached))))
-    return set_err(h, KSIM_E_INVALID, "null volume table");
-  uint32_t plug = 0;
-  for (int32_t f = 0; f < n_families; f++) {
-    if (family_plugin[f] < KSIM_PL_EBS_LIMITS || family_plugin[f] > KSIM_PL_AZURE_DISK_LIMITS)
-      return set_err(h, KSIM_E_INVALID, "family_plugin is not a volume limit plugin");
-    plug |= (uint32_t)(family_plugin[f] - KSIM_PL_EBS_LIMITS) << (4 * f);
-  }
-  for (size_t i = 0; i < N * (size_t)n_families; i++)
-    if (limit[i] < 0 || attached[i] < 0) return set_err(h, KSIM_E_INVALID, "negative volume limit / attached count");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  // the kernels take the cluster by value, and a pod's validation and plan
-  // depend on the table: captured graphs and the loaded queue go
-  drop_graphs(h);
-  h->dp = DevPods{};
-  h->batchable.clear();
-  free_bufs(h->vol_bufs);
-  free_bufs(h->pre_vol_bufs);           // the bound pods' holdings named the old table's families
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  h->vol_init = nullptr;
-  h->dc.vol_nf = 0;
-  h->dc.vol_plug = 0;
-  h->dc.vol_limit = nullptr;
-  h->dc.vol_attached = nullptr;
-  if (n_families == 0) return KSIM_OK;
-  const size_t bytes = 4 * N * (size_t)n_families;
-  void *dl = nullptr, *da = nullptr, *di = nullptr;
-  int rc;
-  if ((rc = upload(h, h->vol_bufs, limit, bytes, &dl)) || (rc = upload(h, h->vol_bufs, attached, bytes, &da)) ||
-      (rc = upload(h, h->vol_bufs, attached, bytes, &di))) {
-    free_bufs(h->vol_bufs);
-    return rc;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->dc.vol_nf = n_families;
-  h->dc.vol_plug = plug;
-  h->dc.vol_limit = (const int32_t*)dl;
-  h->dc.vol_attached = (int32_t*)da;
-  h->vol_init = (int32_t*)di;
-  return KSIM_OK;
-}
-
-int ksim_get_volume_attached(ksim_handle* h, int32_t* out) {
-  if (!h || !h->has_cluster || !out) return set_err(h, KSIM_E_INVALID, "cluster not set / null out");
-  if (!h->dc.vol_nf) return set_err(h, KSIM_E_INVALID, "no volume table (ksim_set_volume_limits)");
-  if (int rc = flush_idle(h)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hcopy(h, out, h->dc.vol_attached, 4 * (size_t)h->dc.n * h->dc.vol_nf, hipMemcpyDeviceToHost));
-  return KSIM_OK;
-}
-
-int ksim_get_class_count(ksim_handle* h, int32_t* out) {
-  if (!h || !h->has_cluster || !out) return set_err(h, KSIM_E_INVALID, "cluster not set / null out");
-  if (int rc = flush_idle(h)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->dc.n_classes)
-    HIPCHK(h, hcopy(h, out, h->dc.cnt, 4 * (size_t)h->dc.n * h->dc.n_classes, hipMemcpyDeviceToHost));
-  return KSIM_OK;
-}
-
-int ksim_get_next_start(ksim_handle* h, int32_t* next_start) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !next_start) return KSIM_E_INVALID;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hcopy(h, next_start, &h->st->next_start, 4, hipMemcpyDeviceToHost));
-  return KSIM_OK;
-}
-
-int ksim_set_next_start(ksim_handle* h, int32_t next_start) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h) return KSIM_E_INVALID;
-  if (h->has_cluster && (next_start < 0 || next_start >= std::max(h->dc.n, 1)))
-    return set_err(h, KSIM_E_INVALID, "next_start out of range");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hcopy(h, &h->st->next_start, &next_start, 4, hipMemcpyHostToDevice));
-  return KSIM_OK;
-}
-
-int ksim_set_pod_seq(ksim_handle* h, int64_t seq) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h) return KSIM_E_INVALID;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hcopy(h, &h->st->pod_seq, &seq, 8, hipMemcpyHostToDevice));
-  return KSIM_OK;
-}
-
 // Device copies of topology uses carry kUseUniqueCol when their key column is
 // unique per node (ksim_device.h use_node_count).
 // A KSIM_USE_VOLUME copy carries its family in _pad and no column, so nothing
@@ -3405,7 +2387,7 @@ static int arena_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
 
 // The handle's pinned staging (the stream must be idle: a copy from it may be
 // in flight otherwise).
-static int pin_reserve(ksim_handle* h, size_t bytes) {
+int ksim_host::pin_reserve(ksim_handle* h, size_t bytes) {
   if (bytes <= h->pin_cap) return KSIM_OK;
   if (h->pin) (void)hipHostFree(h->pin);
   h->pin = h->pin_d = nullptr;
@@ -3603,13 +2585,13 @@ static int upload_blob(ksim_handle* h, const PodBlob& b, DevArena& arena, DevPod
 }
 
 // Upload one pod (re-based) as a device pod set of its own.
-static int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena) {
+int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena) {
   PodBlob b;
   build_pod_blob(h, ps, pod_index, b);
   return upload_blob(h, b, arena, P);
 }
 
-static int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P) {
+int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P) {
   return upload_single(h, ps, pod_index, P, h->pod1_arena);
 }
 
@@ -4232,7 +3214,7 @@ static int apply_bind(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index,
 
 // the queued Unreserves, when no framework cycle sits between PreFilter and
 // Score (the state getters read the cache's view)
-static int flush_idle(ksim_handle* h) {
+int ksim_host::flush_idle(ksim_handle* h) {
   int rc = flush_pend_bind(h);
   if (rc) return rc;
   return (!h->fw_pending && !h->deferred_binds.empty()) ? flush_deferred_binds(h) : KSIM_OK;
@@ -4402,7 +3384,7 @@ static bool tbatch_conflict_ok(const ksim_topo_use& u) {
 // The zone-variant use of a topology batch pod (ksim_device.h TbVar), or -1:
 // its first DoNotSchedule spread use, read from a persistent table, keyed by a
 // column of at most kVarDom domains (value ids 1 .. col_nvals - 1).
-int32_t tbatch_vuse(const ksim_handle* h, const ksim_pod& p, const PodPlan& pl, const ksim_topo_use* U) {
+static int32_t tbatch_vuse(const ksim_handle* h, const ksim_pod& p, const PodPlan& pl, const ksim_topo_use* U) {
   if (!(pl.flags & kPlanPtab)) return -1;
   for (int32_t i = 0; i < p.use_count && i < KSIM_MAX_USES; i++) {
     const ksim_topo_use& u = U[i];
@@ -4424,7 +3406,7 @@ int32_t tbatch_vuse(const ksim_handle* h, const ksim_pod& p, const PodPlan& pl, 
 // use's column is the run's variant column vcol[i] (the first such use's;
 // -1: none), so the chain names its slot by where that pod lands.
 // uses: the queue's device use copies.
-void tbatch_runs(const ksim_pod_set* ps, const std::vector<ksim_topo_use>& uses,
+static void tbatch_runs(const ksim_pod_set* ps, const std::vector<ksim_topo_use>& uses,
                  const std::vector<uint8_t>& batchable, const std::vector<PodPlan>& plans, bool variants,
                  std::vector<int32_t>& tlen, std::vector<uint8_t>& cross, std::vector<int32_t>& vcol) {
   const int32_t n = ps->n_pods;
@@ -4517,13 +3499,13 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
   };
   if (!reuse) drop_queue(KSIM_OK);
   size_t next_buf = 0;
-  auto put = [&](const void* src, size_t nbytes, void** out) -> int {
-    if (!reuse) return upload(h, h->pod_bufs, src, nbytes, out);
+  auto put = [&](auto*& dst, const void* src, size_t nbytes) -> int {
+    if (!reuse) return dev_alloc(h, h->pod_bufs, dst, nbytes, src);
     DevBuf& b = h->pod_bufs[next_buf++];
     const hipError_t e = (src && nbytes) ? hipMemcpyAsync(b.p, src, nbytes, hipMemcpyHostToDevice, h->stream)
                                          : hipMemsetAsync(b.p, 0, b.bytes, h->stream);
     if (e != hipSuccess) return hip_fail(h, e, "pod upload");
-    *out = b.p;
+    dst = (typename std::remove_reference<decltype(dst)>::type)b.p;
     return KSIM_OK;
   };
   std::vector<int32_t> bf(np1, 0);
@@ -4646,50 +3628,37 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
     plans[i].flags |= (uint32_t)(tvcol[(size_t)i] + 1) << kPlanVcolShift;
   }
   DevPods P{};
-  void* p = nullptr;
-  if ((rc = put(ps->pods, sizeof(ksim_pod) * ps->n_pods, &p))) return drop_queue(rc);
-  P.pods = (const ksim_pod*)p;
-  if ((rc = put(ps->exprs, sizeof(ksim_label_expr) * ps->n_exprs, &p))) return drop_queue(rc);
-  P.exprs = (const ksim_label_expr*)p;
-  if ((rc = put(ps->terms, sizeof(ksim_term) * ps->n_terms, &p))) return drop_queue(rc);
-  P.terms = (const ksim_term*)p;
-  if ((rc = put(ps->nn, 4 * (size_t)ps->n_nn, &p))) return drop_queue(rc);
-  P.nn = (const int32_t*)p;
-  if ((rc = put(bf.data(), 4 * bf.size(), &p))) return drop_queue(rc);
-  P.bflags = (const int32_t*)p;
-  if ((rc = put(uses.data(), sizeof(ksim_topo_use) * uses.size(), &p))) return drop_queue(rc);
-  P.uses = (const ksim_topo_use*)p;
-  if ((rc = put(plans.data(), sizeof(PodPlan) * plans.size(), &p))) return drop_queue(rc);
-  P.plans = (const PodPlan*)p;
-  if ((rc = put(ps->adds, sizeof(ksim_class_add) * (size_t)ps->n_adds, &p))) return drop_queue(rc);
-  P.adds = (const ksim_class_add*)p;
-  if ((rc = put(scls.data(), 4 * np1, &p))) return drop_queue(rc);
-  h->d_sclass = (int32_t*)p;
-  if ((rc = put(srep.data(), 4 * np1, &p))) return drop_queue(rc);
-  h->d_srep = (int32_t*)p;
+  if ((rc = put(P.pods, ps->pods, sizeof(ksim_pod) * ps->n_pods)) ||
+      (rc = put(P.exprs, ps->exprs, sizeof(ksim_label_expr) * ps->n_exprs)) ||
+      (rc = put(P.terms, ps->terms, sizeof(ksim_term) * ps->n_terms)) ||
+      (rc = put(P.nn, ps->nn, 4 * (size_t)ps->n_nn)) ||
+      (rc = put(P.bflags, bf.data(), 4 * bf.size())) ||
+      (rc = put(P.uses, uses.data(), sizeof(ksim_topo_use) * uses.size())) ||
+      (rc = put(P.plans, plans.data(), sizeof(PodPlan) * plans.size())) ||
+      (rc = put(P.adds, ps->adds, sizeof(ksim_class_add) * (size_t)ps->n_adds)) ||
+      (rc = put(h->d_sclass, scls.data(), 4 * np1)) ||
+      (rc = put(h->d_srep, srep.data(), 4 * np1)))
+    return drop_queue(rc);
   h->stab_ncls = ncls;
   h->sclass.assign(scls.begin(), scls.begin() + ps->n_pods);
   h->stab_dirty = true;
   h->d_rcls = nullptr;
   h->rq_ncls = 0;
-  if ((rc = put(rcls.data(), 2 * np1, &p))) return drop_queue(rc);
-  uint16_t* const d_rcls = (uint16_t*)p;
-  if ((rc = put(rreq.data(), sizeof(PodReq) * rreq.size(), &p))) return drop_queue(rc);
-  h->d_rreq = (PodReq*)p;
+  uint16_t* d_rcls = nullptr;
+  if ((rc = put(d_rcls, rcls.data(), 2 * np1)) ||
+      (rc = put(h->d_rreq, rreq.data(), sizeof(PodReq) * rreq.size())))
+    return drop_queue(rc);
   h->d_rcls = d_rcls;
   h->rq_cls.assign(rcls.begin(), rcls.begin() + ps->n_pods);
   h->rq_ncls = n_rcls;
-  if ((rc = put(R.ent.data(), sizeof(int4) * R.ent.size(), &p))) return drop_queue(rc);
-  P.ptab_ent = (const int4*)p;
-  if ((rc = put(R.cfirst.data(), 4 * R.cfirst.size(), &p))) return drop_queue(rc);
-  P.ptab_cfirst = R.cfirst.empty() ? nullptr : (const int32_t*)p;
-  if ((rc = put(R.cidx.data(), 4 * R.cidx.size(), &p))) return drop_queue(rc);
-  P.ptab_cidx = (const int32_t*)p;
-  if ((rc = put(nullptr, 8 * (size_t)R.len, &p))) return drop_queue(rc);   // filled by k_ptab_init
-  P.ptab = (int64_t*)p;
+  if ((rc = put(P.ptab_ent, R.ent.data(), sizeof(int4) * R.ent.size())) ||
+      (rc = put(P.ptab_cfirst, R.cfirst.data(), 4 * R.cfirst.size())) ||
+      (rc = put(P.ptab_cidx, R.cidx.data(), 4 * R.cidx.size())) ||
+      (rc = put(P.ptab, nullptr, 8 * (size_t)R.len)) ||   // filled by k_ptab_init
+      (rc = put(P.ptab_padd, R.padd.data(), sizeof(int4) * R.padd.size())))
+    return drop_queue(rc);
+  if (R.cfirst.empty()) P.ptab_cfirst = nullptr;
   P.n_ptab = (int32_t)R.ent.size();
-  if ((rc = put(R.padd.data(), sizeof(int4) * R.padd.size(), &p))) return drop_queue(rc);
-  P.ptab_padd = (const int4*)p;
   P.n_uses = ps->n_uses;
   P.n_adds = ps->n_adds;
   P.n_nn = ps->n_nn;
@@ -4973,43 +3942,6 @@ int ksim_schedule_batch(ksim_handle* h, const ksim_pod_set* ps, int32_t* chosen,
   return ksim_schedule_loaded(h, 0, ps->n_pods, chosen, stats);
 }
 
-int ksim_reset_cluster(ksim_handle* h) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !h->has_cluster) return set_err(h, KSIM_E_INVALID, "cluster not set");
-  // the static table stays: k_static_table reads a node's flags, taints and
-  // labels (static_filters_pass, count_intolerable_prefer, pref_term_mask),
-  // none of the columns restored here
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t N = (size_t)h->dc.n;
-  const DevCluster& c = h->dc;
-  // the dynamic columns from their snapshot copies and the run state zeroed,
-  // in one launch (every buffer is a hipMalloc allocation: 16-byte aligned)
-  ResetList L;
-  hipError_t fe = hipSuccess;
-  auto put = [&](void* d, const void* s, size_t bytes) {   // an entry the launch cannot take: its own copy
-    if (L.add(d, s, bytes) || fe != hipSuccess) return;
-    fe = s ? hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, h->stream) : hipMemsetAsync(d, 0, bytes, h->stream);
-  };
-  put(c.req_cpu, h->init.req_cpu, 8 * N);
-  put(c.req_mem, h->init.req_mem, 8 * N);
-  put(c.req_eph, h->init.req_eph, 8 * N);
-  if (c.n_scalar) put(c.req_scalar, h->init.req_scalar, 8 * N * c.n_scalar);
-  put(c.nz_cpu, h->init.nz_cpu, 8 * N);
-  put(c.nz_mem, h->init.nz_mem, 8 * N);
-  put(c.num_pods, h->init.num_pods, 4 * N);
-  if (c.n_classes) put(c.cnt, h->init.cnt, 4 * N * c.n_classes);
-  put(c.nb_alloc, h->init.nb_alloc, 8 * N);
-  if (c.vol_nf) put(c.vol_attached, h->vol_init, 4 * N * c.vol_nf);
-  static_assert(sizeof(DevState) % 4 == 0, "DevState by words");
-  put(h->st, nullptr, sizeof(DevState));
-  HIPCHK(h, fe);
-  if (L.n) launch_reset_copy(L, h->stream);
-  launch_ptab_init(h->dc, h->dp, h->stream);        // the queue's persistent tables follow the counts
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return KSIM_OK;
-}
-
 int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, int32_t* kernel) {
   int rc = ensure_ready(h);
   if (rc) return rc;
@@ -5214,8 +4146,6 @@ int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_
   return kKinds;
 }
 
-}  // extern "C"
-
 extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   if (!h || !out || n < 0) return KSIM_E_INVALID;
   DevState st;
@@ -5255,568 +4185,4 @@ extern "C" int ksim_batch_geometry(int32_t* out, int32_t n) {
   const int32_t m = n < 4 ? n : 4;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
-}
-
-
-// ---- PostFilter: DefaultPreemption (ksim_preempt.hip) ------------------------------
-extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
-  int rc = ensure_ready(h);
-  if (rc) return rc;
-  if (!b || b->n < 0 || (b->n > 0 && (!b->node || !b->priority || !b->start_time || !b->req)))
-    return set_err(h, KSIM_E_INVALID, "bad bound-pod table");
-  const int32_t N = h->dc.n, n = b->n;
-  for (int32_t i = 0; i < n; i++)
-    if (b->node[i] < 0 || b->node[i] >= N) return set_err(h, KSIM_E_INVALID, "bound pod on a node out of range");
-  // per node, util.MoreImportantPod order (priority desc, start asc), then table order
-  std::vector<int32_t> ix((size_t)n);
-  for (int32_t i = 0; i < n; i++) ix[i] = i;
-  std::sort(ix.begin(), ix.end(), [&](int32_t x, int32_t y) {
-    if (b->node[x] != b->node[y]) return b->node[x] < b->node[y];
-    if (b->priority[x] != b->priority[y]) return b->priority[x] > b->priority[y];
-    if (b->start_time[x] != b->start_time[y]) return b->start_time[x] < b->start_time[y];
-    return x < y;
-  });
-  std::vector<int32_t> off((size_t)N + 1, 0), prio((size_t)std::max(n, 1));
-  std::vector<int64_t> start((size_t)std::max(n, 1)), req((size_t)std::max(n, 1) * KSIM_PREEMPT_REQ);
-  for (int32_t i = 0; i < n; i++) off[b->node[i] + 1]++;
-  for (int32_t v = 0; v < N; v++) off[v + 1] += off[v];
-  for (int32_t k = 0; k < n; k++) {
-    const int32_t i = ix[k];
-    prio[k] = b->priority[i];
-    start[k] = b->start_time[i];
-    for (int q = 0; q < KSIM_PREEMPT_REQ; q++) req[(size_t)k * KSIM_PREEMPT_REQ + q] = b->req[(size_t)i * KSIM_PREEMPT_REQ + q];
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  free_bufs(h->pre_bufs);
-  free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
-  free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
-  free_bufs(h->pre_vol_bufs);                  // and the volume holdings
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  DevPreempt d{};
-  void* p = nullptr;
-  if ((rc = upload(h, h->pre_bufs, off.data(), 4 * off.size(), &p))) return rc;
-  d.off = (const int32_t*)p;
-  if ((rc = upload(h, h->pre_bufs, prio.data(), 4 * prio.size(), &p))) return rc;
-  d.prio = (const int32_t*)p;
-  if ((rc = upload(h, h->pre_bufs, start.data(), 8 * start.size(), &p))) return rc;
-  d.start = (const int64_t*)p;
-  if ((rc = upload(h, h->pre_bufs, req.data(), 8 * req.size(), &p))) return rc;
-  d.req = (const int64_t*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, (size_t)std::max(n, 1), &p))) return rc;
-  d.vflag = (uint8_t*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, sizeof(PreemptNode) * (size_t)N, &p))) return rc;
-  d.res = (PreemptNode*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, 32, &p))) return rc;
-  d.pick = (int32_t*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, 4 * (size_t)std::max(N, 1), &p))) return rc;
-  d.nslot = (int32_t*)p;
-  HIPCHK(h, hipMemsetAsync(d.nslot, 0xff, 4 * (size_t)std::max(N, 1), h->stream));   // -1: no group
-  d.nreq = nullptr;
-  if ((rc = upload(h, h->pre_bufs, nullptr, 8 * (size_t)KSIM_MAX_USES, &p))) return rc;
-  d.afftot = (int64_t*)p;
-  if ((rc = upload(h, h->pre_bufs, nullptr, 8 * 3 * (size_t)KSIM_MAX_USES, &p))) return rc;
-  h->pre_smin = (int64_t*)p;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->pre = d;
-  h->pre_index = ix;
-  h->pre_n = n;
-  return KSIM_OK;
-}
-
-extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds) {
-  if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: ksim_set_bound_pods first");
-  const int32_t n = h->pre_n;
-  if (!off || off[0] < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: bad offsets");
-  for (int32_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: offsets not monotone");
-  if (off[n] > off[0] && !adds) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: adds missing");
-  for (int32_t e = off[0]; e < off[n]; e++)
-    if (adds[e].cls < 0 || adds[e].cls >= h->dc.n_classes)
-      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: class out of range");
-  // into the table's per-node importance order (CSR position k = caller row pre_index[k])
-  std::vector<int32_t> aoff((size_t)n + 1, 0);
-  std::vector<ksim_class_add> perm;
-  perm.reserve((size_t)(off[n] - off[0]));
-  for (int32_t k = 0; k < n; k++) {
-    const int32_t i = h->pre_index[k];
-    if (off[i + 1] > off[i]) perm.insert(perm.end(), adds + off[i], adds + off[i + 1]);
-    aoff[(size_t)k + 1] = (int32_t)perm.size();
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  free_bufs(h->pre_add_bufs);                   // every dry run ends synchronized: nothing reads them
-  h->pre.aoff = nullptr;
-  h->pre.adds = nullptr;
-  int rc;
-  void *po = nullptr, *pa = nullptr;
-  if ((rc = upload(h, h->pre_add_bufs, aoff.data(), 4 * aoff.size(), &po))) return rc;
-  if ((rc = upload(h, h->pre_add_bufs, perm.data(), sizeof(ksim_class_add) * perm.size(), &pa))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
-  h->pre.aoff = (const int32_t*)po;
-  h->pre.adds = (const ksim_class_add*)pa;
-  return KSIM_OK;
-}
-
-extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
-                                       const int32_t* ids) {
-  if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ksim_set_bound_pods first");
-  if (n_pdbs < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: negative budget count");
-  const int32_t n = h->pre_n;
-  std::vector<int32_t> poff((size_t)n + 1, 0), perm;
-  if (n_pdbs > 0) {
-    if (!allowed || !off || off[0] != 0)
-      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: bad offsets (they start at 0)");
-    for (int32_t i = 0; i < n; i++)
-      if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: offsets not monotone");
-    if (off[n] > 0 && !ids) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ids missing");
-    std::vector<int32_t> last((size_t)n_pdbs, -1);   // the last row that named the budget
-    for (int32_t i = 0; i < n; i++)
-      for (int32_t e = off[i]; e < off[i + 1]; e++) {
-        if (ids[e] < 0 || ids[e] >= n_pdbs)
-          return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: budget id out of range");
-        if (last[ids[e]] == i) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: a budget twice in one row");
-        last[ids[e]] = i;
-      }
-    // into the table's per-node importance order (CSR position k = caller row pre_index[k])
-    perm.reserve((size_t)off[n]);
-    for (int32_t k = 0; k < n; k++) {
-      const int32_t i = h->pre_index[k];
-      if (off[i + 1] > off[i]) perm.insert(perm.end(), ids + off[i], ids + off[i + 1]);
-      poff[(size_t)k + 1] = (int32_t)perm.size();
-    }
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  free_bufs(h->pre_pdb_bufs);                   // every dry run ends synchronized: nothing reads them
-  h->pre.poff = h->pre.pids = h->pre.pallowed = nullptr;
-  if (n_pdbs == 0) return KSIM_OK;              // cleared: the dry run takes the forms without budgets
-  int rc;
-  void *po = nullptr, *pi = nullptr, *pa = nullptr;
-  if ((rc = upload(h, h->pre_pdb_bufs, poff.data(), 4 * poff.size(), &po))) return rc;
-  if ((rc = upload(h, h->pre_pdb_bufs, perm.data(), 4 * perm.size(), &pi))) return rc;
-  if ((rc = upload(h, h->pre_pdb_bufs, allowed, 4 * (size_t)n_pdbs, &pa))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
-  h->pre.poff = (const int32_t*)po;
-  h->pre.pids = (const int32_t*)pi;
-  h->pre.pallowed = (const int32_t*)pa;
-  return KSIM_OK;
-}
-
-extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses) {
-  if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: ksim_set_bound_pods first");
-  if (!h->dc.vol_nf)
-    return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: no volume table (ksim_set_volume_limits)");
-  const int32_t n = h->pre_n;
-  if (!off || off[0] < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad offsets");
-  for (int32_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: offsets not monotone");
-  if (off[n] > off[0] && !uses) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: uses missing");
-  for (int32_t e = off[0]; e < off[n]; e++) {
-    const ksim_topo_use& u = uses[e];
-    if (u.kind != KSIM_USE_VOLUME)
-      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: a use that is no KSIM_USE_VOLUME");
-    if (u.col >= h->dc.vol_nf) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: family out of range");
-    if (u.cls < -1 || u.cls >= h->dc.n_classes)
-      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: class out of range");
-    if (u.cls < 0 ? u.arg < 1 : u.arg != 1)
-      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad volume use count");
-  }
-  // into the table's per-node importance order (CSR position k = caller row pre_index[k])
-  std::vector<int32_t> voff((size_t)n + 1, 0);
-  std::vector<VolHold> perm;
-  perm.reserve((size_t)(off[n] - off[0]));
-  for (int32_t k = 0; k < n; k++) {
-    const int32_t i = h->pre_index[k];
-    for (int32_t e = off[i]; e < off[i + 1]; e++) perm.push_back({uses[e].cls, (int32_t)uses[e].col, uses[e].arg});
-    voff[(size_t)k + 1] = (int32_t)perm.size();
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  free_bufs(h->pre_vol_bufs);                   // every dry run ends synchronized: nothing reads them
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  int rc;
-  void *po = nullptr, *pv = nullptr;
-  if ((rc = upload(h, h->pre_vol_bufs, voff.data(), 4 * voff.size(), &po))) return rc;
-  if ((rc = upload(h, h->pre_vol_bufs, perm.data(), sizeof(VolHold) * perm.size(), &pv))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
-  h->pre_voff = (const int32_t*)po;
-  h->pre_vols = (const VolHold*)pv;
-  return KSIM_OK;
-}
-
-extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                            ksim_preempt_out* out) {
-  return ksim_preempt_nominated(h, ps, pod_index, priority, nullptr, 0, nullptr, nullptr, nullptr, out);
-}
-
-// The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
-// DoNotSchedule spread uses are refused), ksim_preempt_spread and
-// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted) and
-// ksim_preempt_full (full = true: every mix of uses is accepted, and a
-// preemptor with volume groups has VolumeBinding / VolumeZone re-run).
-static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
-                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false,
-                       bool full = false) {
-  int rc = ensure_ready(h);
-  if (rc) return rc;
-  if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
-    return set_err(h, KSIM_E_INVALID, "bad pod set / index");
-  if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
-    return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
-  const bool vol_form = has_volume_use(ps, pod_index);   // the volume form of k_preempt_nodes
-  if (vol_form && !volumes && !full)
-    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
-                                          "re-run the node volume limit plugins)");
-  {
-    std::vector<uint8_t> seen((size_t)std::max(h->dc.n, 1), 0);
-    for (int32_t k = 0; k < n_groups; k++) {
-      if (gnodes[k] < 0 || gnodes[k] >= h->dc.n || seen[gnodes[k]])
-        return set_err(h, KSIM_E_INVALID, "nominated node out of range or repeated");
-      seen[gnodes[k]] = 1;
-      if (count[k] < 0 || first[k] < 0 || first[k] + count[k] > nps->n_pods)
-        return set_err(h, KSIM_E_INVALID, "nominated pod range out of the pod set");
-      for (int32_t j = first[k]; j < first[k] + count[k]; j++)
-        if ((rc = validate_pod(h, nps, j))) return rc;
-    }
-  }
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pods first");
-  if (is_sharded(h)) return set_err(h, KSIM_E_UNSUPPORTED, "preemption runs on unsharded handles");
-  if (prof_has_filter(h->prof, KSIM_PL_NETWORK_BANDWIDTH))
-    return set_err(h, KSIM_E_UNSUPPORTED, "preemption dry runs re-run Fit only, not NetworkBandwidth");
-  if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
-    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
-  if ((rc = validate_pod(h, ps, pod_index))) return rc;
-  int32_t fit = -1, port = -1, ipa = -1, pts = -1;
-  for (int f = 0; f < h->prof.n_filter; f++) {
-    if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
-    if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
-    if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) ipa = f;
-    if (h->prof.filter[f] == KSIM_PL_POD_TOPOLOGY_SPREAD) pts = f;
-  }
-  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity and,
-  // through ksim_preempt_spread, PodTopologySpread.  Uses that no Filter reads
-  // (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
-  // ignored; the two older entry points refuse DoNotSchedule spread (their
-  // callers fall back on that code).
-  const ksim_pod& pp = ps->pods[pod_index];
-  const bool topo = pp.use_count > 0;
-  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
-  for (int32_t k = 0; k < pp.use_count && vol_form && !full; k++) {
-    const uint8_t kind = ps->uses[pp.use_first + k].kind;
-    static const char* const kNames[] = {"KSIM_USE_PTS_HARD", nullptr, "KSIM_USE_IPA_EXISTING_ANTI",
-                                         "KSIM_USE_IPA_AFFINITY", "KSIM_USE_IPA_ANTI"};
-    if (kind <= KSIM_USE_IPA_ANTI && kNames[kind])
-      return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_VOLUME use and a ") +
-                                                kNames[kind] + " use (the volume form moves no domain counts)");
-  }
-  for (int32_t k = 0; k < pp.use_count && !spread && !full; k++)
-    if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
-      return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
-                                            "victims' domains: ksim_preempt_spread)");
-  for (int32_t k = 0; k < pp.use_count; k++) {
-    const uint8_t kind = ps->uses[pp.use_first + k].kind;
-    if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_AFFINITY && ipa >= 0) aff_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_ANTI && ipa >= 0) anti_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_EXISTING_ANTI && ipa >= 0) exist_mask |= 1u << k;
-    if (kind == KSIM_USE_PTS_HARD && pts >= 0) hard_mask |= 1u << k;
-  }
-  // the domain form of k_preempt_nodes (the spread form is one: it reads the same row)
-  const bool dom_form = (aff_mask | anti_mask | exist_mask | hard_mask) != 0;
-  if (hard_mask && !h->pre.aoff)
-    return set_err(h, KSIM_E_INVALID, "ksim_preempt_spread for a pod with DoNotSchedule spread: "
-                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
-  if (port_mask && !dom_form && !h->pre.aoff)
-    return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
-                                      "(after ksim_set_bound_pods)");
-  if (vol_form && !h->pre_voff)
-    return set_err(h, KSIM_E_INVALID, "preemption for a pod with a KSIM_USE_VOLUME use: ksim_set_bound_pod_volumes "
-                                      "first (after ksim_set_bound_pods)");
-  // what the profile's limit plugins read of the pod (validate_pod checked the families)
-  PreemptVol vm{};
-  vm.at = 0xffffffffu;
-  if (vol_form) {
-    for (int f = 0; f < h->prof.n_filter; f++) {
-      const int32_t k = h->prof.filter[f] - KSIM_PL_EBS_LIMITS;
-      if (k >= 0 && k < 4) vm.at = (vm.at & ~(255u << (8 * k))) | ((uint32_t)f << (8 * k));
-    }
-    for (int32_t k = 0; k < pp.use_count; k++) {
-      const ksim_topo_use& u = ps->uses[pp.use_first + k];
-      if (u.kind != KSIM_USE_VOLUME) continue;
-      const uint32_t pl = (h->dc.vol_plug >> (4 * u.col)) & 15u;
-      if (((vm.at >> (8 * pl)) & 255u) == 255u) continue;   // its plugin is not in the filter list
-      vm.uses |= 1u << k;
-      vm.fams |= 1u << u.col;
-      if (pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS)) vm.csi |= 1u << u.col;
-    }
-  }
-  if (dom_form && !h->pre.aoff)
-    return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
-                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
-  HIPCHK(h, hipSetDevice(h->device));
-  DevPods P;
-  if ((rc = upload_single(h, ps, pod_index, P))) return rc;
-  if ((rc = set_run(h, 0, 1))) return rc;
-  const LaunchArgs a = make_args(h, P, nullptr);
-  DevPreempt pre = h->pre;
-  // The status pass: the per-pod cycle's filter phase.  For a pod with uses its
-  // PreFilter pass runs first; the domain tables and topology flags it fills
-  // are zero between cycles (k_select / k_bind re-zero them in a whole cycle).
-  // keep: the domain form of k_preempt_nodes reads the last pass's tables, so
-  // the caller re-zeroes them after that kernel.
-  auto rezero = [&]() -> int {
-    if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
-    HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
-    return KSIM_OK;
-  };
-  auto filter_pass = [&](bool keep = false) -> int {
-    launch_filter_only(a, h->stream, topo);
-    HIPCHK(h, hipGetLastError());
-    return topo && !keep ? rezero() : KSIM_OK;
-  };
-  std::vector<uint8_t> gfail((size_t)std::max(n_groups, 1), KSIM_PASSED);
-  std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
-  std::vector<int32_t> goff((size_t)n_groups + 1, 0);    // the groups' class contributions (CSR)
-  std::vector<ksim_class_add> gadds;
-  std::vector<int32_t> gvoff((size_t)n_groups + 1, 0);   // and their volume holdings, for the volume form
-  std::vector<VolHold> gvols;
-  auto bind_group = [&](int32_t k, int sign) -> int {
-    for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
-      DevPods Q;
-      int r;
-      if ((r = upload_single(h, nps, j, Q, h->nom_arena))) return r;
-      launch_assume(h->dc, Q, 0, gnodes[k], sign, h->stream);
-      HIPCHK(h, hipGetLastError());
-    }
-    return KSIM_OK;
-  };
-  for (int32_t k = 0; k < n_groups; k++) {                // pass 1 of each grouped node
-    if ((rc = bind_group(k, 1))) return rc;
-    if ((rc = filter_pass())) return rc;
-    HIPCHK(h, hcopy(h, &gfail[k], h->sc.fail + gnodes[k], 1, hipMemcpyDeviceToHost));
-    if ((rc = bind_group(k, -1))) return rc;
-    int64_t* q = nreq.data() + (size_t)k * (KSIM_PREEMPT_REQ + 1);
-    for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
-      const ksim_pod& x = nps->pods[j];
-      q[0] += x.req_cpu;
-      q[1] += x.req_mem;
-      q[2] += x.req_eph;
-      for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
-      if ((port_mask || dom_form) && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
-      for (int32_t e = 0; e < x.use_count && vol_form; e++) {
-        const ksim_topo_use& u = nps->uses[x.use_first + e];
-        if (u.kind == KSIM_USE_VOLUME) gvols.push_back({u.cls, (int32_t)u.col, u.arg});
-      }
-    }
-    q[KSIM_PREEMPT_REQ] = count[k];
-    goff[(size_t)k + 1] = (int32_t)gadds.size();
-    gvoff[(size_t)k + 1] = (int32_t)gvols.size();
-  }
-  if (n_groups > 0) {
-    free_bufs(h->pre_nom_bufs);
-    void* p = nullptr;
-    if ((rc = upload(h, h->pre_nom_bufs, nreq.data(), 8 * nreq.size(), &p))) return rc;
-    pre.nreq = (const int64_t*)p;
-    if (port_mask || dom_form) {                           // the groups' holdings stay on their nodes too
-      if ((rc = upload(h, h->pre_nom_bufs, goff.data(), 4 * goff.size(), &p))) return rc;
-      pre.goff = (const int32_t*)p;
-      if ((rc = upload(h, h->pre_nom_bufs, gadds.data(), sizeof(ksim_class_add) * gadds.size(), &p))) return rc;
-      pre.gadds = (const ksim_class_add*)p;
-    }
-    if (vol_form) {
-      if ((rc = upload(h, h->pre_nom_bufs, gvoff.data(), 4 * gvoff.size(), &p))) return rc;
-      vm.gvoff = (const int32_t*)p;
-      if ((rc = upload(h, h->pre_nom_bufs, gvols.data(), sizeof(VolHold) * gvols.size(), &p))) return rc;
-      vm.gvols = (const VolHold*)p;
-    }
-  }
-  if ((rc = filter_pass(dom_form))) return rc;             // every node as is
-  if (n_groups > 0) {
-    for (int32_t k = 0; k < n_groups; k++) {
-      // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
-      if (gfail[k] != KSIM_PASSED) {
-        gfail[k] &= (uint8_t)~kFailError;
-        HIPCHK(h, hipMemcpyAsync(h->sc.fail + gnodes[k], &gfail[k], 1, hipMemcpyHostToDevice, h->stream));
-      }
-      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &k, 4, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
-    }
-  }
-  // ksim_preempt_full: the static volume filters of a preemptor with groups
-  const bool vb = full && pp.vb_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_BINDING);
-  const bool vz = full && pp.vz_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_ZONE);
-  vm.voff = h->pre_voff;
-  vm.vols = h->pre_vols;
-  if (vol_form && dom_form && vm.uses) {                   // only ksim_preempt_full gets here: the full form
-    launch_preempt_full(a, pre, fit, priority, h->stream, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
-                        hard_mask, h->pre_smin, vm, vb, vz);
-  } else {
-    if (vol_form && !dom_form)
-      launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
-    else
-      launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask,
-                     pts, hard_mask, h->pre_smin);
-    if (vb || vz) launch_preempt_veto(a, pre, h->stream, vb, vz);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
-  if (n_groups > 0) {
-    static const int32_t kNoGroup = -1;
-    for (int32_t k = 0; k < n_groups; k++)
-      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &kNoGroup, 4, hipMemcpyHostToDevice, h->stream));
-  }
-  int32_t pick[5];
-  HIPCHK(h, hipMemcpyAsync(pick, h->pre.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  out->nominated = pick[0];
-  out->n_victims = pick[1];
-  out->n_potential = pick[2];
-  out->n_candidates = pick[3];
-  out->n_pdb_violations = pick[4];
-  if (pick[0] >= 0 && out->victims && out->victims_cap > 0) {
-    std::vector<int32_t> off(2);
-    HIPCHK(h, hcopy(h, off.data(), h->pre.off + pick[0], 8, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
-    if (off[1] > off[0])
-      HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
-    // the dry run's list order: the victims violating a PDB, then the others, each in CSR order
-    int32_t k = 0;
-    for (const uint8_t want : {(uint8_t)(1 | kPreemptViolating), (uint8_t)1})
-      for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
-        if (flag[j - off[0]] == want) out->victims[k++] = h->pre_index[j];
-  }
-  return KSIM_OK;
-}
-
-extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                                      const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
-                                      const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false);
-}
-
-extern "C" int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                                    const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
-                                    const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false, true);
-}
-
-extern "C" int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                                 const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
-                                 const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true, true, true);
-}
-
-extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                                   const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
-                                   const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true);
-}
-
-// ---- selector / affinity-term matching (ksim_match.hip) ------
-extern "C" int ksim_match_terms(ksim_handle* h, const ksim_match_problem* mp, uint32_t* match_bits, int32_t* counts) {
-  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
-  if (!h || !mp || !match_bits) return set_err(h, KSIM_E_INVALID, "null argument");
-  const ksim_match_problem& q = *mp;
-  if (q.n_sigs < 0 || q.n_feat < 0 || q.n_reqs < 0 || q.n_matchers < 0 || q.n_pods < 0 || q.n_nodes < 0 ||
-      q.n_classes < 0)
-    return set_err(h, KSIM_E_INVALID, "negative size");
-  if (q.n_reqs > kMatchMaxReqs || q.n_feat > kMatchMaxFeat)
-    return set_err(h, KSIM_E_UNSUPPORTED, "match problem exceeds 4096 requirements or 65536 features");
-  if (q.n_classes > 0 && !counts) return set_err(h, KSIM_E_INVALID, "counts buffer missing");
-  if (!q.sig_feat_off || !q.req_feat_off || (!q.req_neg && q.n_reqs > 0) || !q.m_req_off)
-    return set_err(h, KSIM_E_INVALID, "null CSR");
-  // host validation: every index the kernels follow is in range
-  auto csr_ok = [](const int32_t* off, int32_t rows, const int32_t* v, int32_t bound) {
-    if (off[0] != 0) return false;
-    for (int32_t i = 0; i < rows; i++)
-      if (off[i + 1] < off[i]) return false;
-    if (off[rows] > 0 && !v) return false;
-    for (int32_t j = 0; j < off[rows]; j++)
-      if (v[j] < 0 || v[j] >= bound) return false;
-    return true;
-  };
-  if (!csr_ok(q.sig_feat_off, q.n_sigs, q.sig_feat, q.n_feat) ||
-      !csr_ok(q.req_feat_off, q.n_reqs, q.req_feat, q.n_feat) ||
-      !csr_ok(q.m_req_off, q.n_matchers, q.m_req, q.n_reqs))
-    return set_err(h, KSIM_E_INVALID, "feature / requirement index out of range");
-  if (q.n_classes > 0) {
-    if (!q.class_matcher) return set_err(h, KSIM_E_INVALID, "class_matcher missing");
-    for (int32_t c = 0; c < q.n_classes; c++)
-      if (q.class_matcher[c] < 0 || q.class_matcher[c] >= q.n_matchers)
-        return set_err(h, KSIM_E_INVALID, "class matcher out of range");
-    if (q.n_pods > 0 && (!q.pod_sig || !q.pod_node)) return set_err(h, KSIM_E_INVALID, "bound pod arrays missing");
-    for (int32_t p = 0; p < q.n_pods; p++)
-      if (q.pod_sig[p] < 0 || q.pod_sig[p] >= q.n_sigs || q.pod_node[p] < 0 || q.pod_node[p] >= q.n_nodes)
-        return set_err(h, KSIM_E_INVALID, "bound pod signature / node out of range");
-  }
-  if (q.n_sigs == 0) {                         // no signature: no bound pod either (pod_sig < n_sigs)
-    if (q.n_classes > 0 && q.n_nodes > 0) std::memset(counts, 0, (size_t)q.n_classes * q.n_nodes * 4);
-    return KSIM_OK;
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  DevMatch m{};
-  m.s = q.n_sigs;
-  m.sp = (q.n_sigs + 15) / 16 * 16;
-  m.fp = std::max(64, (q.n_feat + 63) / 64 * 64);
-  m.r = q.n_reqs;
-  m.rp = std::max(16, (q.n_reqs + 15) / 16 * 16);
-  m.m = q.n_matchers;
-  m.w = (q.n_matchers + 31) / 32;
-  m.c = q.n_classes;
-  m.cw = (q.n_classes + 31) / 32;
-  m.p = q.n_classes > 0 ? q.n_pods : 0;
-  m.n = q.n_nodes;
-  std::vector<DevBuf> bufs;
-  struct Guard {
-    std::vector<DevBuf>& b;
-    ~Guard() { free_bufs(b); }
-  } guard{bufs};
-  int rc;
-  void* p;
-  std::vector<uint8_t> neg((size_t)m.rp, 0);
-  std::copy(q.req_neg, q.req_neg + q.n_reqs, neg.begin());
-  if ((rc = upload(h, bufs, nullptr, (size_t)m.sp * m.fp, &p))) return rc;
-  m.a = (int8_t*)p;
-  if ((rc = upload(h, bufs, nullptr, (size_t)m.rp * m.fp, &p))) return rc;
-  m.bt = (int8_t*)p;
-  if ((rc = upload(h, bufs, neg.data(), neg.size(), &p))) return rc;
-  m.neg = (uint8_t*)p;
-  auto put = [&](const int32_t* src, int64_t n, const int32_t** dst) {
-    void* d;
-    int r = upload(h, bufs, src, (size_t)std::max<int64_t>(n, 0) * 4, &d);
-    *dst = (const int32_t*)d;
-    return r;
-  };
-  if ((rc = put(q.sig_feat_off, q.n_sigs + 1, &m.sig_off)) || (rc = put(q.sig_feat, q.sig_feat_off[q.n_sigs], &m.sig_feat)) ||
-      (rc = put(q.req_feat_off, q.n_reqs + 1, &m.req_off)) || (rc = put(q.req_feat, q.req_feat_off[q.n_reqs], &m.req_feat)) ||
-      (rc = put(q.m_req_off, q.n_matchers + 1, &m.m_off)) || (rc = put(q.m_req, q.m_req_off[q.n_matchers], &m.m_req)))
-    return rc;
-  if ((rc = upload(h, bufs, nullptr, (size_t)m.s * std::max(m.w, 1) * 4, &p))) return rc;
-  m.bits = (uint32_t*)p;
-  if (m.c > 0) {
-    if ((rc = put(q.class_matcher, m.c, &m.cls_matcher)) || (rc = put(q.pod_sig, m.p, &m.pod_sig)) ||
-        (rc = put(q.pod_node, m.p, &m.pod_node)))
-      return rc;
-    if ((rc = upload(h, bufs, nullptr, (size_t)m.s * m.cw * 4, &p))) return rc;
-    m.cls_bits = (uint32_t*)p;
-    if ((rc = upload(h, bufs, nullptr, (size_t)m.c * std::max(m.n, 1) * 4, &p))) return rc;
-    m.cnt = (int32_t*)p;
-  }
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  launch_match(m, h->stream);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  if (m.w > 0)
-    HIPCHK(h, hipMemcpyAsync(match_bits, m.bits, (size_t)m.s * m.w * 4, hipMemcpyDeviceToHost, h->stream));
-  if (m.c > 0 && m.n > 0)
-    HIPCHK(h, hipMemcpyAsync(counts, m.cnt, (size_t)m.c * m.n * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->match_ns = (int64_t)(ms * 1e6);
-  return KSIM_OK;
 }

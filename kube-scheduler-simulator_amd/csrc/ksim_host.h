@@ -1,0 +1,363 @@
+// ksim_host.h — what the host runtime's units share: the handle behind the C
+// ABI and the helpers ksim_engine.cpp defines for ksim_snapshot.cpp (the node
+// snapshot's life cycle) and ksim_preempt_host.cpp (DefaultPreemption, term
+// matching).  Private to csrc/: no device code includes it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <map>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "ksim_internal.h"
+
+using namespace ksim;
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+
+// A device buffer reused across calls, grown (never shrunk) on demand: the
+// per-call uploads of the framework-driven calls (one pod, its terms and uses)
+// without a hipMalloc / hipFree pair per call.
+struct DevArena {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
+// One pod (re-based) as a device pod set of its own, packed the way it is
+// uploaded: every piece at a 64-byte aligned offset of one blob.
+struct PodBlob {
+  std::vector<char> bytes;
+  size_t off[8];
+  int32_t n_nn, n_exprs, n_terms, n_uses, n_adds;
+};
+
+struct ksim_handle {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::string err;
+
+  bool has_profile = false;
+  ksim_profile prof{};
+  BatchProg bp{};
+  // device copies of prof / bp, read by the batch-path kernels: a captured
+  // batch graph then survives a weight change (ksim_set_profile)
+  ksim_profile* d_prof = nullptr;
+  BatchProg* d_bp = nullptr;
+  std::vector<size_t> pod_buf_bytes;    // sizes of pod_bufs (ksim_load_pods reuses same-sized buffers)
+
+  bool has_cluster = false;
+  DevCluster dc{};
+  std::vector<DevBuf> cluster_bufs;
+  std::vector<uint8_t> taint_effect;    // host copy (batchability analysis)
+  std::vector<uint16_t> hard_taints;    // taint ids with effect NoSchedule/NoExecute on some node
+  bool any_unschedulable = false;       // some node has spec.unschedulable
+  bool alloc_narrow = false;            // every allocatable cpu / memory in [0, 2^46) (dyn_key_fast)
+
+  // device copy of the uploaded dynamic columns (ksim_reset_cluster)
+  struct {
+    int64_t *req_cpu, *req_mem, *req_eph, *req_scalar, *nz_cpu, *nz_mem;
+    int32_t *num_pods, *cnt;
+    int64_t* nb_alloc;
+  } init{};
+  // node volume limits (ksim_set_volume_limits): limit, attached and the copy
+  // of attached that ksim_reset_cluster restores
+  std::vector<DevBuf> vol_bufs;
+  int32_t* vol_init = nullptr;
+  std::vector<int32_t> col_nvals;       // host copy (pod validation)
+  std::vector<uint8_t> col_unique;      // host copy of DevCluster.col_unique (kUseUniqueCol on upload)
+  std::vector<uint8_t> col_total;       // per label column: every node carries the key
+
+  DevScratch sc{};
+  DevEvalOut eo{};
+  std::vector<DevBuf> scratch_bufs;
+
+  DevState* st = nullptr;
+  int32_t run_hdr[2] = {0, 0};
+
+  // loaded pod queue (batch mode)
+  DevPods dp{};
+  int32_t* d_chosen = nullptr;
+  std::vector<DevBuf> pod_bufs;
+  std::vector<uint8_t> batchable;       // per loaded pod
+  std::vector<uint8_t> topo;            // per loaded pod: 0 no topology uses, 1 uses (k_topo_prefilter), 2 uses
+                                        // read from persistent tables (kPlanPtab)
+  std::vector<uint8_t> trivial;         // per loaded pod: kBatchStaticTrivial
+  std::vector<uint8_t> noadd;           // per loaded pod: no count-class adds (deferred-commit batches)
+  std::vector<uint8_t> noscalar;        // ... and no scalar requests (generic deferred-commit batches)
+  // static classes (DevPods::stab, ensure_stab): per loaded pod its class or
+  // -1 (d_sclass), each class's representative pod (d_srep); the table is
+  // rebuilt after any change of pods, cluster or profile (stab_dirty)
+  int32_t* d_sclass = nullptr;
+  int32_t* d_srep = nullptr;
+  int32_t stab_ncls = 0;
+  bool stab_dirty = true, stab_ready = false;
+  std::vector<DevBuf> stab_bufs;
+  size_t stab_bytes = 0;
+  std::vector<int32_t> sclass;          // host copy of d_sclass
+  std::vector<uint8_t> hard_small;      // per loaded pod: every hard spread key column has <= kFuseMinValues values
+  std::vector<uint8_t> soft_le1;        // per loaded pod: at most one ScheduleAnyway spread constraint
+  std::vector<int32_t> tlen;            // per loaded pod: topology batch run length from it (tbatch_runs)
+  std::vector<int32_t> tlen_plain;      // ... without zone variants (replicated topology batches)
+  std::vector<int64_t> xdom_len;        // per loaded pod: sharded cycle, packed domain words
+  std::vector<int64_t> xreg_len;        // per loaded pod: sharded cycle, registration words (0: no soft spread)
+
+  // compat-mode single pod
+  DevArena pod1_arena;                  // the single-pod uploads (upload_single)
+  DevArena nom_arena;                   // a nominated pod (ksim_fw_filter_nominated)
+  // Reserve / Unreserve calls that arrive while a framework cycle sits between
+  // its PreFilter and Score (the binding goroutine's Unreserve):
+  // upstream's running cycle keeps its snapshot, so the engine applies them
+  // once that cycle has scored (flush_deferred_binds), in call order
+  struct DeferredBind {
+    ksim_pod pod;
+    std::vector<ksim_label_expr> ex;
+    std::vector<ksim_term> tm;
+    std::vector<ksim_topo_use> us;
+    std::vector<ksim_class_add> ad;
+    std::vector<int32_t> nn;
+    int32_t node;
+    int sign;
+  };
+  std::vector<DeferredBind> deferred_binds;
+  // pinned, coherent host staging for the per-call uploads / results, and the
+  // device's addresses of it (copy kernels read / write it directly)
+  void* pin = nullptr;
+  void* pin_d = nullptr;
+  size_t pin_cap = 0;
+  // the last pod upload's copy out of the staging (upload_blob waits on it
+  // instead of the whole stream); the pod last uploaded into pod1_arena (its
+  // bytes and device address: a Reserve / Unreserve of the same pod binds
+  // from there, no upload)
+  // upload_blob's pinned staging ring: consecutive pod uploads (an informer's
+  // pod deltas, another pod's Reserve, the next cycle's pod) do not wait for
+  // each other's copies; a slot is reused once its copy has run (its event)
+  struct PinSlot {
+    void* p = nullptr;
+    void* d = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+  };
+  static constexpr int kPinRing = 4;
+  PinSlot ring[kPinRing];
+  int ring_next = 0;
+  std::vector<char> pod1_blob;
+  char* pod1_base = nullptr;
+  // build_pod_blob's pieces and the framework-driven pass's blob, kept so the
+  // per-cycle calls reuse their capacity
+  std::vector<ksim_label_expr> bs_ex;
+  std::vector<ksim_term> bs_tm;
+  std::vector<ksim_topo_use> bs_us;
+  std::vector<ksim_class_add> bs_ad;
+  std::vector<int32_t> bs_nn;
+  PodBlob fw_blob;
+  // the framework-driven filter passes alternate two arenas, so the Reserve of
+  // cycle i (binding from cycle i's arena) can wait, queued, and run inside
+  // cycle i+1's upload launch (pend_bind); any other call launches it first
+  DevArena fw_arena[2];
+  int fw_flip = 0;
+  struct PendBind {
+    bool on = false;
+    DevPods P{};
+    int32_t node = 0;
+    int sign = 0;
+  } pend_bind;
+  int64_t pend_reuse = 0;                      // upload_blob found the queued Reserve's arena reused (flushed)
+  void* pout = nullptr;
+  void* pout_d = nullptr;
+  size_t pout_cap = 0;
+  // DefaultPreemption: bound pods per node in importance order
+  std::vector<DevBuf> pre_bufs;
+  std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
+  int64_t* pre_smin = nullptr;          // ksim_preempt_spread's per-use minima (in pre_bufs; k_preempt_spread_mins)
+  std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
+  std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
+  std::vector<DevBuf> pre_vol_bufs;     // ksim_set_bound_pod_volumes (likewise, and by ksim_set_volume_limits)
+  const int32_t* pre_voff = nullptr;    // [pre_n + 1] CSR order: the rows' volume holdings (null: none set)
+  const VolHold* pre_vols = nullptr;
+  DevPreempt pre{};
+  std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
+  int32_t pre_n = 0;
+  // extender round trip (ksim_eval_pod_filter -> ksim_eval_pod_finish)
+  DevPods pod1{};
+  bool ext_pending = false;
+  uint8_t* ext_fail = nullptr;     // device [n]
+  int64_t* ext_score = nullptr;    // device [n]
+  // framework-driven compat cycle (ksim_fw_prefilter -> ksim_fw_score ->
+  // ksim_fw_normalize): the pod in h->pod1, its filter pass on the host for
+  // list validation, the scan-set size
+  bool fw_pending = false, fw_scored = false, fw_dom_dirty = false, fw_topo = false;
+  int32_t fw_ns = 0;
+  std::vector<uint8_t> fw_fail;
+  // ksim_fw_score's list and answers, host side: a NormalizeScore over that
+  // list with the raw scores it returned is answered from here
+  std::vector<int32_t> fw_list;
+  std::vector<int64_t> fw_raw, fw_norm;         // [slot][list position]
+  // host-answered Score (fw_host): ksim_fw_prefilter also copies every node's
+  // raw scores, the weighted sum of the plugins without NormalizeScore and the
+  // topology flags into pinned memory, and ksim_fw_score normalizes over the
+  // framework's list on the host (no second device round trip) when no
+  // PreScore of the pod depends on that list
+  bool fw_host = false;
+  int64_t fw_counts[4] = {0, 0, 0, 0};   // Score on the host / device, NormalizeScore cached / device
+  std::vector<uint8_t> fw_seen;    // list validation (all zero between calls)
+  std::vector<int64_t> fw_tot;
+  void* fwh = nullptr;             // pinned: [S][n] raw, [n] part
+  void* fwh_d = nullptr;
+  size_t fwh_cap = 0;
+  uint32_t fw_tflags = 0;
+  size_t fw_oraw = 0, fw_opart = 0;  // fwh offsets of the raw scores and the weighted part
+  bool fw_raw32 = false;             // ... as int32 (the filter kernel's own copy) or int64 (a copy launch)
+  int32_t* fw_nodes = nullptr;     // device [n]
+  int64_t* fw_vals = nullptr;      // device [n]
+  int64_t* fw_out = nullptr;       // device [n]
+
+  // node sharding: this handle holds [shard_base, shard_base + n) of shard_total
+  int32_t shard_base = 0, shard_total = 0;
+  // replicated handle (ksim_set_eval_range): holds every node, evaluates
+  // [eval_lo, eval_hi) in the P100 batch top-T and keeps its replica by
+  // binding every placement: one exchange per batch (the records' all-gather)
+  bool replicated = false;
+  int32_t eval_lo = 0, eval_hi = 0;
+  bool rep_primary = true;              // replicated: this replica counts the whole-run evaluations
+  int32_t rank = 0, world = 1;
+  ncclComm_t comm = nullptr;
+
+  // per-pod cycles, by variant: topology kernels (1) | critical paths in the
+  // filter pass (2) | NormalizeScore extrema in the filter pass (4)
+  hipGraphExec_t graph_cycle[16] = {};   // | persistent tables (8)
+  hipGraphExec_t graph_batch = nullptr;
+  hipGraphExec_t graph_batch_fast = nullptr;   // k_batch_top<true> runs
+  hipGraphExec_t graph_batch_stab = nullptr;   // static-class runs (LaunchArgs::stab)
+  hipGraphExec_t graph_tbatch = nullptr;       // topology batches (ksim_tbatch.hip)
+  // deferred-commit FAST batches (ksim_internal.h): the second snapshot buffer
+  // X[1] and state st[1], the ring of chain + pairs outputs, kGraphBatches
+  // batches as one graph (starting at a batch index divisible by kLazySlots)
+  std::vector<DevBuf> lazy_bufs;
+  int32_t lazy_n = -1;
+  DynCols lazy_x1{};
+  DevState* lazy_st1 = nullptr;
+  uint64_t *lazy_g = nullptr, *lazy_m = nullptr;   // [kLazySlots][kBatchPods]
+  int32_t* lazy_e = nullptr;                        // [kLazySlots] prefix length, -1 = empty slot
+  int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
+  hipGraphExec_t graph_lazy = nullptr;
+  hipGraphExec_t graph_lazy_adapt = nullptr;
+  // the tail graphs: kLazySlots batches of the same flavour, captured with and
+  // dropped with the kGraphBatches graph beside them (run_lazy's top-ups of
+  // fewer than kGraphBatches batches)
+  hipGraphExec_t graph_lazy4 = nullptr, graph_lazy4_adapt = nullptr, graph_lazy4_rt = nullptr;
+  // run_lazy's progress words (host-mapped pinned, alloc_lazy): [0] the last
+  // state writer's lazy_progress, [1] the batch counter the run started from
+  unsigned long long* prog = nullptr;
+  unsigned long long* prog_d = nullptr;
+  // ksim_schedule_loaded leaves the zeroing of the call's counters to its first
+  // run (run_range: run_lazy's begin launch takes it, every other run calls
+  // reset_counters first)
+  bool counters_pending = false;
+  // deferred-commit runs since ksim_create (ksim_get_diag out[28..32]): host
+  // synchronisations inside them, batches enqueued past the end of their run,
+  // stretches ended by a flush and a state read instead of the progress word,
+  // top-ups (batches enqueued after a run's first stretch, by the word or a
+  // read), runs whose last flush had an odd ring index (the end launch copied
+  // X[1] and st[1] back)
+  int64_t feed_syncs = 0, feed_past_end = 0, feed_fallbacks = 0, feed_topups = 0, feed_odd_ends = 0;
+  // request classes of the loaded queue (ksim_internal.h ReqTab): per loaded
+  // pod its class (0xffff: none), the classes' requests, and the table's two
+  // halves [2][rq_ncls][dc.n] with the ring's patch entries
+  // [kLazySlots][rq_ncls][kBatchPods] behind them (ensure_rtab; a reallocation
+  // drops graph_lazy_rt, the deferred-commit graph of the runs that take the table)
+  std::vector<uint16_t> rq_cls;
+  uint16_t* d_rcls = nullptr;
+  PodReq* d_rreq = nullptr;
+  int32_t rq_ncls = 0;                             // > kReqMaxClasses: too many, no table
+  std::vector<DevBuf> rtab_bufs;
+  size_t rtab_bytes = 0;
+  hipGraphExec_t graph_lazy_rt = nullptr;
+  int64_t rtab_runs = 0;                           // runs that took the table (ksim_get_diag out[27])
+  int32_t rt_graph_ncls = 0;                       // the class count graph_lazy_rt was captured with
+  // node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and
+  // the global bitmap (allocated at the first such run)
+  std::vector<DevBuf> ash_bufs;
+  uint64_t *ash_send = nullptr, *ash_recv = nullptr, *ash_gmask = nullptr;
+  int32_t ash_world = 0, ash_w = 0;
+  // packed policy sweep (ksim_sweep_loaded, run_sweep): the lanes' buffers as
+  // one slab sized by (dc.n, lanes), the lane table [kLazySlots][kSweepMaxLanes]
+  // (its address is all a sweep graph holds of them), the vectors' profile
+  // copies, the lanes' placement rows, one graph per (lanes, fast_def)
+  struct SweepLaneBufs {
+    DynCols x[2];
+    uint64_t *g, *m;                             // [kLazySlots][kBatchPods]
+    int32_t* e;                                  // [kLazySlots]
+    uint64_t* topk;
+    int32_t *topk_cnt, *topk_complete, *pinv;
+    int64_t* pnorm;
+  };
+  void* sweep_slab = nullptr;
+  int32_t sweep_n = -1, sweep_lanes = 0;
+  std::vector<SweepLaneBufs> sweep_lane;
+  DevState* sweep_st = nullptr;                  // [sweep_lanes][2]
+  SweepLane* sweep_tab = nullptr;
+  DevArena sweep_profs, sweep_rows;
+  std::map<std::pair<int32_t, bool>, hipGraphExec_t> sweep_graphs;
+  // deferred-commit batches end at their first pair cut (KSIM_ONE_CUT=1 at the
+  // last run's start): the setting the handle's deferred-commit graphs hold
+  bool one_cut = false;
+  int64_t graph_captures = 0;                  // graphs captured since ksim_create (ksim_get_diag)
+  // node-sharded per-pod cycles (group leader): graphs of kGraphCycles cycles
+  // per shape (topology, exchange lengths), valid while every handle of the
+  // group keeps the graph generation it had at capture
+  int64_t graph_gen = 0;                       // bumped whenever this handle's cycle graphs are dropped
+  std::vector<std::pair<const ksim_handle*, int64_t>> sg_sig;
+  std::map<std::tuple<bool, int64_t, int64_t>, hipGraphExec_t> sg_graphs;
+  bool sg_off = false;                         // capture failed once (e.g. a collective that cannot be captured)
+  int64_t match_ns = 0;                        // device time of the last ksim_match_terms (HIP events)
+};
+
+#define HIPCHK(h, expr)                                    \
+  do {                                                     \
+    hipError_t _e = (expr);                                \
+    if (_e != hipSuccess) return hip_fail((h), _e, #expr); \
+  } while (0)
+
+// Defined in ksim_engine.cpp, one copy each; hidden: the library exports the C ABI only.
+namespace ksim_host __attribute__((visibility("hidden"))) {
+
+int set_err(ksim_handle* h, int code, const std::string& msg);
+int hip_fail(ksim_handle* h, hipError_t e, const char* what);
+hipError_t hcopy(ksim_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+void free_bufs(std::vector<DevBuf>& v);
+int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t bytes, void** out);
+
+// upload into a typed field: the one way the host runtime allocates a device
+// array (src null: zero-filled).  T may be const-qualified, as the fields the
+// kernels only read are.
+template <class T>
+int dev_alloc(ksim_handle* h, std::vector<DevBuf>& owner, T*& dst, size_t bytes, const void* src = nullptr) {
+  void* p = nullptr;
+  if (const int rc = upload(h, owner, src, bytes, &p)) return rc;
+  dst = (T*)p;
+  return KSIM_OK;
+}
+
+void drop_graphs(ksim_handle* h);
+void drop_loaded_pods(ksim_handle* h);
+void drop_bound_pods(ksim_handle* h);
+bool is_sharded(const ksim_handle* h);
+int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i);
+int flush_pend_bind(ksim_handle* h);
+int flush_idle(ksim_handle* h);
+int ensure_ready(ksim_handle* h, bool fw = false, bool keep_pend = false);
+LaunchArgs make_args(ksim_handle* h, const DevPods& P, int32_t* chosen);
+int set_run(ksim_handle* h, int32_t first, int32_t end);
+int pin_reserve(ksim_handle* h, size_t bytes);
+int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena);
+int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P);
+
+}  // namespace ksim_host

@@ -1,0 +1,549 @@
+// ksim_preempt_host.cpp — the host side of DefaultPreemption (the bound-pod
+// table, the lists set on its rows, the dry run behind the ksim_preempt*
+// entry points; kernels in ksim_preempt.hip) and of ksim_match_terms
+// (ksim_match.hip).
+#include <algorithm>
+#include <cstring>
+
+#include "ksim_host.h"
+
+using namespace ksim_host;
+
+// A pod's KSIM_USE_VOLUME uses (host arrays, the ABI form).
+static bool has_volume_use(const ksim_pod_set* ps, int32_t i) {
+  if (!ps || !ps->pods || !ps->uses || i < 0 || i >= ps->n_pods) return false;
+  const ksim_pod& p = ps->pods[i];
+  if (p.use_first < 0 || p.use_count < 0 || (int64_t)p.use_first + p.use_count > ps->n_uses) return false;
+  for (int32_t k = 0; k < p.use_count; k++)
+    if (ps->uses[p.use_first + k].kind == KSIM_USE_VOLUME) return true;
+  return false;
+}
+
+// ---- PostFilter: DefaultPreemption (ksim_preempt.hip) ------------------------------
+extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  if (!b || b->n < 0 || (b->n > 0 && (!b->node || !b->priority || !b->start_time || !b->req)))
+    return set_err(h, KSIM_E_INVALID, "bad bound-pod table");
+  const int32_t N = h->dc.n, n = b->n;
+  for (int32_t i = 0; i < n; i++)
+    if (b->node[i] < 0 || b->node[i] >= N) return set_err(h, KSIM_E_INVALID, "bound pod on a node out of range");
+  // per node, util.MoreImportantPod order (priority desc, start asc), then table order
+  std::vector<int32_t> ix((size_t)n);
+  for (int32_t i = 0; i < n; i++) ix[i] = i;
+  std::sort(ix.begin(), ix.end(), [&](int32_t x, int32_t y) {
+    if (b->node[x] != b->node[y]) return b->node[x] < b->node[y];
+    if (b->priority[x] != b->priority[y]) return b->priority[x] > b->priority[y];
+    if (b->start_time[x] != b->start_time[y]) return b->start_time[x] < b->start_time[y];
+    return x < y;
+  });
+  std::vector<int32_t> off((size_t)N + 1, 0), prio((size_t)std::max(n, 1));
+  std::vector<int64_t> start((size_t)std::max(n, 1)), req((size_t)std::max(n, 1) * KSIM_PREEMPT_REQ);
+  for (int32_t i = 0; i < n; i++) off[b->node[i] + 1]++;
+  for (int32_t v = 0; v < N; v++) off[v + 1] += off[v];
+  for (int32_t k = 0; k < n; k++) {
+    const int32_t i = ix[k];
+    prio[k] = b->priority[i];
+    start[k] = b->start_time[i];
+    for (int q = 0; q < KSIM_PREEMPT_REQ; q++) req[(size_t)k * KSIM_PREEMPT_REQ + q] = b->req[(size_t)i * KSIM_PREEMPT_REQ + q];
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  free_bufs(h->pre_bufs);
+  free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
+  free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
+  free_bufs(h->pre_vol_bufs);                  // and the volume holdings
+  h->pre_voff = nullptr;
+  h->pre_vols = nullptr;
+  DevPreempt d{};
+  if ((rc = dev_alloc(h, h->pre_bufs, d.off, 4 * off.size(), off.data())) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.prio, 4 * prio.size(), prio.data())) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.start, 8 * start.size(), start.data())) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.req, 8 * req.size(), req.data())) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.vflag, (size_t)std::max(n, 1))) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.res, sizeof(PreemptNode) * (size_t)N)) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.pick, 32)) ||
+      (rc = dev_alloc(h, h->pre_bufs, d.nslot, 4 * (size_t)std::max(N, 1))))
+    return rc;
+  HIPCHK(h, hipMemsetAsync(d.nslot, 0xff, 4 * (size_t)std::max(N, 1), h->stream));   // -1: no group
+  d.nreq = nullptr;
+  if ((rc = dev_alloc(h, h->pre_bufs, d.afftot, 8 * (size_t)KSIM_MAX_USES)) ||
+      (rc = dev_alloc(h, h->pre_bufs, h->pre_smin, 8 * 3 * (size_t)KSIM_MAX_USES)))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->pre = d;
+  h->pre_index = ix;
+  h->pre_n = n;
+  return KSIM_OK;
+}
+
+// The lists set on the bound-pod table's rows (ksim_set_bound_pod_adds, _pdbs,
+// _volumes) arrive as a CSR over the caller's rows.  Its offsets: monotone,
+// from off[0] >= 0 (from_zero: from 0), with the entries there when the list
+// is not empty.  fn: the calling function, as the error texts name it.
+static int bound_csr_check(ksim_handle* h, const std::string& fn, const int32_t* off, bool have_entries,
+                           const char* what, bool from_zero) {
+  const int32_t n = h->pre_n;
+  if (!off || (from_zero ? off[0] != 0 : off[0] < 0))
+    return set_err(h, KSIM_E_INVALID, fn + (from_zero ? ": bad offsets (they start at 0)" : ": bad offsets"));
+  for (int32_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return set_err(h, KSIM_E_INVALID, fn + ": offsets not monotone");
+  if (off[n] > off[0] && !have_entries) return set_err(h, KSIM_E_INVALID, fn + ": " + what + " missing");
+  return KSIM_OK;
+}
+
+// ... and, every entry validated by the caller: the rows go into the table's
+// per-node importance order (CSR position k = caller row pre_index[k]; conv
+// makes the device's entry of the caller's), the old list is freed (every dry
+// run ends synchronized: nothing reads it) and the new one uploaded, and
+// published once the copies have read this call's vectors.  off == null only
+// clears the list.  extra: one more int32 array that goes with the list (the
+// budgets' allowed counts).
+template <class E, class In, class Conv>
+static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_t* off, const In* in, Conv conv,
+                         const int32_t*& d_off, const E*& d_ent, const int32_t* extra = nullptr, size_t n_extra = 0,
+                         const int32_t** d_extra = nullptr) {
+  const int32_t n = h->pre_n;
+  std::vector<int32_t> poff((size_t)n + 1, 0);
+  std::vector<E> perm;
+  if (off) {
+    perm.reserve((size_t)(off[n] - off[0]));
+    for (int32_t k = 0; k < n; k++) {
+      const int32_t i = h->pre_index[k];
+      for (int32_t e = off[i]; e < off[i + 1]; e++) perm.push_back(conv(in[e]));
+      poff[(size_t)k + 1] = (int32_t)perm.size();
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  free_bufs(bufs);
+  d_off = nullptr;
+  d_ent = nullptr;
+  if (d_extra) *d_extra = nullptr;
+  if (!off) return KSIM_OK;
+  const int32_t *po = nullptr, *px = nullptr;
+  const E* pe = nullptr;
+  int rc;
+  if ((rc = dev_alloc(h, bufs, po, 4 * poff.size(), poff.data())) ||
+      (rc = dev_alloc(h, bufs, pe, sizeof(E) * perm.size(), perm.data())) ||
+      (d_extra && (rc = dev_alloc(h, bufs, px, 4 * n_extra, extra))))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
+  d_off = po;
+  d_ent = pe;
+  if (d_extra) *d_extra = px;
+  return KSIM_OK;
+}
+
+extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: ksim_set_bound_pods first");
+  if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_adds", off, adds != nullptr, "adds", false)) return rc;
+  for (int32_t e = off[0]; e < off[h->pre_n]; e++)
+    if (adds[e].cls < 0 || adds[e].cls >= h->dc.n_classes)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: class out of range");
+  return bound_csr_set(h, h->pre_add_bufs, off, adds, [](const ksim_class_add& a) { return a; }, h->pre.aoff,
+                       h->pre.adds);
+}
+
+extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
+                                       const int32_t* ids) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ksim_set_bound_pods first");
+  if (n_pdbs < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: negative budget count");
+  if (n_pdbs > 0) {
+    // the offsets start at 0 here, and the allowed counts are as much a part of them as the array itself
+    if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_pdbs", allowed ? off : nullptr, ids != nullptr, "ids", true))
+      return rc;
+    std::vector<int32_t> last((size_t)n_pdbs, -1);   // the last row that named the budget
+    for (int32_t i = 0; i < h->pre_n; i++)
+      for (int32_t e = off[i]; e < off[i + 1]; e++) {
+        if (ids[e] < 0 || ids[e] >= n_pdbs)
+          return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: budget id out of range");
+        if (last[ids[e]] == i) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: a budget twice in one row");
+        last[ids[e]] = i;
+      }
+  }
+  // n_pdbs == 0 clears: the dry run takes the forms without budgets
+  return bound_csr_set(h, h->pre_pdb_bufs, n_pdbs > 0 ? off : nullptr, ids, [](int32_t id) { return id; }, h->pre.poff,
+                       h->pre.pids, allowed, (size_t)n_pdbs, &h->pre.pallowed);
+}
+
+extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses) {
+  if (!h) return KSIM_E_INVALID;
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: ksim_set_bound_pods first");
+  if (!h->dc.vol_nf)
+    return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: no volume table (ksim_set_volume_limits)");
+  if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_volumes", off, uses != nullptr, "uses", false)) return rc;
+  for (int32_t e = off[0]; e < off[h->pre_n]; e++) {
+    const ksim_topo_use& u = uses[e];
+    if (u.kind != KSIM_USE_VOLUME)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: a use that is no KSIM_USE_VOLUME");
+    if (u.col >= h->dc.vol_nf) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: family out of range");
+    if (u.cls < -1 || u.cls >= h->dc.n_classes)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: class out of range");
+    if (u.cls < 0 ? u.arg < 1 : u.arg != 1)
+      return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad volume use count");
+  }
+  return bound_csr_set(h, h->pre_vol_bufs, off, uses,
+                       [](const ksim_topo_use& u) { return VolHold{u.cls, (int32_t)u.col, u.arg}; }, h->pre_voff,
+                       h->pre_vols);
+}
+
+extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                            ksim_preempt_out* out) {
+  return ksim_preempt_nominated(h, ps, pod_index, priority, nullptr, 0, nullptr, nullptr, nullptr, out);
+}
+
+// The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
+// DoNotSchedule spread uses are refused), ksim_preempt_spread and
+// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted) and
+// ksim_preempt_full (full = true: every mix of uses is accepted, and a
+// preemptor with volume groups has VolumeBinding / VolumeZone re-run).
+static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
+                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false,
+                       bool full = false) {
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
+    return set_err(h, KSIM_E_INVALID, "bad pod set / index");
+  if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
+    return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
+  const bool vol_form = has_volume_use(ps, pod_index);   // the volume form of k_preempt_nodes
+  if (vol_form && !volumes && !full)
+    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
+                                          "re-run the node volume limit plugins)");
+  {
+    std::vector<uint8_t> seen((size_t)std::max(h->dc.n, 1), 0);
+    for (int32_t k = 0; k < n_groups; k++) {
+      if (gnodes[k] < 0 || gnodes[k] >= h->dc.n || seen[gnodes[k]])
+        return set_err(h, KSIM_E_INVALID, "nominated node out of range or repeated");
+      seen[gnodes[k]] = 1;
+      if (count[k] < 0 || first[k] < 0 || first[k] + count[k] > nps->n_pods)
+        return set_err(h, KSIM_E_INVALID, "nominated pod range out of the pod set");
+      for (int32_t j = first[k]; j < first[k] + count[k]; j++)
+        if ((rc = validate_pod(h, nps, j))) return rc;
+    }
+  }
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pods first");
+  if (is_sharded(h)) return set_err(h, KSIM_E_UNSUPPORTED, "preemption runs on unsharded handles");
+  if (prof_has_filter(h->prof, KSIM_PL_NETWORK_BANDWIDTH))
+    return set_err(h, KSIM_E_UNSUPPORTED, "preemption dry runs re-run Fit only, not NetworkBandwidth");
+  if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
+    return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
+  if ((rc = validate_pod(h, ps, pod_index))) return rc;
+  int32_t fit = -1, port = -1, ipa = -1, pts = -1;
+  for (int f = 0; f < h->prof.n_filter; f++) {
+    if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
+    if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
+    if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) ipa = f;
+    if (h->prof.filter[f] == KSIM_PL_POD_TOPOLOGY_SPREAD) pts = f;
+  }
+  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity and,
+  // through ksim_preempt_spread, PodTopologySpread.  Uses that no Filter reads
+  // (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
+  // ignored; the two older entry points refuse DoNotSchedule spread (their
+  // callers fall back on that code).
+  const ksim_pod& pp = ps->pods[pod_index];
+  const bool topo = pp.use_count > 0;
+  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
+  for (int32_t k = 0; k < pp.use_count && vol_form && !full; k++) {
+    const uint8_t kind = ps->uses[pp.use_first + k].kind;
+    static const char* const kNames[] = {"KSIM_USE_PTS_HARD", nullptr, "KSIM_USE_IPA_EXISTING_ANTI",
+                                         "KSIM_USE_IPA_AFFINITY", "KSIM_USE_IPA_ANTI"};
+    if (kind <= KSIM_USE_IPA_ANTI && kNames[kind])
+      return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_VOLUME use and a ") +
+                                                kNames[kind] + " use (the volume form moves no domain counts)");
+  }
+  for (int32_t k = 0; k < pp.use_count && !spread && !full; k++)
+    if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
+      return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
+                                            "victims' domains: ksim_preempt_spread)");
+  for (int32_t k = 0; k < pp.use_count; k++) {
+    const uint8_t kind = ps->uses[pp.use_first + k].kind;
+    if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_AFFINITY && ipa >= 0) aff_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_ANTI && ipa >= 0) anti_mask |= 1u << k;
+    if (kind == KSIM_USE_IPA_EXISTING_ANTI && ipa >= 0) exist_mask |= 1u << k;
+    if (kind == KSIM_USE_PTS_HARD && pts >= 0) hard_mask |= 1u << k;
+  }
+  // the domain form of k_preempt_nodes (the spread form is one: it reads the same row)
+  const bool dom_form = (aff_mask | anti_mask | exist_mask | hard_mask) != 0;
+  if (hard_mask && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "ksim_preempt_spread for a pod with DoNotSchedule spread: "
+                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
+  if (port_mask && !dom_form && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
+                                      "(after ksim_set_bound_pods)");
+  if (vol_form && !h->pre_voff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with a KSIM_USE_VOLUME use: ksim_set_bound_pod_volumes "
+                                      "first (after ksim_set_bound_pods)");
+  // what the profile's limit plugins read of the pod (validate_pod checked the families)
+  PreemptVol vm{};
+  vm.at = 0xffffffffu;
+  if (vol_form) {
+    for (int f = 0; f < h->prof.n_filter; f++) {
+      const int32_t k = h->prof.filter[f] - KSIM_PL_EBS_LIMITS;
+      if (k >= 0 && k < 4) vm.at = (vm.at & ~(255u << (8 * k))) | ((uint32_t)f << (8 * k));
+    }
+    for (int32_t k = 0; k < pp.use_count; k++) {
+      const ksim_topo_use& u = ps->uses[pp.use_first + k];
+      if (u.kind != KSIM_USE_VOLUME) continue;
+      const uint32_t pl = (h->dc.vol_plug >> (4 * u.col)) & 15u;
+      if (((vm.at >> (8 * pl)) & 255u) == 255u) continue;   // its plugin is not in the filter list
+      vm.uses |= 1u << k;
+      vm.fams |= 1u << u.col;
+      if (pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS)) vm.csi |= 1u << u.col;
+    }
+  }
+  if (dom_form && !h->pre.aoff)
+    return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
+                                      "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
+  HIPCHK(h, hipSetDevice(h->device));
+  DevPods P;
+  if ((rc = upload_single(h, ps, pod_index, P))) return rc;
+  if ((rc = set_run(h, 0, 1))) return rc;
+  const LaunchArgs a = make_args(h, P, nullptr);
+  DevPreempt pre = h->pre;
+  // The status pass: the per-pod cycle's filter phase.  For a pod with uses its
+  // PreFilter pass runs first; the domain tables and topology flags it fills
+  // are zero between cycles (k_select / k_bind re-zero them in a whole cycle).
+  // keep: the domain form of k_preempt_nodes reads the last pass's tables, so
+  // the caller re-zeroes them after that kernel.
+  auto rezero = [&]() -> int {
+    if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
+    HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
+    return KSIM_OK;
+  };
+  auto filter_pass = [&](bool keep = false) -> int {
+    launch_filter_only(a, h->stream, topo);
+    HIPCHK(h, hipGetLastError());
+    return topo && !keep ? rezero() : KSIM_OK;
+  };
+  std::vector<uint8_t> gfail((size_t)std::max(n_groups, 1), KSIM_PASSED);
+  std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
+  std::vector<int32_t> goff((size_t)n_groups + 1, 0);    // the groups' class contributions (CSR)
+  std::vector<ksim_class_add> gadds;
+  std::vector<int32_t> gvoff((size_t)n_groups + 1, 0);   // and their volume holdings, for the volume form
+  std::vector<VolHold> gvols;
+  auto bind_group = [&](int32_t k, int sign) -> int {
+    for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
+      DevPods Q;
+      int r;
+      if ((r = upload_single(h, nps, j, Q, h->nom_arena))) return r;
+      launch_assume(h->dc, Q, 0, gnodes[k], sign, h->stream);
+      HIPCHK(h, hipGetLastError());
+    }
+    return KSIM_OK;
+  };
+  for (int32_t k = 0; k < n_groups; k++) {                // pass 1 of each grouped node
+    if ((rc = bind_group(k, 1))) return rc;
+    if ((rc = filter_pass())) return rc;
+    HIPCHK(h, hcopy(h, &gfail[k], h->sc.fail + gnodes[k], 1, hipMemcpyDeviceToHost));
+    if ((rc = bind_group(k, -1))) return rc;
+    int64_t* q = nreq.data() + (size_t)k * (KSIM_PREEMPT_REQ + 1);
+    for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
+      const ksim_pod& x = nps->pods[j];
+      q[0] += x.req_cpu;
+      q[1] += x.req_mem;
+      q[2] += x.req_eph;
+      for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
+      if ((port_mask || dom_form) && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
+      for (int32_t e = 0; e < x.use_count && vol_form; e++) {
+        const ksim_topo_use& u = nps->uses[x.use_first + e];
+        if (u.kind == KSIM_USE_VOLUME) gvols.push_back({u.cls, (int32_t)u.col, u.arg});
+      }
+    }
+    q[KSIM_PREEMPT_REQ] = count[k];
+    goff[(size_t)k + 1] = (int32_t)gadds.size();
+    gvoff[(size_t)k + 1] = (int32_t)gvols.size();
+  }
+  if (n_groups > 0) {
+    free_bufs(h->pre_nom_bufs);
+    if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.nreq, 8 * nreq.size(), nreq.data()))) return rc;
+    if (port_mask || dom_form) {                           // the groups' holdings stay on their nodes too
+      if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.goff, 4 * goff.size(), goff.data())) ||
+          (rc = dev_alloc(h, h->pre_nom_bufs, pre.gadds, sizeof(ksim_class_add) * gadds.size(), gadds.data())))
+        return rc;
+    }
+    if (vol_form) {
+      if ((rc = dev_alloc(h, h->pre_nom_bufs, vm.gvoff, 4 * gvoff.size(), gvoff.data())) ||
+          (rc = dev_alloc(h, h->pre_nom_bufs, vm.gvols, sizeof(VolHold) * gvols.size(), gvols.data())))
+        return rc;
+    }
+  }
+  if ((rc = filter_pass(dom_form))) return rc;             // every node as is
+  if (n_groups > 0) {
+    for (int32_t k = 0; k < n_groups; k++) {
+      // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
+      if (gfail[k] != KSIM_PASSED) {
+        gfail[k] &= (uint8_t)~kFailError;
+        HIPCHK(h, hipMemcpyAsync(h->sc.fail + gnodes[k], &gfail[k], 1, hipMemcpyHostToDevice, h->stream));
+      }
+      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &k, 4, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
+    }
+  }
+  // ksim_preempt_full: the static volume filters of a preemptor with groups
+  const bool vb = full && pp.vb_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_BINDING);
+  const bool vz = full && pp.vz_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_ZONE);
+  vm.voff = h->pre_voff;
+  vm.vols = h->pre_vols;
+  if (vol_form && dom_form && vm.uses) {                   // only ksim_preempt_full gets here: the full form
+    launch_preempt_full(a, pre, fit, priority, h->stream, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
+                        hard_mask, h->pre_smin, vm, vb, vz);
+  } else {
+    if (vol_form && !dom_form)
+      launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
+    else
+      launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask,
+                     pts, hard_mask, h->pre_smin);
+    if (vb || vz) launch_preempt_veto(a, pre, h->stream, vb, vz);
+  }
+  HIPCHK(h, hipGetLastError());
+  if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
+  if (n_groups > 0) {
+    static const int32_t kNoGroup = -1;
+    for (int32_t k = 0; k < n_groups; k++)
+      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &kNoGroup, 4, hipMemcpyHostToDevice, h->stream));
+  }
+  int32_t pick[5];
+  HIPCHK(h, hipMemcpyAsync(pick, h->pre.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  out->nominated = pick[0];
+  out->n_victims = pick[1];
+  out->n_potential = pick[2];
+  out->n_candidates = pick[3];
+  out->n_pdb_violations = pick[4];
+  if (pick[0] >= 0 && out->victims && out->victims_cap > 0) {
+    std::vector<int32_t> off(2);
+    HIPCHK(h, hcopy(h, off.data(), h->pre.off + pick[0], 8, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
+    if (off[1] > off[0])
+      HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
+    // the dry run's list order: the victims violating a PDB, then the others, each in CSR order
+    int32_t k = 0;
+    for (const uint8_t want : {(uint8_t)(1 | kPreemptViolating), (uint8_t)1})
+      for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
+        if (flag[j - off[0]] == want) out->victims[k++] = h->pre_index[j];
+  }
+  return KSIM_OK;
+}
+
+extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                      const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                      const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false);
+}
+
+extern "C" int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                    const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                    const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false, true);
+}
+
+extern "C" int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                 const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                 const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true, true, true);
+}
+
+extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                                   const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
+                                   const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
+  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true);
+}
+
+// ---- selector / affinity-term matching (ksim_match.hip) ------
+extern "C" int ksim_match_terms(ksim_handle* h, const ksim_match_problem* mp, uint32_t* match_bits, int32_t* counts) {
+  if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
+  if (!h || !mp || !match_bits) return set_err(h, KSIM_E_INVALID, "null argument");
+  const ksim_match_problem& q = *mp;
+  if (q.n_sigs < 0 || q.n_feat < 0 || q.n_reqs < 0 || q.n_matchers < 0 || q.n_pods < 0 || q.n_nodes < 0 ||
+      q.n_classes < 0)
+    return set_err(h, KSIM_E_INVALID, "negative size");
+  if (q.n_reqs > kMatchMaxReqs || q.n_feat > kMatchMaxFeat)
+    return set_err(h, KSIM_E_UNSUPPORTED, "match problem exceeds 4096 requirements or 65536 features");
+  if (q.n_classes > 0 && !counts) return set_err(h, KSIM_E_INVALID, "counts buffer missing");
+  if (!q.sig_feat_off || !q.req_feat_off || (!q.req_neg && q.n_reqs > 0) || !q.m_req_off)
+    return set_err(h, KSIM_E_INVALID, "null CSR");
+  // host validation: every index the kernels follow is in range
+  auto csr_ok = [](const int32_t* off, int32_t rows, const int32_t* v, int32_t bound) {
+    if (off[0] != 0) return false;
+    for (int32_t i = 0; i < rows; i++)
+      if (off[i + 1] < off[i]) return false;
+    if (off[rows] > 0 && !v) return false;
+    for (int32_t j = 0; j < off[rows]; j++)
+      if (v[j] < 0 || v[j] >= bound) return false;
+    return true;
+  };
+  if (!csr_ok(q.sig_feat_off, q.n_sigs, q.sig_feat, q.n_feat) ||
+      !csr_ok(q.req_feat_off, q.n_reqs, q.req_feat, q.n_feat) ||
+      !csr_ok(q.m_req_off, q.n_matchers, q.m_req, q.n_reqs))
+    return set_err(h, KSIM_E_INVALID, "feature / requirement index out of range");
+  if (q.n_classes > 0) {
+    if (!q.class_matcher) return set_err(h, KSIM_E_INVALID, "class_matcher missing");
+    for (int32_t c = 0; c < q.n_classes; c++)
+      if (q.class_matcher[c] < 0 || q.class_matcher[c] >= q.n_matchers)
+        return set_err(h, KSIM_E_INVALID, "class matcher out of range");
+    if (q.n_pods > 0 && (!q.pod_sig || !q.pod_node)) return set_err(h, KSIM_E_INVALID, "bound pod arrays missing");
+    for (int32_t p = 0; p < q.n_pods; p++)
+      if (q.pod_sig[p] < 0 || q.pod_sig[p] >= q.n_sigs || q.pod_node[p] < 0 || q.pod_node[p] >= q.n_nodes)
+        return set_err(h, KSIM_E_INVALID, "bound pod signature / node out of range");
+  }
+  if (q.n_sigs == 0) {                         // no signature: no bound pod either (pod_sig < n_sigs)
+    if (q.n_classes > 0 && q.n_nodes > 0) std::memset(counts, 0, (size_t)q.n_classes * q.n_nodes * 4);
+    return KSIM_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevMatch m{};
+  m.s = q.n_sigs;
+  m.sp = (q.n_sigs + 15) / 16 * 16;
+  m.fp = std::max(64, (q.n_feat + 63) / 64 * 64);
+  m.r = q.n_reqs;
+  m.rp = std::max(16, (q.n_reqs + 15) / 16 * 16);
+  m.m = q.n_matchers;
+  m.w = (q.n_matchers + 31) / 32;
+  m.c = q.n_classes;
+  m.cw = (q.n_classes + 31) / 32;
+  m.p = q.n_classes > 0 ? q.n_pods : 0;
+  m.n = q.n_nodes;
+  std::vector<DevBuf> bufs;
+  struct Guard {
+    std::vector<DevBuf>& b;
+    ~Guard() { free_bufs(b); }
+  } guard{bufs};
+  int rc;
+  std::vector<uint8_t> neg((size_t)m.rp, 0);
+  std::copy(q.req_neg, q.req_neg + q.n_reqs, neg.begin());
+  if ((rc = dev_alloc(h, bufs, m.a, (size_t)m.sp * m.fp)) || (rc = dev_alloc(h, bufs, m.bt, (size_t)m.rp * m.fp)) ||
+      (rc = dev_alloc(h, bufs, m.neg, neg.size(), neg.data())))
+    return rc;
+  auto put = [&](const int32_t* src, int64_t n, const int32_t*& dst) {
+    return dev_alloc(h, bufs, dst, (size_t)std::max<int64_t>(n, 0) * 4, src);
+  };
+  if ((rc = put(q.sig_feat_off, q.n_sigs + 1, m.sig_off)) || (rc = put(q.sig_feat, q.sig_feat_off[q.n_sigs], m.sig_feat)) ||
+      (rc = put(q.req_feat_off, q.n_reqs + 1, m.req_off)) || (rc = put(q.req_feat, q.req_feat_off[q.n_reqs], m.req_feat)) ||
+      (rc = put(q.m_req_off, q.n_matchers + 1, m.m_off)) || (rc = put(q.m_req, q.m_req_off[q.n_matchers], m.m_req)))
+    return rc;
+  if ((rc = dev_alloc(h, bufs, m.bits, (size_t)m.s * std::max(m.w, 1) * 4))) return rc;
+  if (m.c > 0) {
+    if ((rc = put(q.class_matcher, m.c, m.cls_matcher)) || (rc = put(q.pod_sig, m.p, m.pod_sig)) ||
+        (rc = put(q.pod_node, m.p, m.pod_node)) || (rc = dev_alloc(h, bufs, m.cls_bits, (size_t)m.s * m.cw * 4)) ||
+        (rc = dev_alloc(h, bufs, m.cnt, (size_t)m.c * std::max(m.n, 1) * 4)))
+      return rc;
+  }
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  launch_match(m, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  if (m.w > 0)
+    HIPCHK(h, hipMemcpyAsync(match_bits, m.bits, (size_t)m.s * m.w * 4, hipMemcpyDeviceToHost, h->stream));
+  if (m.c > 0 && m.n > 0)
+    HIPCHK(h, hipMemcpyAsync(counts, m.cnt, (size_t)m.c * m.n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->match_ns = (int64_t)(ms * 1e6);
+  return KSIM_OK;
+}
