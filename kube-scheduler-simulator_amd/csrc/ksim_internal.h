@@ -338,20 +338,6 @@ struct DevPreempt {
   const int32_t* pids;
   const int32_t* pallowed;             // [n_pdbs] status.disruptionsAllowed
 };
-// filter = false: s.fail already holds the statuses (ksim_preempt_nominated).
-// port_index / port_mask: NodePorts' place in the profile's filter list and
-// the preemptor's NodePorts uses (bit i = use i); 0: the dry run re-runs Fit alone.
-// ipa_index / aff, anti, exist: InterPodAffinity's place and the preemptor's
-// required-affinity, required-anti-affinity and existing-anti-affinity uses
-// (the domain form: s.dom still holds the status pass's domain tables).
-// pts_index / hard / smin: PodTopologySpread's place, the preemptor's
-// DoNotSchedule spread uses (the spread form, which reads the same tables) and
-// [KSIM_MAX_USES][3] device words for k_preempt_spread_mins' minima.
-void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio, hipStream_t stream,
-                    bool filter = true, int32_t port_index = -1, uint32_t port_mask = 0, int32_t ipa_index = -1,
-                    uint32_t aff = 0, uint32_t anti = 0, uint32_t exist = 0, int32_t pts_index = -1,
-                    uint32_t hard = 0, int64_t* smin = nullptr);
-
 // One counted-volume holding of a bound pod or of a nominated pod: the device
 // form of a KSIM_USE_VOLUME use (ksim_set_bound_pod_volumes).
 struct VolHold {
@@ -359,10 +345,10 @@ struct VolHold {
   int32_t fam;                         // family index < vol_nf
   int32_t arg;
 };
-// The volume form's argument (ksim_preempt_volumes for a preemptor with
-// KSIM_USE_VOLUME uses; the other forms keep their kernel arguments).  Only
-// what the profile's limit plugins read is named: a family whose plugin the
-// filter list lacks is in none of the masks.
+// What the dry run's volume side reads (a preemptor with KSIM_USE_VOLUME uses:
+// the volume form and the full form; the other forms' kernels do not take it).
+// Only what the profile's limit plugins read is named: a family whose plugin
+// the filter list lacks is in none of the masks.
 struct PreemptVol {
   const int32_t* voff;                 // [n_bound + 1] CSR order: vols[voff[j] .. voff[j + 1]) of bound pod j
   const VolHold* vols;
@@ -373,22 +359,22 @@ struct PreemptVol {
   uint32_t csi;                        // those under NodeVolumeLimits' rule (new > 0)
   uint32_t at;                         // byte k: the profile position of plugin KSIM_PL_EBS_LIMITS + k, 0xff: absent
 };
-// The volume form: launch_preempt with filter = false for a preemptor with
-// volume uses (and possibly NodePorts uses); a.c carries the volume table.
-void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                            hipStream_t stream, int32_t port_index, uint32_t port_mask, const PreemptVol& vm);
-// The full form (ksim_preempt_full): a preemptor with volume uses beside
-// required pod (anti-)affinity or DoNotSchedule spread uses; launch_preempt's
-// and launch_preempt_volumes' arguments together.  vb / vz: the preemptor has
-// volume groups and VolumeBinding / VolumeZone is in the filter list; the
-// nodes either fails leave the candidates before the pick.
-void launch_preempt_full(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                         hipStream_t stream, int32_t port_index, uint32_t port_mask, int32_t ipa_index, uint32_t aff,
-                         uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin,
-                         const PreemptVol& vm, bool vb, bool vz);
-// The same veto after one of the older forms' launches, and the pick again on
-// the candidates that are left.
-void launch_preempt_veto(const LaunchArgs& a, const DevPreempt& pre, hipStream_t stream, bool vb, bool vz);
+// Which uses of the preemptor one dry run reads, and where their filters stand.
+struct PreemptPlan {
+  int32_t fit, port, ipa, pts;         // NodeResourcesFit's, NodePorts', InterPodAffinity's, PodTopologySpread's places (-1: absent)
+  int32_t prio;                        // the preemptor's priority
+  // Its NodePorts, required-affinity, required-anti-affinity, existing-anti-affinity and DoNotSchedule
+  // spread uses (bit i = use i).  A use whose filter the profile lacks is in none of them.
+  uint32_t ports, aff, anti, exist, hard;
+  int64_t* smin;                       // [KSIM_MAX_USES][3] device words for k_preempt_spread_mins' minima
+  PreemptVol vol;                      // voff: null for a preemptor without volume uses
+  bool vb, vz;                         // it has volume groups and VolumeBinding / VolumeZone is in the filter list
+  // the node kernel reads the status pass's domain tables (a form with a row side)
+  bool reads_domains() const { return (aff | anti | exist | hard) != 0; }
+};
+// One dry run over the statuses in s.fail (reads_domains(): and the status pass's domain tables
+// in s.dom): the node kernel of the plan's form (ksim_preempt.hip), the static veto (vb / vz), the pick.
+void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& plan, hipStream_t stream);
 
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);

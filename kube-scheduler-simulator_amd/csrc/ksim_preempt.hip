@@ -1,40 +1,45 @@
 // ksim_preempt.hip — PostFilter: DefaultPreemption's dry run on the device
 // (upstream preemption.go / default_preemption.go, v1.26).
 //
-// After an unschedulable cycle, every node where preemption might help (the
-// filter pass failed it at NodeResourcesFit or, for a pod with host ports, at
-// NodePorts) runs SelectVictimsOnNode on its own thread: remove every bound pod
-// of lower priority, check the pod fits, then reprieve the removed pods most
-// important first (priority desc, start time asc), keeping each one the pod
-// still fits beside.  "Fits" is NodeResourcesFit on the node's requests and,
-// for a pod with NodePorts uses, no pod left on the node in any of its port
-// classes: the thread keeps the node's count of each (at most KSIM_MAX_USES)
-// and moves it with every pod it removes or adds back, from the bound pods'
-// class contributions (ksim_set_bound_pod_adds).  The bound pods are
-// held per node in importance order (CSR), so the lower-priority pods are a
-// suffix of the node's range.  A pod with required pod (anti-)affinity uses
-// takes the domain form: the thread holds the node's TopoRow (the domain sum of
-// the node's topology value, or the node's own count, per use), moves it the
-// same way and re-runs interpodaffinity's Filter on it; a node that failed
-// InterPodAffinity for an anti-affinity reason is a potential node too.  With
+// After an unschedulable cycle, every node where preemption might help (its
+// first failing filter returned plain Unschedulable and the dry run re-runs it)
+// runs SelectVictimsOnNode on its own thread: remove every bound pod of lower
+// priority, check the pod fits, then reprieve the removed pods most important
+// first (priority desc, start time asc), keeping each one the pod still fits
+// beside.  The bound pods are held per node in importance order (CSR), so the
+// lower-priority pods are a suffix of the node's range.  With
 // PodDisruptionBudgets on the table (ksim_set_bound_pod_pdbs) the thread first
-// splits the lower-priority pods as filterPodsWithPDBViolation does (the PDB
-// form, kernels of their own) and reprieves the violating ones first.  A pod
-// with DoNotSchedule spread uses (ksim_preempt_spread) takes the spread form:
-// the domain form plus PodTopologySpread's Filter on the moved row, against
-// min(the node's own domain, the minimum over the other present domains),
-// which k_preempt_spread_mins takes once per dry run.  A pod with counted
-// volumes (ksim_preempt_volumes) takes the volume form, k_preempt_nodes_vol:
-// the ports form plus the node volume limit plugins on the node's attached
-// count per family, moved with the rows' holdings (ksim_set_bound_pod_volumes);
-// a node that failed one of those plugins is a potential node too.  A pod with
-// counted volumes beside (anti-)affinity or spread uses (ksim_preempt_full)
-// takes the full form, k_preempt_nodes_full: the spread form and the volume
-// form in one thread; for a pod with volume groups k_preempt_static_veto then
-// takes the nodes VolumeBinding or VolumeZone fails out of the candidates.  One
-// block then keeps candidates in nodeTree order (upstream scans from a random
-// offset; offset 0 here) until numCandidates were found and one of them has
-// no PDB violation, and picks one by pickOneNodeForPreemption's criteria.
+// splits that suffix as filterPodsWithPDBViolation does and reprieves the
+// violating rows first (PDB, a template parameter of its own).
+//
+// The thread's trial state is made of sides.  Each owns its registers and has
+// init (its start on the node), move (one row in or out), move_group (the
+// node's nominated group in) and fails (the filters it re-runs):
+//   RequestSide  the node's requests; NodeResourcesFit
+//   PortSide     the node's count of each port class of the preemptor's, from the
+//                rows' class contributions (ksim_set_bound_pod_adds); NodePorts
+//   RowSide      the node's TopoRow, moved by the same contributions; NodePorts,
+//                InterPodAffinity and, with SPREAD, PodTopologySpread against the
+//                minimum over the other present domains (k_preempt_spread_mins)
+//   VolSide      the node's attached volumes per family, moved by the rows'
+//                holdings (ksim_set_bound_pod_volumes); the node volume limit
+//                plugins.  A shared volume's holder count lives in the side
+//                beside it: PortSide's held[] or the TopoRow's own entry.
+// A form lists the sides one kind of preemptor needs and says which first
+// failing filters make a potential node.  Each has kernels and a kernel
+// argument of its own, so a preemptor without a kind of use runs the code and
+// keeps the registers of the form without it:
+//   FreeForm     request                  no filter-read uses
+//   PortsForm    request, ports           host ports (in FreeForm's kernels, behind one uniform branch)
+//   DomForm      request, row             required pod (anti-)affinity
+//   SpreadForm   request, row + SPREAD    DoNotSchedule spread (ksim_preempt_spread)
+//   VolumeForm   request, ports, volume   counted volumes (ksim_preempt_volumes)
+//   FullForm     request, row + SPREAD, volume   volumes beside affinity or spread (ksim_preempt_full)
+// For a preemptor with volume groups k_preempt_static_veto then takes the nodes
+// VolumeBinding or VolumeZone fails out of the candidates.  One block keeps
+// candidates in nodeTree order (upstream scans from a random offset; offset 0
+// here) until numCandidates were found and one of them has no PDB violation,
+// and picks one by pickOneNodeForPreemption's criteria.
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
@@ -43,6 +48,75 @@
 
 namespace ksim {
 
+// The arguments every form's node kernel takes.  fit_index / port_index:
+// NodeResourcesFit's and NodePorts' places in the filter list (-1: absent);
+// port_mask: the preemptor's NodePorts uses (bit i = use i).
+struct PreemptCommon {
+  DevCluster c;
+  DevPods P;
+  const DevState* st;
+  DevScratch s;
+  DevPreempt pre;
+  int32_t fit_index, prio, port_index;
+  uint32_t port_mask;
+};
+// The preemptor's filter-read uses in the domain form (kernel argument, bit i =
+// use i): its InterPodAffinity uses by role, and that filter's place in the
+// profile.
+struct PreemptDom {
+  uint32_t aff, anti, exist;
+  int32_t ipa_index;
+};
+// The spread form's argument: the preemptor's DoNotSchedule spread uses,
+// PodTopologySpread's place, and per use {the minimum over the present
+// domains, the value id of one arg-min, the minimum over the others}
+// (k_preempt_spread_mins; [KSIM_MAX_USES][3]).
+struct PreemptSpread : PreemptDom {
+  uint32_t hard;
+  int32_t pts_index;
+  int64_t* smin;
+};
+// The full form's: hard may be empty (volumes beside affinity alone); then no
+// use is a spread use and PodTopologySpread's place is not read.
+struct PreemptFull {
+  PreemptSpread ds;
+  PreemptVol vm;
+};
+
+// One node's dry run: what the sides read beside their own state.  g: the
+// node's nominated group (-1: none); [j0, b): the rows of lower priority than
+// the preemptor's.
+struct Trial {
+  const PreemptCommon& a;
+  const ksim_pod& p;
+  const PodPlan& plan;
+  const ksim_topo_use* U;
+  int32_t node, g, j0, b;
+};
+
+// The first failing filter is NodeResourcesFit or, for a preemptor with port
+// uses, NodePorts: a potential node in every form.
+__device__ __forceinline__ bool failed_fit_or_ports(uint32_t f, const PreemptCommon& a) {
+  return (a.fit_index >= 0 && f == (uint32_t)a.fit_index) || (a.port_mask && f == (uint32_t)a.port_index);
+}
+
+// NodeInfo.AddPod / RemovePod (and PreFilterExtensions' of the same names) on
+// per-use counts: sign x count of every add of [e0, e1) whose class one of the
+// preemptor's uses reads.  cls[i]: that class, kNoPortClass for a use no add
+// moves (no add carries it), block-uniform.
+constexpr int32_t kNoPortClass = -2;
+template <class T>
+__device__ __forceinline__ void count_add(T (&n)[KSIM_MAX_USES], const int32_t (&cls)[KSIM_MAX_USES],
+                                          const ksim_class_add* __restrict__ adds, int32_t e0, int32_t e1, int sign) {
+  for (int32_t e = e0; e < e1; e++) {
+    const ksim_class_add x = adds[e];
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++)
+      if (cls[i] == x.cls) n[i] += (T)sign * x.count;
+  }
+}
+
+// ---- the request side ----------------------------------------------------------
 __device__ __forceinline__ void row_add_req(NodeRow& r, const int64_t* q, int sign, int n_scalar) {
   r.req_cpu += sign * q[0];
   r.req_mem += sign * q[1];
@@ -52,187 +126,58 @@ __device__ __forceinline__ void row_add_req(NodeRow& r, const int64_t* q, int si
     if (k < n_scalar) r.req_sc[k] += sign * q[3 + k];
   r.num_pods += sign;
 }
+struct RequestSide {
+  NodeRow r;
+  __device__ __forceinline__ void init(const Trial& x) { r = load_row(x.a.c, x.node); }
+  __device__ __forceinline__ void move(const Trial& x, int32_t j, int sign) {
+    row_add_req(r, x.a.pre.req + (size_t)j * KSIM_PREEMPT_REQ, sign, x.a.c.n_scalar);
+  }
+  __device__ __forceinline__ void move_group(const Trial& x) {   // the nominated pods stay (pass 1)
+    const int64_t* q = x.a.pre.nreq + (size_t)x.g * (KSIM_PREEMPT_REQ + 1);
+    row_add_req(r, q, 1, x.a.c.n_scalar);
+    r.num_pods += (int32_t)q[KSIM_PREEMPT_REQ] - 1;
+  }
+  // alone: the form re-runs no other filter; one that does re-runs NodeResourcesFit only when the profile has it
+  __device__ __forceinline__ bool fails(const Trial& x, bool alone = false) const {
+    return (alone || x.a.fit_index >= 0) && fits_request(r, x.p, x.a.c.n_scalar, x.a.c.fit_ignore) != 0;
+  }
+};
 
-// The preemptor's NodePorts uses on one node: held[i] = pods on the node of
-// use i's port class (0 for every other use).  cls[i] is the class of port
-// use i, kNoPortClass elsewhere (no add carries it), block-uniform.
-constexpr int32_t kNoPortClass = -2;
-struct PortHold {
+// ---- the ports side ------------------------------------------------------------
+// held[i] = pods on the node of port use i's class (0 for every other use; the
+// volume side keeps a shared volume's holders in the entry of its use).
+struct PortSide {
+  int32_t cls[KSIM_MAX_USES];
   int32_t held[KSIM_MAX_USES];
-};
-// NodeInfo.AddPod / RemovePod on the holdings: the adds [e0, e1) of one pod (or
-// nominated group) that count into a class of the preemptor's
-__device__ __forceinline__ void hold_add(PortHold& h, const int32_t (&cls)[KSIM_MAX_USES],
-                                         const ksim_class_add* __restrict__ adds, int32_t e0, int32_t e1, int sign) {
-  for (int32_t e = e0; e < e1; e++) {
-    const ksim_class_add x = adds[e];
+  __device__ __forceinline__ void init(const Trial& x) {
 #pragma unroll
-    for (int i = 0; i < KSIM_MAX_USES; i++)
-      if (cls[i] == x.cls) h.held[i] += sign * x.count;
-  }
-}
-// nodeports Filter on the holdings (node_port_conflict)
-__device__ __forceinline__ bool hold_conflict(const PortHold& h) {
-  bool hit = false;
-#pragma unroll
-  for (int i = 0; i < KSIM_MAX_USES; i++)
-    if (h.held[i] > 0) hit = true;
-  return hit;
-}
-
-// The volume form's per-thread state: the node's distinct family-f volumes
-// (c.vol_attached, moved with every pod taken out or put back) and its limit,
-// for the families the preemptor has a use of.  Indexed by unrolled constants
-// only, so both stay in registers.
-struct VolRow {
-  int64_t att[KSIM_MAX_VOL_FAMILIES];
-  int32_t lim[KSIM_MAX_VOL_FAMILIES];
-};
-struct NoVol {};                                         // the other forms' (empty) volume argument
-// The full form's holder counts: the TopoRow's own entries (load_topo_row put a
-// volume use's class count there), under the name the volume form reads.
-struct RowHold {
-  int64_t (&held)[KSIM_MAX_USES];
-};
-// The volume side's holder counts of a form: the row's in the full form (ROW),
-// held[] in the volume form.
-template <bool ROW>
-__device__ __forceinline__ decltype(auto) vol_holder(PortHold& h, TopoRow& t) {
-  if constexpr (ROW) return RowHold{t.x};
-  else return (h);
-}
-// nodeports Filter on the holdings of the volume form: only the port uses
-// conflict (a held volume class is no conflict)
-__device__ __forceinline__ bool hold_conflict(const PortHold& h, uint32_t port_mask) {
-  bool hit = false;
-#pragma unroll
-  for (int i = 0; i < KSIM_MAX_USES; i++)
-    if (((port_mask >> i) & 1u) && h.held[i] > 0) hit = true;
-  return hit;
-}
-// Pods of the node's suffix [j0, b) that are out of the trial state (bit 0 of
-// their flag; row `skip` apart) and hold volume class `cls`: a direct count,
-// quadratic in the node's victims like the PDB form's.
-__device__ __forceinline__ int32_t vol_out_holders(const DevPreempt& pre, const PreemptVol& vm, int32_t j0, int32_t b,
-                                                   int32_t skip, int32_t cls) {
-  int32_t n = 0;
-  for (int32_t k = j0; k < b; k++) {
-    if (k == skip || !(pre.vflag[k] & 1)) continue;
-    for (int32_t e = vm.voff[k]; e < vm.voff[k + 1]; e++) n += vm.vols[e].cls == cls;
-  }
-  return n;
-}
-// Entries [e0, e1) of `ents` that hold class `cls`
-__device__ __forceinline__ int32_t vol_class_entries(const VolHold* __restrict__ ents, int32_t e0, int32_t e1,
-                                                     int32_t cls) {
-  int32_t n = 0;
-  for (int32_t e = e0; e < e1; e++) n += ents[e].cls == cls;
-  return n;
-}
-// The holders of volume class x on the node apart from row j, for a class the
-// preemptor does not use: the device's count (every bound holder of the node,
-// whatever its priority, row j among them) and the nominated group's, less the
-// rows that are out.
-struct VolOthers {
-  const DevCluster& c;
-  const DevPreempt& pre;
-  const PreemptVol& vm;
-  int32_t node, g, j0, b, j;
-  __device__ __forceinline__ int32_t operator()(int32_t x, int32_t) const {
-    const int32_t grp = g >= 0 ? vol_class_entries(vm.gvols, vm.gvoff[g], vm.gvoff[g + 1], x) : 0;
-    return (int32_t)class_count(c, x, node) - 1 + grp - vol_out_holders(pre, vm, j0, b, j, x);
-  }
-};
-// NodeInfo.AddPod / RemovePod on the node's attached volumes (volume_bind's
-// rule on the thread's copy): the holdings [e0, e1) of one pod.  A classless
-// holding moves its family's count by arg.  A class holding moves it by one
-// when no other pod on the node holds the volume: for a class of the
-// preemptor's that is held[i] (moved here too), for any other class
-// others(cls, e) counts the other holders.  Families the preemptor has no use
-// of are not read.
-template <typename OTHERS, typename HOLD>
-__device__ __forceinline__ void vol_add(VolRow& v, HOLD&& h, const int32_t (&cls)[KSIM_MAX_USES],
-                                        const PreemptVol& vm, const VolHold* __restrict__ ents, int32_t e0,
-                                        int32_t e1, int sign, OTHERS others) {
-  for (int32_t e = e0; e < e1; e++) {
-    const VolHold x = ents[e];
-    if (!((vm.fams >> x.fam) & 1u)) continue;
-    int64_t d = (int64_t)sign * x.arg;
-    if (x.cls >= 0) {
-      bool mine = false;
-      int32_t rest = 0;                                  // the volume's other holders on the node
-#pragma unroll
-      for (int i = 0; i < KSIM_MAX_USES; i++)
-        if (((vm.uses >> i) & 1u) && cls[i] == x.cls) {
-          mine = true;
-          rest = (int32_t)(sign < 0 ? h.held[i] - 1 : h.held[i]);
-          h.held[i] += sign;
-        }
-      if (!mine) rest = others(x.cls, e);
-      d = rest == 0 ? sign : 0;
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      cls[i] = kNoPortClass;
+      held[i] = 0;
+      if ((x.a.port_mask >> i) & 1u) {
+        cls[i] = load_use(x.U, i).cls;
+        held[i] = (int32_t)class_count(x.a.c, cls[i], x.node);
+      }
     }
-#pragma unroll
-    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
-      if (k == x.fam) v.att[k] += d;
   }
-}
-// nodevolumelimits Filter on the moved counts (volume_limit_fails' rule, 64-bit
-// sums): per family of the preemptor's, new = its classless volumes (own[f])
-// plus its class volumes no pod left on the node holds.  ufam: four bits per
-// use, the family of volume use i.
-template <typename HOLD>
-__device__ __forceinline__ bool vol_fails(const VolRow& v, const HOLD& h, const int32_t (&cls)[KSIM_MAX_USES],
-                                          const PreemptVol& vm, uint64_t ufam,
-                                          const int64_t (&own)[KSIM_MAX_VOL_FAMILIES]) {
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
-    if (!((vm.fams >> k) & 1u)) continue;
-    int64_t add = own[k];
+  __device__ __forceinline__ void move(const Trial& x, int32_t j, int sign) {
+    count_add(held, cls, x.a.pre.adds, x.a.pre.aoff[j], x.a.pre.aoff[j + 1], sign);
+  }
+  __device__ __forceinline__ void move_group(const Trial& x) {
+    count_add(held, cls, x.a.pre.gadds, x.a.pre.goff[x.g], x.a.pre.goff[x.g + 1], 1);
+  }
+  // nodeports Filter.  among: the port uses, for a form whose volume side keeps
+  // its holders here (a held volume class is no conflict)
+  __device__ __forceinline__ bool fails(uint32_t among = ~0u) const {
+    bool hit = false;
 #pragma unroll
     for (int i = 0; i < KSIM_MAX_USES; i++)
-      if (((vm.uses >> i) & 1u) && cls[i] >= 0 && (int)((ufam >> (4 * i)) & 15u) == k) add += h.held[i] == 0;
-    const bool csi = (vm.csi >> k) & 1u;
-    if (v.lim[k] != 2147483647 && v.att[k] + add > (int64_t)v.lim[k] && (!csi || add > 0)) bad = true;
+      if (((among >> i) & 1u) && held[i] > 0) hit = true;
+    return hit;
   }
-  return bad;
-}
+};
 
-// The preemptor's filter-read uses in the domain form (kernel argument, bit i =
-// use i): its InterPodAffinity uses by role when the profile filters on them,
-// and that filter's place in the profile.  All zero: no domain form.
-struct PreemptDom {
-  uint32_t aff, anti, exist;
-  int32_t ipa_index;
-};
-// The spread form's argument (the other forms keep PreemptDom, and with it
-// their kernel arguments): the preemptor's DoNotSchedule spread uses when the
-// profile filters on PodTopologySpread, that filter's place, and per use
-// {the minimum over the present domains, the value id of one arg-min, the
-// minimum over the others} (k_preempt_spread_mins; [KSIM_MAX_USES][3]).
-struct PreemptSpread : PreemptDom {
-  uint32_t hard;
-  int32_t pts_index;
-  int64_t* smin;
-};
-// NodeInfo.AddPod / RemovePod and PreFilterExtensions.AddPod / RemovePod of one
-// pod (or nominated group) on the node's row: sign x count of every add whose
-// class a filter-read use reads.  A use whose key the node lacks (t.v[i] == 0)
-// moves too, but no Filter reads its count (upstream leaves its maps alone).
-// A DoNotSchedule spread use's entry carries the presence marks above its
-// count (kDomMarkShift): the count of the pods the status pass summed never
-// goes below zero, so adding to the whole entry leaves the marks alone; such a
-// use moves only on a node that is eligible for it (its cls[i] is
-// kNoPortClass elsewhere: podtopologyspread's updateWithPod).
-__device__ __forceinline__ void topo_add(TopoRow& t, const int32_t (&cls)[KSIM_MAX_USES],
-                                         const ksim_class_add* __restrict__ adds, int32_t e0, int32_t e1, int sign) {
-  for (int32_t e = e0; e < e1; e++) {
-    const ksim_class_add x = adds[e];
-#pragma unroll
-    for (int i = 0; i < KSIM_MAX_USES; i++)
-      if (cls[i] == x.cls) t.x[i] += (int64_t)sign * x.count;
-  }
-}
+// ---- the row side --------------------------------------------------------------
 // podtopologyspread Filter on the moved row -> 0 or KSIM_PTS_* (the first
 // failing constraint's reason, as pts_filter).  Constraint i fails for skew
 // when match + selfMatch - crit > maxSkew, crit = min(match, others_i) on a
@@ -272,15 +217,385 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
     if (((aff >> i) & 1u) && t.v[i] != 0 && t.x[i] > 0) any = true;
   return any ? kTopoAffinityNonEmpty : 0u;
 }
+// The node's TopoRow under the roles the dry run's filters read (mm): ports,
+// affinity and spread counts move by the class adds.  A use whose key the node
+// lacks (t.v[i] == 0) moves too, but no Filter reads its count.  SPREAD:
+// PodTopologySpread is re-run as well.  In node n's dry run only n's pods move,
+// so per constraint only the count of n's own domain moves and the critical
+// path is min(own count, others_i): the minimum over the other present domains
+// (dm.smin: the second minimum when n's value is the arg-min), fixed for the
+// dry run and folded into thr[i].  A DoNotSchedule use's entry carries the
+// presence marks above its count (kDomMarkShift); the count never goes below
+// zero, so adding to the whole entry leaves them alone.  A pod of n moves
+// constraint i only when n is eligible for it (every hard constraint's key on
+// n, and n passes i's node inclusion policies, as k_topo_prefilter counted;
+// cls[i] is kNoPortClass elsewhere: updateWithPod) and elsewhere the verdict is
+// the status pass's.
+template <bool SPREAD>
+struct RowSide {
+  using Args = std::conditional_t<SPREAD, PreemptSpread, PreemptDom>;
+  TopoRow t;
+  int32_t cls[KSIM_MAX_USES];
+  UseMasks mm;
+  bool outside;
+  uint32_t elig, over;                                  // SPREAD: the hard uses this node's pods move; spread_filter
+  int64_t thr[KSIM_MAX_USES];                           // SPREAD: per hard use, the count the row may reach
 
-// SelectVictimsOnNode of one potential node.  PORTS: the dry run re-runs
-// NodePorts beside NodeResourcesFit (the preemptor has port uses and the
-// profile filters on them); fit: the profile has NodeResourcesFit.
-// DOM (the domain form): the dry run re-runs NodePorts and InterPodAffinity on
-// the node's TopoRow.  The node failed at Fit, NodePorts or InterPodAffinity;
-// the last is a potential node only for an anti-affinity reason, which the
-// thread re-derives from the row (with the nominated group on it: pass 1).
-// PDB (the PDB form): the table carries budgets (pre.poff / pids / pallowed).
+  // A node that failed InterPodAffinity or PodTopologySpread is a potential
+  // node only for an anti-affinity / the skew reason (resolvable, below).
+  static __device__ __forceinline__ bool potential(uint32_t f, const PreemptCommon& a, const Args& dm, bool& at_ipa,
+                                                   bool& at_pts) {
+    at_ipa = (dm.aff | dm.anti | dm.exist) != 0 && f == (uint32_t)dm.ipa_index;
+    if constexpr (SPREAD) at_pts = dm.hard != 0 && f == (uint32_t)dm.pts_index;
+    return failed_fit_or_ports(f, a) || at_ipa || at_pts;
+  }
+  __device__ __forceinline__ void init(const Trial& x, const Args& dm) {
+    mm = UseMasks{};
+    mm.port = x.a.port_mask;
+    mm.aff = dm.aff;
+    mm.anti = dm.anti;
+    mm.exist = dm.exist;
+    outside = false;
+    elig = over = 0;
+    const uint32_t read = x.a.port_mask | dm.aff | dm.anti | dm.exist;
+    load_topo_row(x.a.c, x.U, x.p.use_count, x.plan.m, x.a.s, x.a.P.ptab, x.node, t);
+    if constexpr (SPREAD) {                             // updateWithPod's node tests, once per node
+      bool all_hard = true;                             // nodeLabelsMatchSpreadConstraints
+#pragma unroll
+      for (int i = 0; i < KSIM_MAX_USES; i++)
+        if (((dm.hard >> i) & 1u) && t.v[i] == 0) all_hard = false;
+      if (all_hard) {                                   // matchNodeInclusionPolicies, as k_topo_prefilter
+        const UseMasks& m = x.plan.m;
+        const bool aff_ok = (m.honor_aff & dm.hard) ? required_node_affinity_match(x.a.c, x.a.P, x.p, x.node) : true;
+        const bool taint_ok = (m.honor_taints & dm.hard) ? !node_has_untolerated_taint(x.a.c, x.p, x.node) : true;
+        elig = dm.hard & ~(aff_ok ? 0u : m.honor_aff) & ~(taint_ok ? 0u : m.honor_taints);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      cls[i] = kNoPortClass;
+      if ((read >> i) & 1u) cls[i] = load_use(x.U, i).cls;
+      if (((dm.aff >> i) & 1u) && t.v[i] != 0 && x.a.pre.afftot[i] - t.x[i] > 0) outside = true;
+      if constexpr (SPREAD) {
+        thr[i] = 0;
+        if ((dm.hard >> i) & 1u) {
+          const int64_t* mn = dm.smin + 3 * i;          // {min1, the arg-min's value id, min2}
+          const ksim_topo_use u = load_use(x.U, i);
+          const bool mine = (elig >> i) & 1u;
+          // others_i(n): the second minimum when n's own domain is the arg-min
+          const int64_t oth = mine && (int64_t)t.v[i] == mn[1] ? mn[2] : mn[0];
+          const int64_t lim = (int64_t)((x.plan.m.self_match >> i) & 1u) - (int64_t)u.arg;
+          thr[i] = oth - lim;
+          if (mine && lim > 0) over |= 1u << i;
+          if (mine) cls[i] = u.cls;
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void move(const Trial& x, int32_t j, int sign) {
+    count_add(t.x, cls, x.a.pre.adds, x.a.pre.aoff[j], x.a.pre.aoff[j + 1], sign);
+  }
+  __device__ __forceinline__ void move_group(const Trial& x, const Args&) {
+    count_add(t.x, cls, x.a.pre.gadds, x.a.pre.goff[x.g], x.a.pre.goff[x.g + 1], 1);
+  }
+  // The status pass's detail, re-derived from the row (with the nominated group
+  // on it: pass 1): false for UnschedulableAndUnresolvable, no potential node.
+  __device__ __forceinline__ bool resolvable(const Trial& x, const Args& dm, bool at_ipa, bool at_pts) const {
+    if constexpr (SPREAD) {
+      if (at_pts && spread_filter(dm.hard, over, thr, t) == KSIM_PTS_MISSING_LABEL) return false;
+    }
+    if (at_ipa) {
+      const uint32_t why = ipa_filter(mm, x.p, affinity_flags(dm.aff, outside, t), t);
+      if (why != KSIM_IPA_ANTI_AFFINITY && why != KSIM_IPA_EXISTING_ANTI) return false;
+    }
+    return true;
+  }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args& dm) const {
+    if constexpr (SPREAD) {
+      if (spread_fails(dm.hard, over, thr, t)) return true;
+    }
+    return node_port_conflict(mm, t) || ipa_filter(mm, x.p, affinity_flags(dm.aff, outside, t), t) != 0;
+  }
+};
+
+// ---- the volume side -----------------------------------------------------------
+// Pods of the node's suffix [j0, b) that are out of the trial state (bit 0 of
+// their flag; row `skip` apart) and hold volume class `cls`: a direct count,
+// quadratic in the node's victims like the PDB split's.
+__device__ __forceinline__ int32_t vol_out_holders(const Trial& x, const PreemptVol& vm, int32_t skip, int32_t cls) {
+  int32_t n = 0;
+  for (int32_t k = x.j0; k < x.b; k++) {
+    if (k == skip || !(x.a.pre.vflag[k] & 1)) continue;
+    for (int32_t e = vm.voff[k]; e < vm.voff[k + 1]; e++) n += vm.vols[e].cls == cls;
+  }
+  return n;
+}
+// Entries [e0, e1) of `ents` that hold class `cls`
+__device__ __forceinline__ int32_t vol_class_entries(const VolHold* __restrict__ ents, int32_t e0, int32_t e1,
+                                                     int32_t cls) {
+  int32_t n = 0;
+  for (int32_t e = e0; e < e1; e++) n += ents[e].cls == cls;
+  return n;
+}
+// The node's attached volumes per family of the preemptor's (att, c.vol_attached
+// moved with every pod taken out or put back) and their limits, the family of
+// each volume use (ufam, four bits each) and per family the preemptor's
+// classless volumes (own).  A shared volume the preemptor mounts is a count
+// class; the node's holders of it are hv.held[i] under hv.cls[i], both in the
+// side the form keeps beside this one and hands in (Holders; the ids are
+// disjoint from the port and selector classes, and no add names one; a
+// classless volume use keeps kNoPortClass).  Everything is indexed by unrolled
+// constants only, so it stays in registers.
+template <class H>
+struct Holders {
+  int32_t (&cls)[KSIM_MAX_USES];
+  H (&held)[KSIM_MAX_USES];
+};
+struct VolSide {
+  int64_t att[KSIM_MAX_VOL_FAMILIES];
+  int32_t lim[KSIM_MAX_VOL_FAMILIES];
+  uint64_t ufam;
+  int64_t own[KSIM_MAX_VOL_FAMILIES];
+
+  // the first failing filter is one of the four limit plugins (at: their places; they return plain Unschedulable)
+  static __device__ __forceinline__ bool potential(uint32_t f, const PreemptVol& vm) {
+    bool hit = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t at = (vm.at >> (8 * k)) & 255u;      // 0xff: absent (KSIM_PASSED is no plugin's place)
+      if (at != 255u && f == at) hit = true;
+    }
+    return hit;
+  }
+  template <class H>
+  __device__ __forceinline__ void init(const Trial& x, const PreemptVol& vm, const Holders<H>& hv) {
+    ufam = 0;
+#pragma unroll
+    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
+      own[k] = 0;
+      att[k] = 0;
+      lim[k] = 2147483647;
+      if ((vm.fams >> k) & 1u) {
+        att[k] = x.a.c.vol_attached[(size_t)k * x.a.c.n + x.node];
+        lim[k] = x.a.c.vol_limit[(size_t)k * x.a.c.n + x.node];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      if (!((vm.uses >> i) & 1u)) continue;
+      const ksim_topo_use u = load_use(x.U, i);          // the device copy: family in _pad
+      ufam |= (uint64_t)(u._pad & 15) << (4 * i);
+      if (u.cls >= 0) {
+        hv.cls[i] = u.cls;
+        hv.held[i] = (H)class_count(x.a.c, u.cls, x.node);    // (a TopoRow's entry of a volume use holds just that)
+      } else {
+#pragma unroll
+        for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
+          if (k == u._pad) own[k] += u.arg;
+      }
+    }
+  }
+  // NodeInfo.AddPod / RemovePod on the node's attached volumes (volume_bind's
+  // rule on the thread's copy): the holdings [e0, e1) of one pod.  A classless
+  // holding moves its family's count by arg.  A class holding moves it by one
+  // when no other pod on the node holds the volume: for a class of the
+  // preemptor's that is hv.held[i] (moved here too), for any other class
+  // others(cls, e) counts the other holders.  Families the preemptor has no use
+  // of are not read.
+  template <class H, typename OTHERS>
+  __device__ __forceinline__ void add(const PreemptVol& vm, const Holders<H>& hv, const VolHold* __restrict__ ents,
+                                      int32_t e0, int32_t e1, int sign, OTHERS others) {
+    for (int32_t e = e0; e < e1; e++) {
+      const VolHold x = ents[e];
+      if (!((vm.fams >> x.fam) & 1u)) continue;
+      int64_t d = (int64_t)sign * x.arg;
+      if (x.cls >= 0) {
+        bool mine = false;
+        int32_t rest = 0;                                  // the volume's other holders on the node
+#pragma unroll
+        for (int i = 0; i < KSIM_MAX_USES; i++)
+          if (((vm.uses >> i) & 1u) && hv.cls[i] == x.cls) {
+            mine = true;
+            rest = (int32_t)(sign < 0 ? hv.held[i] - 1 : hv.held[i]);
+            hv.held[i] += sign;
+          }
+        if (!mine) rest = others(x.cls, e);
+        d = rest == 0 ? sign : 0;
+      }
+#pragma unroll
+      for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
+        if (k == x.fam) att[k] += d;
+    }
+  }
+  // Row j's holdings.  The holders of a class the preemptor does not use, row j
+  // apart: the device's count (every bound holder of the node, whatever its
+  // priority, row j among them) and the nominated group's, less the rows that
+  // are out.
+  template <class H>
+  __device__ __forceinline__ void move(const Trial& x, const PreemptVol& vm, const Holders<H>& hv, int32_t j, int sign) {
+    add(vm, hv, vm.vols, vm.voff[j], vm.voff[j + 1], sign, [&](int32_t cl, int32_t) {
+      const int32_t grp = x.g >= 0 ? vol_class_entries(vm.gvols, vm.gvoff[x.g], vm.gvoff[x.g + 1], cl) : 0;
+      return (int32_t)class_count(x.a.c, cl, x.node) - 1 + grp - vol_out_holders(x, vm, j, cl);
+    });
+  }
+  // The group's volumes, each pod after the ones before it
+  template <class H>
+  __device__ __forceinline__ void move_group(const Trial& x, const PreemptVol& vm, const Holders<H>& hv) {
+    const int32_t g0 = vm.gvoff[x.g];
+    add(vm, hv, vm.gvols, g0, vm.gvoff[x.g + 1], 1, [&](int32_t cl, int32_t e) {
+      return class_count(x.a.c, cl, x.node) + vol_class_entries(vm.gvols, g0, e, cl);
+    });
+  }
+  // nodevolumelimits Filter on the moved counts (volume_limit_fails' rule, 64-bit
+  // sums): per family of the preemptor's, new = its classless volumes (own[f])
+  // plus its class volumes no pod left on the node holds.
+  template <class H>
+  __device__ __forceinline__ bool fails(const PreemptVol& vm, const Holders<H>& hv) const {
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
+      if (!((vm.fams >> k) & 1u)) continue;
+      int64_t add = own[k];
+#pragma unroll
+      for (int i = 0; i < KSIM_MAX_USES; i++)
+        if (((vm.uses >> i) & 1u) && hv.cls[i] >= 0 && (int)((ufam >> (4 * i)) & 15u) == k) add += hv.held[i] == 0;
+      const bool csi = (vm.csi >> k) & 1u;
+      if (lim[k] != 2147483647 && att[k] + add > (int64_t)lim[k] && (!csi || add > 0)) bad = true;
+    }
+    return bad;
+  }
+};
+
+// ---- the forms -----------------------------------------------------------------
+// Args: the form's kernel argument.  potential(): the node's first failing
+// filter is one the form re-runs (at_ipa / at_pts: InterPodAffinity's /
+// PodTopologySpread's, whose detail resolvable() then asks for).  init(): side
+// by side, its start and then the node's nominated group (the nominated pods
+// stay: pass 1).  fails(): false = the pod passes; a form that re-runs another
+// filter re-runs NodeResourcesFit only when the profile has it.  kOut:
+// bit 0 of a row's flag says "out of the trial state" during the trials too
+// (the volume side reads it).
+template <class SIDE, class... A>
+__device__ __forceinline__ void start(SIDE& side, const Trial& x, const A&... a) {
+  side.init(x, a...);
+  if (x.g >= 0) side.move_group(x, a...);
+}
+struct FormBase {
+  static constexpr uint8_t kOut = 0;
+  RequestSide req;
+  template <class A>
+  __device__ __forceinline__ bool resolvable(const Trial&, const A&, bool, bool) const {
+    return true;
+  }
+};
+struct FreeForm : FormBase {
+  using Args = PreemptDom;                               // not read
+  static __device__ __forceinline__ bool potential(uint32_t f, const PreemptCommon& a, const Args&, bool&, bool&) {
+    return failed_fit_or_ports(f, a);
+  }
+  __device__ __forceinline__ void init(const Trial& x, const Args&) { start(req, x); }
+  __device__ __forceinline__ void move_row(const Trial& x, const Args&, int32_t j, int sign) { req.move(x, j, sign); }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args&) { return req.fails(x, true); }
+};
+struct PortsForm : FormBase {                            // (FreeForm's kernels and potential nodes)
+  using Args = FreeForm::Args;
+  PortSide ports;
+  __device__ __forceinline__ void init(const Trial& x, const Args&) {
+    start(req, x);
+    start(ports, x);
+  }
+  __device__ __forceinline__ void move_row(const Trial& x, const Args&, int32_t j, int sign) {
+    req.move(x, j, sign);
+    ports.move(x, j, sign);
+  }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args&) {
+    return req.fails(x) || ports.fails();
+  }
+};
+template <bool SPREAD>
+struct RowForm : FormBase {
+  using Args = typename RowSide<SPREAD>::Args;
+  RowSide<SPREAD> row;
+  static constexpr auto potential = &RowSide<SPREAD>::potential;
+  __device__ __forceinline__ void init(const Trial& x, const Args& dm) {
+    start(req, x);
+    start(row, x, dm);
+  }
+  __device__ __forceinline__ bool resolvable(const Trial& x, const Args& dm, bool at_ipa, bool at_pts) const {
+    return row.resolvable(x, dm, at_ipa, at_pts);
+  }
+  __device__ __forceinline__ void move_row(const Trial& x, const Args&, int32_t j, int sign) {
+    req.move(x, j, sign);
+    row.move(x, j, sign);
+  }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args& dm) {
+    return req.fails(x) || row.fails(x, dm);
+  }
+};
+using DomForm = RowForm<false>;
+using SpreadForm = RowForm<true>;
+// The ports side moves only for a preemptor with port uses (port_mask,
+// block-uniform); its held[] keeps the shared volumes' holders either way.
+struct VolumeForm : FormBase {
+  using Args = PreemptVol;
+  static constexpr uint8_t kOut = 1;
+  PortSide ports;
+  VolSide vol;
+  __device__ __forceinline__ Holders<int32_t> hv() { return {ports.cls, ports.held}; }
+  static __device__ __forceinline__ bool potential(uint32_t f, const PreemptCommon& a, const Args& vm, bool&, bool&) {
+    return failed_fit_or_ports(f, a) || VolSide::potential(f, vm);
+  }
+  __device__ __forceinline__ void init(const Trial& x, const Args& vm) {
+    start(req, x);
+    ports.init(x);
+    vol.init(x, vm, hv());
+    if (x.g >= 0 && x.a.port_mask) ports.move_group(x);
+    if (x.g >= 0) vol.move_group(x, vm, hv());
+  }
+  __device__ __forceinline__ void move_row(const Trial& x, const Args& vm, int32_t j, int sign) {
+    req.move(x, j, sign);
+    if (x.a.port_mask) ports.move(x, j, sign);
+    vol.move(x, vm, hv(), j, sign);
+  }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args& vm) {
+    return req.fails(x) || ports.fails(x.a.port_mask) || vol.fails(vm, hv());
+  }
+};
+// One TopoRow, moved by the rows' class adds, and the volume side, moved by
+// their holdings; a shared volume's holder count is the row's own entry of the
+// volume use (load_topo_row put the node's class count there, and no add names
+// a volume class, so only the volume side moves it).
+struct FullForm : FormBase {
+  using Args = PreemptFull;
+  static constexpr uint8_t kOut = 1;
+  RowSide<true> row;
+  VolSide vol;
+  __device__ __forceinline__ Holders<int64_t> hv() { return {row.cls, row.t.x}; }
+  static __device__ __forceinline__ bool potential(uint32_t f, const PreemptCommon& a, const Args& fa, bool& at_ipa,
+                                                   bool& at_pts) {
+    const bool at_row = RowSide<true>::potential(f, a, fa.ds, at_ipa, at_pts);
+    return at_row || VolSide::potential(f, fa.vm);
+  }
+  __device__ __forceinline__ void init(const Trial& x, const Args& fa) {
+    start(req, x);
+    start(row, x, fa.ds);
+    start(vol, x, fa.vm, hv());
+  }
+  __device__ __forceinline__ bool resolvable(const Trial& x, const Args& fa, bool at_ipa, bool at_pts) const {
+    return row.resolvable(x, fa.ds, at_ipa, at_pts);
+  }
+  __device__ __forceinline__ void move_row(const Trial& x, const Args& fa, int32_t j, int sign) {
+    req.move(x, j, sign);
+    row.move(x, j, sign);
+    vol.move(x, fa.vm, hv(), j, sign);
+  }
+  __device__ __forceinline__ bool fails(const Trial& x, const Args& fa) {
+    return req.fails(x) || row.fails(x, fa.ds) || vol.fails(fa.vm, hv());
+  }
+};
+
+// SelectVictimsOnNode of one potential node, in the form's trial state.
+// PDB: the table carries budgets (pre.poff / pids / pallowed).
 // filterPodsWithPDBViolation walks the suffix most important first with a
 // fresh copy of every budget and decrements each budget a pod matches; the pod
 // violates when one of them went below zero, i.e. when the rows of [j0, j]
@@ -289,210 +604,28 @@ __device__ __forceinline__ uint32_t affinity_flags(uint32_t aff, bool outside, c
 // the number of budgets).  The violating rows are reprieved first, then the
 // others, so the victims list need not be sorted by priority: `high` is the
 // first victim appended, `early` follows the true maximum priority.
-// SPREAD (the spread form; implies DOM): the dry run also re-runs
-// PodTopologySpread on the row.  In node n's dry run only n's pods move, so
-// per constraint only the count of n's own domain moves and the critical path
-// is min(own count, others_i): the minimum over the other present domains
-// (dm.smin: the second minimum when n's value is the arg-min), fixed for the
-// whole dry run and folded into thr[i].  A pod of n moves constraint i only when n is
-// eligible for it (every hard constraint's key on n, and n passes i's node
-// inclusion policies: what k_topo_prefilter counted); elsewhere the verdict
-// is the status pass's.  A node that failed PodTopologySpread is a potential
-// node only for the skew reason, re-derived from the row like
-// InterPodAffinity's.
-// VOL (the volume form; PORTS with it): the dry run also re-runs the node
-// volume limit plugins of the profile.  The thread keeps the node's attached
-// count per family of the preemptor's (VolRow) and, in held[], the node's count
-// of each shared volume the preemptor mounts, beside its port classes (the ids
-// are disjoint; a classless volume use keeps kNoPortClass).  Both move with
-// the rows' holdings (vm.voff / vols); bit 0 of a row's flag says "out of the
-// trial state" from the first removal on, which is what it says at the end.
-// VOL with DOM and SPREAD (the full form): both sides at once.  Ports, affinity
-// and spread counts move in the TopoRow by the class adds; VolRow moves by the
-// holdings, and a shared volume's holder count is the row's own entry of the
-// volume use (RowHold) instead of held[], which the full form does not keep.
-template <bool PORTS, bool DOM = false, bool PDB = false, bool SPREAD = false, typename DM = PreemptDom,
-          bool VOL = false, typename VM = NoVol>
-__device__ __forceinline__ void select_victims(const DevCluster& c, const DevPods& P, const DevScratch& s,
-                                               const ksim_pod& p, const PodPlan& plan, const ksim_topo_use* U,
-                                               const DevPreempt& pre, int32_t node, int32_t prio, bool fit,
-                                               uint32_t port_mask, const DM& dm, bool at_ipa, bool at_pts,
-                                               PreemptNode& out, const VM& vm = VM{}) {
-  const int32_t a = pre.off[node], b = pre.off[node + 1];
+// Bit 0 of a row's flag: "victim" at the end and, in a form with kOut, "out of
+// the trial state" from the row's removal on (the PDB split keeps it, a reprieve clears it).
+template <class FORM, bool PDB>
+__device__ __forceinline__ void select_victims(Trial& x, const typename FORM::Args& fa, bool at_ipa, bool at_pts,
+                                               PreemptNode& out) {
+  const DevPreempt& pre = x.a.pre;
+  const int32_t a = pre.off[x.node], b = pre.off[x.node + 1];
   int32_t j0 = a;
-  while (j0 < b && pre.prio[j0] >= prio) j0++;       // lower priorities: the suffix [j0, b)
+  while (j0 < b && pre.prio[j0] >= x.a.prio) j0++;     // lower priorities: the suffix [j0, b)
   for (int32_t j = a; j < j0; j++) pre.vflag[j] = 0;   // no stale flags from an earlier preemptor
-  NodeRow r = load_row(c, node);
-  const int32_t g = pre.nslot ? pre.nslot[node] : -1;
-  if (g >= 0) {                                         // the nominated pods stay (pass 1)
-    const int64_t* q = pre.nreq + (size_t)g * (KSIM_PREEMPT_REQ + 1);
-    row_add_req(r, q, 1, c.n_scalar);
-    r.num_pods += (int32_t)q[KSIM_PREEMPT_REQ] - 1;
-  }
-  int32_t cls[KSIM_MAX_USES];
-  PortHold h;
-  TopoRow t;
-  UseMasks mm{};                                        // the roles the dry run's filters read
-  bool outside = false;
-  VolRow vr;                                            // VOL: the families' moved counts and limits
-  uint64_t ufam = 0;                                    // VOL: the family of each volume use, four bits each
-  int64_t own[KSIM_MAX_VOL_FAMILIES];                   // VOL: per family, the preemptor's classless volumes
-  uint32_t elig = 0, over = 0;                          // SPREAD: the hard uses this node's pods move; spread_filter
-  int64_t thr[KSIM_MAX_USES];                           // SPREAD: per hard use, the count the row may reach
-  if (DOM) {
-    mm.port = port_mask;
-    mm.aff = dm.aff;
-    mm.anti = dm.anti;
-    mm.exist = dm.exist;
-    const uint32_t read = port_mask | dm.aff | dm.anti | dm.exist;
-    load_topo_row(c, U, p.use_count, plan.m, s, P.ptab, node, t);
-    if constexpr (SPREAD) {                             // updateWithPod's node tests, once per node
-      bool all_hard = true;                             // nodeLabelsMatchSpreadConstraints
-#pragma unroll
-      for (int i = 0; i < KSIM_MAX_USES; i++)
-        if (((dm.hard >> i) & 1u) && t.v[i] == 0) all_hard = false;
-      if (all_hard) {                                   // matchNodeInclusionPolicies, as k_topo_prefilter
-        const bool aff_ok = (plan.m.honor_aff & dm.hard) ? required_node_affinity_match(c, P, p, node) : true;
-        const bool taint_ok = (plan.m.honor_taints & dm.hard) ? !node_has_untolerated_taint(c, p, node) : true;
-        elig = dm.hard & ~(aff_ok ? 0u : plan.m.honor_aff) & ~(taint_ok ? 0u : plan.m.honor_taints);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < KSIM_MAX_USES; i++) {
-      cls[i] = kNoPortClass;
-      if ((read >> i) & 1u) cls[i] = load_use(U, i).cls;
-      if (((dm.aff >> i) & 1u) && t.v[i] != 0 && pre.afftot[i] - t.x[i] > 0) outside = true;
-      if constexpr (SPREAD) {
-        thr[i] = 0;
-        if ((dm.hard >> i) & 1u) {
-          const int64_t* mn = dm.smin + 3 * i;          // {min1, the arg-min's value id, min2}
-          const ksim_topo_use u = load_use(U, i);
-          const bool mine = (elig >> i) & 1u;
-          // others_i(n): the second minimum when n's own domain is the arg-min
-          const int64_t oth = mine && (int64_t)t.v[i] == mn[1] ? mn[2] : mn[0];
-          const int64_t lim = (int64_t)((plan.m.self_match >> i) & 1u) - (int64_t)u.arg;
-          thr[i] = oth - lim;
-          if (mine && lim > 0) over |= 1u << i;
-          if (mine) cls[i] = u.cls;
-        }
-      }
-    }
-    if (g >= 0) topo_add(t, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
-    if constexpr (SPREAD) {
-      if (at_pts && spread_filter(dm.hard, over, thr, t) == KSIM_PTS_MISSING_LABEL)
-        return;                                         // the status pass's detail: UnschedulableAndUnresolvable
-    }
-    if (at_ipa) {                                       // the status pass's InterPodAffinity detail
-      const uint32_t why = ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t);
-      if (why != KSIM_IPA_ANTI_AFFINITY && why != KSIM_IPA_EXISTING_ANTI) return;   // UnschedulableAndUnresolvable
-    }
-    out.potential = 1;
-  }
-  decltype(auto) hv = vol_holder<VOL && DOM>(h, t);      // VOL: the shared volumes' holder counts
-  if constexpr (VOL && DOM) {                           // the full form's volume side, as the volume form's below
-    ufam = 0;
-#pragma unroll
-    for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
-      own[k] = 0;
-      vr.att[k] = 0;
-      vr.lim[k] = 2147483647;
-      if ((vm.fams >> k) & 1u) {
-        vr.att[k] = c.vol_attached[(size_t)k * c.n + node];
-        vr.lim[k] = c.vol_limit[(size_t)k * c.n + node];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < KSIM_MAX_USES; i++) {
-      if (!((vm.uses >> i) & 1u)) continue;
-      const ksim_topo_use u = load_use(U, i);            // the device copy: family in _pad
-      ufam |= (uint64_t)(u._pad & 15) << (4 * i);
-      if (u.cls >= 0) {
-        cls[i] = u.cls;                                  // t.x[i]: the node's holders (load_topo_row); no add names it
-      } else {
-#pragma unroll
-        for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
-          if (k == u._pad) own[k] += u.arg;
-      }
-    }
-    if (g >= 0) {                                        // the group's volumes, each pod after the ones before it
-      const int32_t g0 = vm.gvoff[g];
-      vol_add(vr, hv, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
-        return class_count(c, x, node) + vol_class_entries(vm.gvols, g0, e, x);
-      });
-    }
+  x.j0 = j0, x.b = b, x.g = pre.nslot ? pre.nslot[x.node] : -1;
+  FORM t;
+  t.init(x, fa);
+  if (!t.resolvable(x, fa, at_ipa, at_pts)) return;     // the status pass's detail: UnschedulableAndUnresolvable
+  out.potential = 1;
+  if (FORM::kOut)
     for (int32_t j = j0; j < b; j++) pre.vflag[j] = 0;   // nobody is out yet
-  }
-  if (PORTS) {
-#pragma unroll
-    for (int i = 0; i < KSIM_MAX_USES; i++) {
-      cls[i] = kNoPortClass;
-      h.held[i] = 0;
-      if ((port_mask >> i) & 1u) {
-        cls[i] = load_use(U, i).cls;
-        h.held[i] = (int32_t)class_count(c, cls[i], node);
-      }
-    }
-    if constexpr (VOL) {
-      ufam = 0;
-#pragma unroll
-      for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++) {
-        own[k] = 0;
-        vr.att[k] = 0;
-        vr.lim[k] = 2147483647;
-        if ((vm.fams >> k) & 1u) {
-          vr.att[k] = c.vol_attached[(size_t)k * c.n + node];
-          vr.lim[k] = c.vol_limit[(size_t)k * c.n + node];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < KSIM_MAX_USES; i++) {
-        if (!((vm.uses >> i) & 1u)) continue;
-        const ksim_topo_use u = load_use(U, i);          // the device copy: family in _pad
-        ufam |= (uint64_t)(u._pad & 15) << (4 * i);
-        if (u.cls >= 0) {
-          cls[i] = u.cls;
-          h.held[i] = (int32_t)class_count(c, u.cls, node);
-        } else {
-#pragma unroll
-          for (int k = 0; k < KSIM_MAX_VOL_FAMILIES; k++)
-            if (k == u._pad) own[k] += u.arg;
-        }
-      }
-    }
-    if (g >= 0 && (!VOL || port_mask)) hold_add(h, cls, pre.gadds, pre.goff[g], pre.goff[g + 1], 1);
-    if constexpr (VOL) {
-      if (g >= 0) {                                      // the group's volumes, each pod after the ones before it
-        const int32_t g0 = vm.gvoff[g];
-        vol_add(vr, hv, cls, vm, vm.gvols, g0, vm.gvoff[g + 1], 1, [&](int32_t x, int32_t e) {
-          return class_count(c, x, node) + vol_class_entries(vm.gvols, g0, e, x);
-        });
-      }
-      for (int32_t j = j0; j < b; j++) pre.vflag[j] = 0; // nobody is out yet
-    }
-  }
   for (int32_t j = j0; j < b; j++) {
-    row_add_req(r, pre.req + (size_t)j * KSIM_PREEMPT_REQ, -1, c.n_scalar);
-    if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
-    if constexpr (VOL) {
-      vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
-      pre.vflag[j] = 1;
-    }
-    if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
+    t.move_row(x, fa, j, -1);
+    if (FORM::kOut) pre.vflag[j] = FORM::kOut;
   }
-  // the filters the dry run re-runs: 0 = the pod passes
-  auto fails = [&]() -> bool {
-    if ((!(PORTS || DOM) || fit) && fits_request(r, p, c.n_scalar, c.fit_ignore) != 0) return true;
-    if constexpr (SPREAD) {
-      if (spread_fails(dm.hard, over, thr, t)) return true;
-    }
-    if constexpr (VOL && DOM) {
-      if (vol_fails(vr, hv, cls, vm, ufam, own)) return true;
-    }
-    if (DOM) return node_port_conflict(mm, t) || ipa_filter(mm, p, affinity_flags(dm.aff, outside, t), t) != 0;
-    if constexpr (VOL) return hold_conflict(h, port_mask) || vol_fails(vr, hv, cls, vm, ufam, own);
-    return PORTS && hold_conflict(h);
-  };
-  if (!fails()) {
+  if (!t.fails(x, fa)) {
     out.cand = 1;
     if (PDB) {                                          // filterPodsWithPDBViolation
       for (int32_t j = j0; j < b; j++) {
@@ -503,7 +636,7 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
           for (int32_t e2 = pre.poff[j0]; e2 < pre.poff[j + 1]; e2++) used += pre.pids[e2] == id;
           if (used > pre.pallowed[id]) viol = true;
         }
-        pre.vflag[j] = (viol ? kPreemptViolating : 0) | (VOL ? 1 : 0);
+        pre.vflag[j] = (viol ? kPreemptViolating : 0) | FORM::kOut;
       }
     }
     int32_t nv = 0, nviol = 0, high = 0, top = INT32_MIN;
@@ -515,20 +648,11 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
           mark = pre.vflag[j] & kPreemptViolating;
           if ((mark != 0) != (pass == 0)) continue;
         }
-        const int64_t* q = pre.req + (size_t)j * KSIM_PREEMPT_REQ;
-        row_add_req(r, q, 1, c.n_scalar);
-        if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
-        if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], 1);
-        if constexpr (VOL)
-          vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], 1, VolOthers{c, pre, vm, node, g, j0, b, j});
-        const bool victim = fails();
+        t.move_row(x, fa, j, 1);
+        const bool victim = t.fails(x, fa);
         pre.vflag[j] = (uint8_t)victim | mark;
         if (victim) {
-          row_add_req(r, q, -1, c.n_scalar);
-          if (PORTS && (!VOL || port_mask)) hold_add(h, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
-          if (DOM) topo_add(t, cls, pre.adds, pre.aoff[j], pre.aoff[j + 1], -1);
-          if constexpr (VOL)
-            vol_add(vr, hv, cls, vm, vm.vols, vm.voff[j], vm.voff[j + 1], -1, VolOthers{c, pre, vm, node, g, j0, b, j});
+          t.move_row(x, fa, j, -1);
           if (nv == 0) high = pre.prio[j];
           sum += (int64_t)pre.prio[j] + ((int64_t)INT32_MAX + 1);
           if (PDB) {                                     // GetEarliestPodStartTime on an unsorted list
@@ -559,120 +683,30 @@ __device__ __forceinline__ void select_victims(const DevCluster& c, const DevPod
 // Per node: SelectVictimsOnNode.  res[node] = {potential, candidate (with the
 // PDB violations among the victims above bit 0), victims, the first victim's
 // priority, sum of (priority + 2^31), earliest start among the
-// highest-priority victims}; vflag marks the victims (bit 0) and, in the PDB
-// form, the violating rows (bit 1), in CSR order.  A potential
-// node failed NodeResourcesFit or, for a preemptor with port uses (port_mask),
-// NodePorts or, for one with required pod (anti-)affinity uses (dm),
-// InterPodAffinity with an anti-affinity detail: the filters that return
-// Unschedulable and that the dry run re-runs.  DOM: the domain form, a kernel
-// of its own, so a preemptor without such uses runs the code (and keeps the
-// registers) it had before that form existed.  PDB: the PDB form, likewise
-// kernels of their own, launched only when the table carries budgets.
-// SPREAD: the spread form (ksim_preempt_spread for a preemptor with
-// DoNotSchedule spread uses; DOM with it), kernels of their own again: a node
-// that failed PodTopologySpread for the skew reason is a potential node too.
-template <bool DOM, bool PDB, bool SPREAD = false>
-__global__ __launch_bounds__(256) void k_preempt_nodes(DevCluster c, DevPods P, const DevState* __restrict__ st,
-                                                       DevScratch s, DevPreempt pre, int32_t fit_index,
-                                                       int32_t prio, int32_t port_index, uint32_t port_mask,
-                                                       std::conditional_t<SPREAD, PreemptSpread, PreemptDom> dm) {
+// highest-priority victims}; vflag marks the victims (bit 0) and, with PDB,
+// the violating rows (bit 1), in CSR order.  One instantiation per form and
+// PDB, each a code object of its own; FreeForm's also runs PortsForm, behind
+// one branch on the kernel argument port_mask.
+template <class FORM, bool PDB>
+__global__ __launch_bounds__(256) void k_preempt_nodes(PreemptCommon a, typename FORM::Args fa) {
   const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= c.n) return;
+  if (node >= a.c.n) return;
   PreemptNode out{};
-  out.cand = 0;
-  const uint8_t f = s.fail[node];
-  const ksim_pod& p = P.pods[st->cursor];
-  const ksim_topo_use* U = P.uses + p.use_first;
-  if constexpr (SPREAD) {
-    const bool at_ipa = (dm.aff | dm.anti | dm.exist) != 0 && f == (uint8_t)dm.ipa_index;
-    const bool at_pts = f == (uint8_t)dm.pts_index;
-    if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa || at_pts)
-      select_victims<false, true, PDB, true>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0,
-                                             port_mask, dm, at_ipa, at_pts, out);
-  } else if (DOM) {
-    const bool at_ipa = f == (uint8_t)dm.ipa_index;
-    if ((fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index) || at_ipa)
-      select_victims<false, true, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
-                                  at_ipa, false, out);
-  } else {
-    const bool potential = (fit_index >= 0 && f == (uint8_t)fit_index) || (port_mask && f == (uint8_t)port_index);
-    out.potential = potential;
-    if (potential) {
-      if (port_mask)                                   // kernel argument: one uniform branch
-        select_victims<true, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, fit_index >= 0, port_mask, dm,
-                             false, false, out);
+  const uint32_t f = a.s.fail[node];
+  const ksim_pod& p = a.P.pods[a.st->cursor];
+  Trial x{a, p, a.P.plans[a.st->cursor], a.P.uses + p.use_first, node, -1, 0, 0};
+  bool at_ipa = false, at_pts = false;
+  if (FORM::potential(f, a, fa, at_ipa, at_pts)) {
+    if constexpr (std::is_same_v<FORM, FreeForm>) {
+      if (a.port_mask)                                   // kernel argument: one uniform branch
+        select_victims<PortsForm, PDB>(x, fa, at_ipa, at_pts, out);
       else
-        select_victims<false, false, PDB>(c, P, s, p, P.plans[st->cursor], U, pre, node, prio, true, 0u, dm, false, false,
-                                          out);
+        select_victims<FreeForm, PDB>(x, fa, at_ipa, at_pts, out);
+    } else {
+      select_victims<FORM, PDB>(x, fa, at_ipa, at_pts, out);
     }
   }
-  pre.res[node] = out;
-}
-
-// k_preempt_nodes for a preemptor with KSIM_USE_VOLUME uses (ksim_preempt_volumes):
-// the volume form, kernels of their own with an argument of their own, so the
-// forms above keep theirs.  The four limit plugins return Unschedulable, so a
-// node whose first failing filter is one of them (vm.at: their places in the
-// profile) is a potential node beside Fit's and NodePorts'.
-template <bool PDB>
-__global__ __launch_bounds__(256) void k_preempt_nodes_vol(DevCluster c, DevPods P, const DevState* __restrict__ st,
-                                                           DevScratch s, DevPreempt pre, int32_t fit_index,
-                                                           int32_t prio, int32_t port_index, uint32_t port_mask,
-                                                           PreemptVol vm) {
-  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= c.n) return;
-  PreemptNode out{};
-  out.cand = 0;
-  const uint32_t f = s.fail[node];
-  const ksim_pod& p = P.pods[st->cursor];
-  bool potential = (fit_index >= 0 && f == (uint32_t)fit_index) || (port_mask && f == (uint32_t)port_index);
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t at = (vm.at >> (8 * k)) & 255u;      // 0xff: absent (KSIM_PASSED is no plugin's place)
-    if (at != 255u && f == at) potential = true;
-  }
-  out.potential = potential;
-  if (potential)
-    select_victims<true, false, PDB, false, PreemptDom, true, PreemptVol>(
-        c, P, s, p, P.plans[st->cursor], P.uses + p.use_first, pre, node, prio, fit_index >= 0, port_mask, PreemptDom{},
-        false, false, out, vm);
-  pre.res[node] = out;
-}
-
-// k_preempt_nodes for a preemptor with KSIM_USE_VOLUME uses beside required pod
-// (anti-)affinity or DoNotSchedule spread uses (ksim_preempt_full): the full
-// form, the spread form and the volume form in one thread, kernels of their
-// own again with both arguments.  The thread keeps one TopoRow, moved by
-// topo_add over the rows' class adds (ports, affinity and spread counts), and
-// VolRow, moved by vol_add over the rows' holdings; a shared volume's holder
-// count lives in the row's own entry (no add names a volume class, so only
-// vol_add moves it).  ds.hard may be empty (volumes beside affinity alone):
-// then no use is a spread use and PodTopologySpread's place is not read.
-template <bool PDB>
-__global__ __launch_bounds__(256) void k_preempt_nodes_full(DevCluster c, DevPods P, const DevState* __restrict__ st,
-                                                            DevScratch s, DevPreempt pre, int32_t fit_index,
-                                                            int32_t prio, int32_t port_index, uint32_t port_mask,
-                                                            PreemptSpread ds, PreemptVol vm) {
-  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
-  if (node >= c.n) return;
-  PreemptNode out{};
-  out.cand = 0;
-  const uint32_t f = s.fail[node];
-  const ksim_pod& p = P.pods[st->cursor];
-  const bool at_ipa = (ds.aff | ds.anti | ds.exist) != 0 && f == (uint32_t)ds.ipa_index;
-  const bool at_pts = ds.hard != 0 && f == (uint32_t)ds.pts_index;
-  bool enter = (fit_index >= 0 && f == (uint32_t)fit_index) || (port_mask && f == (uint32_t)port_index) || at_ipa ||
-               at_pts;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t at = (vm.at >> (8 * k)) & 255u;      // 0xff: absent (KSIM_PASSED is no plugin's place)
-    if (at != 255u && f == at) enter = true;
-  }
-  if (enter)
-    select_victims<false, true, PDB, true, PreemptSpread, true, PreemptVol>(
-        c, P, s, p, P.plans[st->cursor], P.uses + p.use_first, pre, node, prio, fit_index >= 0, port_mask, ds, at_ipa,
-        at_pts, out, vm);
-  pre.res[node] = out;
+  a.pre.res[node] = out;
 }
 
 // VolumeBinding and VolumeZone after the removals (ksim_preempt_full, for a
@@ -910,70 +944,25 @@ __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, Dev
   }
 }
 
-void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                    hipStream_t stream, bool filter, int32_t port_index, uint32_t port_mask, int32_t ipa_index,
-                    uint32_t aff, uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin) {
-  const int blocks = (a.c.n + 255) / 256;
-  if (filter) launch_filter_only(a, stream);             // the filter statuses of every node
-  if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
-  if (ipa_index < 0) aff = anti = exist = 0;             // nor the InterPodAffinity uses without that filter
-  if (pts_index < 0) hard = 0;                           // nor the DoNotSchedule spread uses without PodTopologySpread
-  const PreemptDom dm{aff, anti, exist, ipa_index};
-  const bool dom = (aff | anti | exist) != 0, pdb = pre.poff != nullptr;
-  if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
-  if (hard) {                                            // the spread form
-    PreemptSpread ds{};
-    static_cast<PreemptDom&>(ds) = dm;
-    ds.hard = hard;
-    ds.pts_index = pts_index;
-    ds.smin = smin;
-    k_preempt_spread_mins<<<__builtin_popcount(hard), 256, 0, stream>>>(a.c, a.P, a.st, a.s, smin, hard);
-    auto nodes = pdb ? k_preempt_nodes<true, true, true> : k_preempt_nodes<true, false, true>;
-    nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, ds);
-  } else {
-    auto nodes = dom ? (pdb ? k_preempt_nodes<true, true> : k_preempt_nodes<true, false>)
-                     : (pdb ? k_preempt_nodes<false, true> : k_preempt_nodes<false, false>);
-    nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, dm);
-  }
-  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+template <class FORM>
+static void launch_nodes(const PreemptCommon& ca, const typename FORM::Args& fa, hipStream_t stream) {
+  auto nodes = ca.pre.poff != nullptr ? k_preempt_nodes<FORM, true> : k_preempt_nodes<FORM, false>;
+  nodes<<<(ca.c.n + 255) / 256, 256, 0, stream>>>(ca, fa);
 }
 
-void launch_preempt_volumes(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                            hipStream_t stream, int32_t port_index, uint32_t port_mask, const PreemptVol& vm) {
-  const int blocks = (a.c.n + 255) / 256;
-  if (port_index < 0) port_mask = 0;                     // no NodePorts in the profile: port uses are ignored
-  auto nodes = pre.poff != nullptr ? k_preempt_nodes_vol<true> : k_preempt_nodes_vol<false>;
-  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, vm);
-  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
-}
-
-void launch_preempt_full(const LaunchArgs& a, const DevPreempt& pre, int32_t fit_index, int32_t prio,
-                         hipStream_t stream, int32_t port_index, uint32_t port_mask, int32_t ipa_index, uint32_t aff,
-                         uint32_t anti, uint32_t exist, int32_t pts_index, uint32_t hard, int64_t* smin,
-                         const PreemptVol& vm, bool vb, bool vz) {
-  const int blocks = (a.c.n + 255) / 256;
-  if (port_index < 0) port_mask = 0;                     // as launch_preempt: a use whose filter the profile lacks
-  if (ipa_index < 0) aff = anti = exist = 0;             // is in none of the masks
-  if (pts_index < 0) hard = 0;
-  PreemptSpread ds{};
-  ds.aff = aff;
-  ds.anti = anti;
-  ds.exist = exist;
-  ds.ipa_index = ipa_index;
-  ds.hard = hard;
-  ds.pts_index = pts_index;
-  ds.smin = smin;
-  if (aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, aff);
-  if (hard) k_preempt_spread_mins<<<__builtin_popcount(hard), 256, 0, stream>>>(a.c, a.P, a.st, a.s, smin, hard);
-  auto nodes = pre.poff != nullptr ? k_preempt_nodes_full<true> : k_preempt_nodes_full<false>;
-  nodes<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, a.s, pre, fit_index, prio, port_index, port_mask, ds, vm);
-  if (vb || vz) k_preempt_static_veto<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, pre, vb, vz);
-  k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
-}
-
-void launch_preempt_veto(const LaunchArgs& a, const DevPreempt& pre, hipStream_t stream, bool vb, bool vz) {
-  const int blocks = (a.c.n + 255) / 256;
-  k_preempt_static_veto<<<blocks, 256, 0, stream>>>(a.c, a.P, a.st, pre, vb, vz);
+void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& q, hipStream_t stream) {
+  const PreemptCommon ca{a.c, a.P, a.st, a.s, pre, q.fit, q.prio, q.port, q.ports};
+  const PreemptFull fa{{{q.aff, q.anti, q.exist, q.ipa}, q.hard, q.pts, q.smin}, q.vol};
+  // the form: by the uses the dry run reads (q.vol.voff: set for a preemptor with volume uses)
+  const bool dom = q.reads_domains(), vol = q.vol.voff != nullptr;
+  if (q.aff) k_preempt_totals<<<1, 256, 0, stream>>>(a.c, a.P, a.st, pre, q.aff);
+  if (q.hard) k_preempt_spread_mins<<<__builtin_popcount(q.hard), 256, 0, stream>>>(a.c, a.P, a.st, a.s, q.smin, q.hard);
+  if (vol && dom && q.vol.uses) launch_nodes<FullForm>(ca, fa, stream);
+  else if (vol && !dom) launch_nodes<VolumeForm>(ca, fa.vm, stream);
+  else if (q.hard) launch_nodes<SpreadForm>(ca, fa.ds, stream);
+  else if (dom) launch_nodes<DomForm>(ca, fa.ds, stream);
+  else launch_nodes<FreeForm>(ca, fa.ds, stream);
+  if (q.vb || q.vz) k_preempt_static_veto<<<(a.c.n + 255) / 256, 256, 0, stream>>>(a.c, a.P, a.st, pre, q.vb, q.vz);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 

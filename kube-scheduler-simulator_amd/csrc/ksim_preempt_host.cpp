@@ -194,36 +194,36 @@ extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_
   return ksim_preempt_nominated(h, ps, pod_index, priority, nullptr, 0, nullptr, nullptr, nullptr, out);
 }
 
-// The dry run behind ksim_preempt / ksim_preempt_nominated (spread = false:
-// DoNotSchedule spread uses are refused), ksim_preempt_spread and
-// ksim_preempt_volumes (volumes = true: KSIM_USE_VOLUME uses are accepted) and
-// ksim_preempt_full (full = true: every mix of uses is accepted, and a
-// preemptor with volume groups has VolumeBinding / VolumeZone re-run).
-static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
-                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes, const int32_t* first,
-                       const int32_t* count, ksim_preempt_out* out, bool spread, bool volumes = false,
-                       bool full = false) {
-  int rc = ensure_ready(h);
-  if (rc) return rc;
+// The entry point a dry run came through (plain: ksim_preempt / _nominated), which says what it accepts:
+//   a KSIM_USE_VOLUME use     through `volumes` (beside no affinity or spread use) and `full`;
+//   a KSIM_USE_PTS_HARD use   through `spread` and `full`.
+// Through `full` a preemptor with volume groups also has VolumeBinding / VolumeZone re-run.
+enum class PreemptEntry { plain, spread, volumes, full };
+struct NominatedGroups {   // of one call: pods [first[k], first[k] + count[k]) of ps on node nodes[k], k < n
+  const ksim_pod_set* ps;
+  int32_t n;
+  const int32_t *nodes, *first, *count;
+};
+
+static int preempt_check_args(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, const NominatedGroups& ng,
+                              const ksim_preempt_out* out, PreemptEntry entry) {
+  int rc;
   if (!ps || !out || pod_index < 0 || pod_index >= ps->n_pods || !ps->pods)
     return set_err(h, KSIM_E_INVALID, "bad pod set / index");
-  if (n_groups < 0 || (n_groups > 0 && (!nps || !nps->pods || !gnodes || !first || !count)))
+  if (ng.n < 0 || (ng.n > 0 && (!ng.ps || !ng.ps->pods || !ng.nodes || !ng.first || !ng.count)))
     return set_err(h, KSIM_E_INVALID, "bad nominated-node groups");
-  const bool vol_form = has_volume_use(ps, pod_index);   // the volume form of k_preempt_nodes
-  if (vol_form && !volumes && !full)
+  if (has_volume_use(ps, pod_index) && entry != PreemptEntry::volumes && entry != PreemptEntry::full)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_VOLUME use (the dry run does not "
                                           "re-run the node volume limit plugins)");
-  {
-    std::vector<uint8_t> seen((size_t)std::max(h->dc.n, 1), 0);
-    for (int32_t k = 0; k < n_groups; k++) {
-      if (gnodes[k] < 0 || gnodes[k] >= h->dc.n || seen[gnodes[k]])
-        return set_err(h, KSIM_E_INVALID, "nominated node out of range or repeated");
-      seen[gnodes[k]] = 1;
-      if (count[k] < 0 || first[k] < 0 || first[k] + count[k] > nps->n_pods)
-        return set_err(h, KSIM_E_INVALID, "nominated pod range out of the pod set");
-      for (int32_t j = first[k]; j < first[k] + count[k]; j++)
-        if ((rc = validate_pod(h, nps, j))) return rc;
-    }
+  std::vector<uint8_t> seen((size_t)std::max(h->dc.n, 1), 0);
+  for (int32_t k = 0; k < ng.n; k++) {
+    if (ng.nodes[k] < 0 || ng.nodes[k] >= h->dc.n || seen[ng.nodes[k]])
+      return set_err(h, KSIM_E_INVALID, "nominated node out of range or repeated");
+    seen[ng.nodes[k]] = 1;
+    if (ng.count[k] < 0 || ng.first[k] < 0 || ng.first[k] + ng.count[k] > ng.ps->n_pods)
+      return set_err(h, KSIM_E_INVALID, "nominated pod range out of the pod set");
+    for (int32_t j = ng.first[k]; j < ng.first[k] + ng.count[k]; j++)
+      if ((rc = validate_pod(h, ng.ps, j))) return rc;
   }
   if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pods first");
   if (is_sharded(h)) return set_err(h, KSIM_E_UNSUPPORTED, "preemption runs on unsharded handles");
@@ -231,63 +231,69 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption dry runs re-run Fit only, not NetworkBandwidth");
   if (ps->pods[pod_index].flags & KSIM_POD_NODE_NAMES)
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods a PreFilterResult restricts");
-  if ((rc = validate_pod(h, ps, pod_index))) return rc;
-  int32_t fit = -1, port = -1, ipa = -1, pts = -1;
+  return validate_pod(h, ps, pod_index);
+}
+
+// Which uses does the dry run read?  It re-runs NodeResourcesFit, NodePorts,
+// InterPodAffinity, PodTopologySpread and the node volume limit plugins where
+// the profile filters on them.  A use that no Filter reads (ScheduleAnyway
+// spread, InterPodAffinity scores, ImageLocality) or whose filter the profile
+// lacks is in none of the plan's masks.
+static int preempt_plan(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                        PreemptEntry entry, PreemptPlan& q) {
+  q = PreemptPlan{};
+  q.fit = q.port = q.ipa = q.pts = -1;
+  q.prio = priority, q.smin = h->pre_smin;
   for (int f = 0; f < h->prof.n_filter; f++) {
-    if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) fit = f;
-    if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) port = f;
-    if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) ipa = f;
-    if (h->prof.filter[f] == KSIM_PL_POD_TOPOLOGY_SPREAD) pts = f;
+    if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) q.fit = f;
+    if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) q.port = f;
+    if (h->prof.filter[f] == KSIM_PL_INTER_POD_AFFINITY) q.ipa = f;
+    if (h->prof.filter[f] == KSIM_PL_POD_TOPOLOGY_SPREAD) q.pts = f;
   }
-  // The dry run re-runs NodeResourcesFit, NodePorts and InterPodAffinity and,
-  // through ksim_preempt_spread, PodTopologySpread.  Uses that no Filter reads
-  // (ScheduleAnyway spread, InterPodAffinity scores, ImageLocality) are
-  // ignored; the two older entry points refuse DoNotSchedule spread (their
-  // callers fall back on that code).
   const ksim_pod& pp = ps->pods[pod_index];
-  const bool topo = pp.use_count > 0;
-  uint32_t port_mask = 0, aff_mask = 0, anti_mask = 0, exist_mask = 0, hard_mask = 0;
+  const ksim_topo_use* uses = ps->uses + pp.use_first;
+  const bool full = entry == PreemptEntry::full, vol_form = has_volume_use(ps, pod_index);
   for (int32_t k = 0; k < pp.use_count && vol_form && !full; k++) {
-    const uint8_t kind = ps->uses[pp.use_first + k].kind;
     static const char* const kNames[] = {"KSIM_USE_PTS_HARD", nullptr, "KSIM_USE_IPA_EXISTING_ANTI",
                                          "KSIM_USE_IPA_AFFINITY", "KSIM_USE_IPA_ANTI"};
-    if (kind <= KSIM_USE_IPA_ANTI && kNames[kind])
+    if (uses[k].kind <= KSIM_USE_IPA_ANTI && kNames[uses[k].kind])
       return set_err(h, KSIM_E_UNSUPPORTED, std::string("preemption for pods with a KSIM_USE_VOLUME use and a ") +
-                                                kNames[kind] + " use (the volume form moves no domain counts)");
+                                                kNames[uses[k].kind] + " use (the volume form moves no domain counts)");
   }
-  for (int32_t k = 0; k < pp.use_count && !spread && !full; k++)
-    if (ps->uses[pp.use_first + k].kind == KSIM_USE_PTS_HARD)
+  for (int32_t k = 0; k < pp.use_count && entry != PreemptEntry::spread && !full; k++)
+    if (uses[k].kind == KSIM_USE_PTS_HARD)   // (the older entry points' callers fall back on that code)
       return set_err(h, KSIM_E_UNSUPPORTED, "preemption for pods with a KSIM_USE_PTS_HARD use (its dry run needs the "
                                             "victims' domains: ksim_preempt_spread)");
   for (int32_t k = 0; k < pp.use_count; k++) {
-    const uint8_t kind = ps->uses[pp.use_first + k].kind;
-    if (kind == KSIM_USE_NODE_PORT && port >= 0) port_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_AFFINITY && ipa >= 0) aff_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_ANTI && ipa >= 0) anti_mask |= 1u << k;
-    if (kind == KSIM_USE_IPA_EXISTING_ANTI && ipa >= 0) exist_mask |= 1u << k;
-    if (kind == KSIM_USE_PTS_HARD && pts >= 0) hard_mask |= 1u << k;
+    const uint8_t kind = uses[k].kind;
+    if (kind == KSIM_USE_NODE_PORT && q.port >= 0) q.ports |= 1u << k;
+    if (kind == KSIM_USE_IPA_AFFINITY && q.ipa >= 0) q.aff |= 1u << k;
+    if (kind == KSIM_USE_IPA_ANTI && q.ipa >= 0) q.anti |= 1u << k;
+    if (kind == KSIM_USE_IPA_EXISTING_ANTI && q.ipa >= 0) q.exist |= 1u << k;
+    if (kind == KSIM_USE_PTS_HARD && q.pts >= 0) q.hard |= 1u << k;
   }
-  // the domain form of k_preempt_nodes (the spread form is one: it reads the same row)
-  const bool dom_form = (aff_mask | anti_mask | exist_mask | hard_mask) != 0;
-  if (hard_mask && !h->pre.aoff)
+  const bool dom = q.reads_domains();
+  if (q.hard && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "ksim_preempt_spread for a pod with DoNotSchedule spread: "
                                       "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
-  if (port_mask && !dom_form && !h->pre.aoff)
+  if (q.ports && !dom && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
                                       "(after ksim_set_bound_pods)");
   if (vol_form && !h->pre_voff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with a KSIM_USE_VOLUME use: ksim_set_bound_pod_volumes "
                                       "first (after ksim_set_bound_pods)");
   // what the profile's limit plugins read of the pod (validate_pod checked the families)
-  PreemptVol vm{};
+  PreemptVol& vm = q.vol;
   vm.at = 0xffffffffu;
   if (vol_form) {
+    vm.voff = h->pre_voff;
+    vm.vols = h->pre_vols;
     for (int f = 0; f < h->prof.n_filter; f++) {
       const int32_t k = h->prof.filter[f] - KSIM_PL_EBS_LIMITS;
       if (k >= 0 && k < 4) vm.at = (vm.at & ~(255u << (8 * k))) | ((uint32_t)f << (8 * k));
     }
     for (int32_t k = 0; k < pp.use_count; k++) {
-      const ksim_topo_use& u = ps->uses[pp.use_first + k];
+      const ksim_topo_use& u = uses[k];
       if (u.kind != KSIM_USE_VOLUME) continue;
       const uint32_t pl = (h->dc.vol_plug >> (4 * u.col)) & 15u;
       if (((vm.at >> (8 * pl)) & 255u) == 255u) continue;   // its plugin is not in the filter list
@@ -296,35 +302,46 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       if (pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS)) vm.csi |= 1u << u.col;
     }
   }
-  if (dom_form && !h->pre.aoff)
+  if (dom && !h->pre.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
                                       "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
-  HIPCHK(h, hipSetDevice(h->device));
-  DevPods P;
-  if ((rc = upload_single(h, ps, pod_index, P))) return rc;
-  if ((rc = set_run(h, 0, 1))) return rc;
-  const LaunchArgs a = make_args(h, P, nullptr);
-  DevPreempt pre = h->pre;
-  // The status pass: the per-pod cycle's filter phase.  For a pod with uses its
-  // PreFilter pass runs first; the domain tables and topology flags it fills
-  // are zero between cycles (k_select / k_bind re-zero them in a whole cycle).
-  // keep: the domain form of k_preempt_nodes reads the last pass's tables, so
-  // the caller re-zeroes them after that kernel.
-  auto rezero = [&]() -> int {
-    if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
-    HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
-    return KSIM_OK;
-  };
-  auto filter_pass = [&](bool keep = false) -> int {
-    launch_filter_only(a, h->stream, topo);
-    HIPCHK(h, hipGetLastError());
-    return topo && !keep ? rezero() : KSIM_OK;
-  };
+  // the static volume filters of a preemptor with groups
+  q.vb = full && pp.vb_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_BINDING);
+  q.vz = full && pp.vz_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_ZONE);
+  return KSIM_OK;
+}
+
+// The status pass: the per-pod cycle's filter phase.  For a pod with uses
+// (topo) its PreFilter pass runs first; the domain tables and topology flags it
+// fills are zero between cycles (k_select / k_bind re-zero them in a whole
+// cycle).  keep: a form with a row side reads the last pass's tables, so the
+// caller re-zeroes them after the node kernel.
+static int preempt_rezero(ksim_handle* h) {
+  if (h->sc.dom) HIPCHK(h, hipMemsetAsync(h->sc.dom, 0, 8 * (size_t)KSIM_MAX_USES * h->dc.vmax, h->stream));
+  HIPCHK(h, hipMemsetAsync(&h->st->topo_flags, 0, sizeof(uint32_t), h->stream));
+  return KSIM_OK;
+}
+static int preempt_filter_pass(ksim_handle* h, const LaunchArgs& a, bool topo, bool keep) {
+  launch_filter_only(a, h->stream, topo);
+  HIPCHK(h, hipGetLastError());
+  return topo && !keep ? preempt_rezero(h) : KSIM_OK;
+}
+
+// The statuses the dry run starts from (s.fail): pass 1 of each grouped node,
+// its nominated pods assumed on it, then every node as is.  The groups'
+// requests, class contributions and volume holdings are uploaded for the sides
+// that move them, and pre.nslot names each grouped node's group until the caller clears it.
+static int preempt_statuses(ksim_handle* h, const LaunchArgs& a, const NominatedGroups& ng, bool topo,
+                            PreemptPlan& plan, DevPreempt& pre) {
+  int rc;
+  const ksim_pod_set* nps = ng.ps;
+  const int32_t n_groups = ng.n, *gnodes = ng.nodes, *first = ng.first, *count = ng.count;
+  const bool dom_form = plan.reads_domains(), adds_form = plan.ports || dom_form, vol_form = plan.vol.voff != nullptr;
   std::vector<uint8_t> gfail((size_t)std::max(n_groups, 1), KSIM_PASSED);
   std::vector<int64_t> nreq((size_t)std::max(n_groups, 1) * (KSIM_PREEMPT_REQ + 1), 0);
   std::vector<int32_t> goff((size_t)n_groups + 1, 0);    // the groups' class contributions (CSR)
   std::vector<ksim_class_add> gadds;
-  std::vector<int32_t> gvoff((size_t)n_groups + 1, 0);   // and their volume holdings, for the volume form
+  std::vector<int32_t> gvoff((size_t)n_groups + 1, 0);   // and their volume holdings, for the volume side
   std::vector<VolHold> gvols;
   auto bind_group = [&](int32_t k, int sign) -> int {
     for (int32_t j = first[k]; j < first[k] + count[k]; j++) {
@@ -338,7 +355,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   };
   for (int32_t k = 0; k < n_groups; k++) {                // pass 1 of each grouped node
     if ((rc = bind_group(k, 1))) return rc;
-    if ((rc = filter_pass())) return rc;
+    if ((rc = preempt_filter_pass(h, a, topo, false))) return rc;
     HIPCHK(h, hcopy(h, &gfail[k], h->sc.fail + gnodes[k], 1, hipMemcpyDeviceToHost));
     if ((rc = bind_group(k, -1))) return rc;
     int64_t* q = nreq.data() + (size_t)k * (KSIM_PREEMPT_REQ + 1);
@@ -348,7 +365,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
       q[1] += x.req_mem;
       q[2] += x.req_eph;
       for (int c = 0; c < KSIM_MAX_SCALAR; c++) q[3 + c] += x.scalar_req[c];
-      if ((port_mask || dom_form) && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
+      if (adds_form && x.add_count > 0) gadds.insert(gadds.end(), nps->adds + x.add_first, nps->adds + x.add_first + x.add_count);
       for (int32_t e = 0; e < x.use_count && vol_form; e++) {
         const ksim_topo_use& u = nps->uses[x.use_first + e];
         if (u.kind == KSIM_USE_VOLUME) gvols.push_back({u.cls, (int32_t)u.col, u.arg});
@@ -361,52 +378,33 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   if (n_groups > 0) {
     free_bufs(h->pre_nom_bufs);
     if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.nreq, 8 * nreq.size(), nreq.data()))) return rc;
-    if (port_mask || dom_form) {                           // the groups' holdings stay on their nodes too
+    if (adds_form) {                                       // the groups' holdings stay on their nodes too
       if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.goff, 4 * goff.size(), goff.data())) ||
           (rc = dev_alloc(h, h->pre_nom_bufs, pre.gadds, sizeof(ksim_class_add) * gadds.size(), gadds.data())))
         return rc;
     }
     if (vol_form) {
-      if ((rc = dev_alloc(h, h->pre_nom_bufs, vm.gvoff, 4 * gvoff.size(), gvoff.data())) ||
-          (rc = dev_alloc(h, h->pre_nom_bufs, vm.gvols, sizeof(VolHold) * gvols.size(), gvols.data())))
+      if ((rc = dev_alloc(h, h->pre_nom_bufs, plan.vol.gvoff, 4 * gvoff.size(), gvoff.data())) ||
+          (rc = dev_alloc(h, h->pre_nom_bufs, plan.vol.gvols, sizeof(VolHold) * gvols.size(), gvols.data())))
         return rc;
     }
   }
-  if ((rc = filter_pass(dom_form))) return rc;             // every node as is
-  if (n_groups > 0) {
-    for (int32_t k = 0; k < n_groups; k++) {
-      // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
-      if (gfail[k] != KSIM_PASSED) {
-        gfail[k] &= (uint8_t)~kFailError;
-        HIPCHK(h, hipMemcpyAsync(h->sc.fail + gnodes[k], &gfail[k], 1, hipMemcpyHostToDevice, h->stream));
-      }
-      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &k, 4, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));        // k and gfail[k] are host stack / vector slots
+  if ((rc = preempt_filter_pass(h, a, topo, dom_form))) return rc;   // every node as is
+  for (int32_t k = 0; k < n_groups; k++) {
+    // a grouped node's status: pass 1's unless it passed (then pass 2's, as is)
+    if (gfail[k] != KSIM_PASSED) {
+      gfail[k] &= (uint8_t)~kFailError;
+      HIPCHK(h, hipMemcpyAsync(h->sc.fail + gnodes[k], &gfail[k], 1, hipMemcpyHostToDevice, h->stream));
     }
+    HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &k, 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // k and gfail[k] are host stack / vector slots
   }
-  // ksim_preempt_full: the static volume filters of a preemptor with groups
-  const bool vb = full && pp.vb_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_BINDING);
-  const bool vz = full && pp.vz_count > 0 && prof_has_filter(h->prof, KSIM_PL_VOLUME_ZONE);
-  vm.voff = h->pre_voff;
-  vm.vols = h->pre_vols;
-  if (vol_form && dom_form && vm.uses) {                   // only ksim_preempt_full gets here: the full form
-    launch_preempt_full(a, pre, fit, priority, h->stream, port, port_mask, ipa, aff_mask, anti_mask, exist_mask, pts,
-                        hard_mask, h->pre_smin, vm, vb, vz);
-  } else {
-    if (vol_form && !dom_form)
-      launch_preempt_volumes(a, pre, fit, priority, h->stream, port, port_mask, vm);
-    else
-      launch_preempt(a, pre, fit, priority, h->stream, false, port, port_mask, ipa, aff_mask, anti_mask, exist_mask,
-                     pts, hard_mask, h->pre_smin);
-    if (vb || vz) launch_preempt_veto(a, pre, h->stream, vb, vz);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (dom_form && (rc = rezero())) return rc;              // the tables k_preempt_nodes read
-  if (n_groups > 0) {
-    static const int32_t kNoGroup = -1;
-    for (int32_t k = 0; k < n_groups; k++)
-      HIPCHK(h, hipMemcpyAsync(pre.nslot + gnodes[k], &kNoGroup, 4, hipMemcpyHostToDevice, h->stream));
-  }
+  return KSIM_OK;
+}
+
+// The pick, and the nominated node's victims in the dry run's list order: the
+// victims violating a PDB, then the others, each in CSR order.
+static int preempt_read_back(ksim_handle* h, ksim_preempt_out* out) {
   int32_t pick[5];
   HIPCHK(h, hipMemcpyAsync(pick, h->pre.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -421,7 +419,6 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
     std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
     if (off[1] > off[0])
       HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
-    // the dry run's list order: the victims violating a PDB, then the others, each in CSR order
     int32_t k = 0;
     for (const uint8_t want : {(uint8_t)(1 | kPreemptViolating), (uint8_t)1})
       for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
@@ -430,28 +427,53 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   return KSIM_OK;
 }
 
+// The dry run behind the four entry points.
+static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
+                       const NominatedGroups& ng, ksim_preempt_out* out, PreemptEntry entry) {
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  PreemptPlan plan;
+  if ((rc = preempt_check_args(h, ps, pod_index, ng, out, entry)) ||
+      (rc = preempt_plan(h, ps, pod_index, priority, entry, plan)))
+    return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  DevPods P;
+  if ((rc = upload_single(h, ps, pod_index, P))) return rc;
+  if ((rc = set_run(h, 0, 1))) return rc;
+  const LaunchArgs a = make_args(h, P, nullptr);
+  DevPreempt pre = h->pre;
+  if ((rc = preempt_statuses(h, a, ng, ps->pods[pod_index].use_count > 0, plan, pre))) return rc;
+  launch_preempt(a, pre, plan, h->stream);
+  HIPCHK(h, hipGetLastError());
+  if (plan.reads_domains() && (rc = preempt_rezero(h))) return rc;   // the tables the node kernel read
+  static const int32_t kNoGroup = -1;
+  for (int32_t k = 0; k < ng.n; k++)
+    HIPCHK(h, hipMemcpyAsync(pre.nslot + ng.nodes[k], &kNoGroup, 4, hipMemcpyHostToDevice, h->stream));
+  return preempt_read_back(h, out);
+}
+
 extern "C" int ksim_preempt_nominated(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                                       const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                       const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false);
+  return preempt_run(h, ps, pod_index, priority, {nps, n_groups, gnodes, first, count}, out, PreemptEntry::plain);
 }
 
 extern "C" int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                                     const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                     const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, false, true);
+  return preempt_run(h, ps, pod_index, priority, {nps, n_groups, gnodes, first, count}, out, PreemptEntry::volumes);
 }
 
 extern "C" int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                                  const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                  const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true, true, true);
+  return preempt_run(h, ps, pod_index, priority, {nps, n_groups, gnodes, first, count}, out, PreemptEntry::full);
 }
 
 extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
                                    const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                    const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
-  return preempt_run(h, ps, pod_index, priority, nps, n_groups, gnodes, first, count, out, true);
+  return preempt_run(h, ps, pod_index, priority, {nps, n_groups, gnodes, first, count}, out, PreemptEntry::spread);
 }
 
 // ---- selector / affinity-term matching (ksim_match.hip) ------

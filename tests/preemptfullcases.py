@@ -1,5 +1,5 @@
 """Hand-made clusters for the full DefaultPreemption dry run (ksim_preempt_full;
-csrc/ksim_preempt.hip, k_preempt_nodes_full and k_preempt_static_veto), as model
+csrc/ksim_preempt.hip, k_preempt_nodes<FullForm> and k_preempt_static_veto), as model
 objects: tests/test_preempt_full_ref.py checks on the CPU that they tell the
 reference (tests/preemptfullref.py) from its wrong readings, and
 tests/test_gpu_preempt_full.py runs the engine on them.
@@ -396,6 +396,28 @@ _ALL = (statefulset_replica, one_node_anti, one_node_without_ipa, shared_volume_
         pv_zone_without_volume_zone, group_holds_and_counts, group_holds_and_repels, every_slot,
         every_slot_without_ports, eight_families, block_edge, three_hundred_zoned)
 WIDE = ("block_edge_257", "three_hundred_zoned")        # too wide to run every wrong reading on
+
+
+# ---- a budget between the rows (not in scenes(): it carries PodDisruptionBudgets) ----------------
+def mixed_budget() -> FullScene:
+    """tests/preemptvolcases.py mixed_budget for a preemptor that also carries
+    hostname anti-affinity against app=q, which no pod matches: the full form
+    on the same volumes.  n0, EBS limit 3: b1 (40) and b3 (20) mount a, b2 (30)
+    and b4 (10) mount b; the preemptor brings two new volumes.  One budget,
+    disruptionsAllowed 1, over b1, b2, b3: b2 and b3 violate.  b2 back, {b}: it
+    stays; b3 back, {a, b}: 4 > 3, a violating victim; b1: a attaches again, a
+    victim; b4: b is attached (b2), it stays after b3 stayed out.  Without
+    budgets: b2 and b4."""
+    from ksim.model import PodDisruptionBudget
+    s = FullScene("mixed_budget")
+    s.znode("n0", "za", {EBS_KEY: "3"})
+    for name, prio, vol in (("b1", 40, "a"), ("b2", 30, "b"), ("b3", 20, "a"), ("b4", 10, "b")):
+        s.bpod(name, "n0", prio, [("ebs", vol)], labels={"tier": "db"} if name != "b4" else None)
+    s.preemptor([("ebs", "x"), ("ebs", "y")], terms=[anti(app="q")])
+    s.budgets = [PodDisruptionBudget("db", selector=LabelSelector({"tier": "db"}), disruptions_allowed=1)]
+    s.expect_result = ("n0", ["b2", "b4"], 1, 1)
+    s.expect_budgets = ("n0", ["b3", "b1"], 1, 1, 1)
+    return s
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,6 +22,11 @@ Potential nodes: the first failing filter is NodeResourcesFit, NodePorts, a
 limit plugin, InterPodAffinity with one of its two anti-affinity messages, or
 PodTopologySpread with the skew message.
 
+With ``pdbs`` (budgets) the lower-priority pods are split and reprieved as
+tests/preemptvolref.py ``reprieve_all`` has it (filterPodsWithPDBViolation, the
+violating pods first) and the result carries the nominated node's violations
+as a fifth element.
+
 ``flaw`` switches on one wrong reading (FLAWS) for the test that the scenes of
 tests/preemptfullcases.py tell each from the reference.  EQUAL lists readings
 that cannot differ: ``static_skipped_in_reprieve`` skips VolumeBinding and
@@ -31,12 +36,13 @@ out and is no candidate either way."""
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, List, Optional, Set, Tuple
+from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import preemptobjref
 from ksim import profile
 from ksim.model import Container, Node, Pod
 from oracle.objref import IPA_ANTI, IPA_EXIST, PTS_SKEW, NodeInfo, ObjScheduler
+from preemptvolref import reprieve_all
 from vollimitref import PLUGINS, VolLimitRef, owner
 
 FLAWS = ("volumes_stale",                  # volume counts do not move in a trial that moves domain counts
@@ -174,11 +180,12 @@ class _Run(preemptobjref._Run):
 
 def dry_run(nodes: List[Node], pvs, pvcs, bound: List[Pod], start: Dict[str, int], order: Dict[str, int], pod: Pod,
             priority: int, args=(10, 100), nominated: Optional[Dict[str, List[Pod]]] = None,
-            flaw: Optional[str] = None, filter_order=None, classes=()) -> Tuple[Optional[str], List[str], int, int]:
+            flaw: Optional[str] = None, filter_order=None, classes=(), pdbs: Optional[Sequence] = None) -> tuple:
     """(nominated node name or None, victim names in reprieve order, potential
     nodes, candidates kept), as preemptobjref.dry_run.  ``nominated``: {node
     name: pods nominated there}; ``flaw``: None for the reference, one of FLAWS
-    or one of EQUAL."""
+    or one of EQUAL.  ``pdbs``: the PodDisruptionBudgets (None: no budget table,
+    the 4-tuple); the 5-tuple of preemptpdbref.dry_run then, cut and pick as there."""
     assert flaw is None or flaw in FLAWS or flaw in EQUAL
     run = _Run(nodes, pvs, pvcs, classes, bound, pod, nominated, flaw, filter_order)
     s = run.s
@@ -211,37 +218,36 @@ def dry_run(nodes: List[Node], pvs, pvcs, bound: List[Pod], start: Dict[str, int
             if not run.passes(ni, on):
                 return None
             run.reprieving = True
-            victims = []
-            for q in lower:                                # reprievePod
-                if run.passes(ni, on + [q]):
-                    on.append(q)
-                else:
-                    victims.append(q)
-            return victims
+            return reprieve_all(lower, on, lambda pods: run.passes(ni, pods), run.real, pdbs)
         finally:
             run.dry = run.reprieving = run.no_static = False
 
-    cands, found = [], 0
-    for ni in potential:
-        if found >= want:
+    cands, found, clean = [], 0, 0
+    for ni in potential if want > 0 else []:
+        if found >= want and clean >= 1:                   # without budgets every candidate is clean
             break
-        v = select_victims(ni)
-        if v is not None:
-            cands.append((ni, v))
+        got = select_victims(ni)
+        if got is not None:
+            cands.append((ni,) + got)
             found += 1
+            clean += got[1] == 0
         elif flaw == "vetoed_count_toward_cut" and select_victims(ni, no_static=True) is not None:
             found += 1
+            clean += 1
+    tail = () if pdbs is None else (0,)
     if not cands:
-        return None, [], len(potential), 0
+        return (None, [], len(potential), 0) + tail
 
-    def criteria(c):                                       # pickOneNodeForPreemption (no PDBs)
-        v = c[1]
+    def criteria(c):                                       # pickOneNodeForPreemption
+        _, v, nviol = c
+        top = max((q.priority for q in v), default=-(2 ** 31))     # v[0]'s without budgets: the list is sorted
         high = v[0].priority if v else -(2 ** 31)
         total = sum(q.priority + 2 ** 31 for q in v)
-        early = min((start[q.name] for q in v if q.priority == high), default=2 ** 63)
-        return (high, total, len(v), -early)
+        early = min((start[q.name] for q in v if q.priority == top), default=2 ** 63)
+        return (nviol, high, total, len(v), -early)
     best = min(range(len(cands)), key=lambda i: (criteria(cands[i]), i))
-    return cands[best][0].node.name, [q.name for q in cands[best][1]], len(potential), len(cands)
+    ni, v, nviol = cands[best]
+    return (ni.node.name, [q.name for q in v], len(potential), len(cands)) + (() if pdbs is None else (nviol,))
 
 
 as_indices = preemptobjref.as_indices

@@ -10,7 +10,7 @@ potential node is tried (args (100, 0)).  ``expect`` is the hand-derived result
 with the scene's nominated group, ``expect_plain`` the one without;
 ``tells``: the faulty readings (preemptvolref.FLAWS) the scene is there to tell
 from the reference.  Sizes: 1 to 8 nodes, plus 257 (one node past the first
-256-thread block of k_preempt_nodes_vol) and 300."""
+256-thread block of k_preempt_nodes<VolumeForm>) and 300."""
 from __future__ import annotations
 
 import functools
@@ -38,6 +38,8 @@ class VolScene(Scene):
     expect_result: Optional[tuple] = None
     expect_plain: Optional[tuple] = None
     tells: Tuple[str, ...] = ()
+    budgets: List = field(default_factory=list)              # PodDisruptionBudgets (mixed_budget only)
+    expect_budgets: Optional[tuple] = None                   # the hand-derived 5-tuple under them
 
     def bpod(self, name: str, on: str, prio: int, vols=(), cpu: str = "100m", start: int = 100, port: int = 0) -> Pod:
         p = self.pod(name, vols, on=on, cpu=cpu)
@@ -319,6 +321,30 @@ _ALL = (ebs_slot, two_victims_share, shared_with_higher, preemptor_mounts_victim
         csi_over_limit_nothing_new, csi_node_without_key, two_families_and_a_third, fit_first_limit_decides,
         functools.partial(fit_first_limit_decides, True), profile_without_ebs, group_holds_volumes,
         group_shares_with_victim, port_and_volume, block_edge, three_hundred_shared)
+
+
+# ---- a budget between the rows (not in scenes(): it carries PodDisruptionBudgets) ----------------
+def mixed_budget() -> VolScene:
+    """n0: EBS limit 3, four lower-priority pods holding two shared volumes
+    two-and-two: b1 (40) and b3 (20) mount a, b2 (30) and b4 (10) mount b.  The
+    preemptor brings two new volumes: 2 + 2 > 3 (potential); all out: 0 + 2.
+    ``budgets``: one budget, disruptionsAllowed 1, over b1, b2, b3 (tier=db):
+    b1 takes the one disruption, b2 and b3 violate.  The violating pods first:
+    b2 back, {b}: 1 + 2 stays; b3 back, {a, b}: 4 > 3, a victim that violates.
+    Then b1: a left with b3, so it attaches again, 4 > 3, a victim; b4: b is
+    attached (b2 was reprieved), 1 + 2, it stays after b3 stayed out.
+    Without budgets (``expect_result``): b1 stays, b2 out, b3 stays (a is
+    attached), b4 out."""
+    from ksim.model import LabelSelector, PodDisruptionBudget
+    s = VolScene("mixed_budget")
+    s.node("n0", {EBS_KEY: "3"})
+    for name, prio, vol in (("b1", 40, "a"), ("b2", 30, "b"), ("b3", 20, "a"), ("b4", 10, "b")):
+        s.bpod(name, "n0", prio, [("ebs", vol)]).labels = {"tier": "db"} if name != "b4" else {}
+    s.preemptor([("ebs", "x"), ("ebs", "y")])
+    s.budgets = [PodDisruptionBudget("db", selector=LabelSelector({"tier": "db"}), disruptions_allowed=1)]
+    s.expect_result = ("n0", ["b2", "b4"], 1, 1)
+    s.expect_budgets = ("n0", ["b3", "b1"], 1, 1, 1)
+    return s
 
 
 @functools.lru_cache(maxsize=None)

@@ -17,6 +17,12 @@ Potential nodes: the first failing filter is NodeResourcesFit, NodePorts or one
 of the four limit plugins (all return plain Unschedulable; upstream counts such
 a node among nodesWherePreemptionMightHelp).
 
+With ``pdbs`` (budgets) the lower-priority pods are split as
+filterPodsWithPDBViolation does and the violating ones are reprieved first, the
+way tests/preemptpdbref.py has it (its ``matching`` decides which budgets a pod
+decrements); the result then carries the nominated node's violations as a
+fifth element.
+
 ``flaw`` switches on one wrong reading an implementation of the incremental
 rule could have (FLAWS), for the test that the scenes of
 tests/preemptvolcases.py tell each from the reference.  ``sums_32bit`` needs
@@ -25,11 +31,12 @@ array scene, through its numpy restatement of the device rule."""
 from __future__ import annotations
 
 import dataclasses
-from typing import Dict, List, Optional, Set, Tuple
+from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 from ksim import profile
 from ksim.model import Node, Pod
 from preemptobjref import _Run, as_indices  # noqa: F401  (as_indices: re-exported)
+from preemptpdbref import matching
 from vollimitref import PLUGINS, VolLimitRef, owner
 
 FLAWS = ("removed_stay_attached",      # a removed pod's volumes stay attached
@@ -129,10 +136,12 @@ class _VolRun(_Run):
 
 def dry_run(nodes: List[Node], pvs, pvcs, bound: List[Pod], start: Dict[str, int], order: Dict[str, int], pod: Pod,
             priority: int, args=(10, 100), nominated: Optional[Dict[str, List[Pod]]] = None,
-            flaw: Optional[str] = None, filter_order=None) -> Tuple[Optional[str], List[str], int, int]:
+            flaw: Optional[str] = None, filter_order=None, pdbs: Optional[Sequence] = None) -> tuple:
     """(nominated node name or None, victim names in reprieve order, potential
     nodes, candidates kept), as preemptobjref.dry_run.  ``nominated``: {node
-    name: pods nominated there}; ``flaw``: None for the reference or one of FLAWS."""
+    name: pods nominated there}; ``flaw``: None for the reference or one of FLAWS.
+    ``pdbs``: the PodDisruptionBudgets (None: no budget table, the 4-tuple);
+    the 5-tuple of preemptpdbref.dry_run then, cut and pick as there."""
     assert flaw is None or flaw in FLAWS
     run = _VolRun(nodes, pvs, pvcs, bound, pod, nominated, flaw, filter_order)
     s = run.s
@@ -155,29 +164,52 @@ def dry_run(nodes: List[Node], pvs, pvcs, bound: List[Pod], start: Dict[str, int
         if not run.passes_recomputed(ni, on):
             return None
         run.reprieving = True
-        victims = []
-        for q in lower:                                    # reprievePod
-            if run.passes_recomputed(ni, on + [q]):
+        return reprieve_all(lower, on, lambda pods: run.passes_recomputed(ni, pods), run.real, pdbs)
+
+    cands, clean = [], 0
+    for ni in potential if want > 0 else []:
+        if len(cands) >= want and clean >= 1:              # without budgets every candidate is clean
+            break
+        got = select_victims(ni)
+        if got is not None:
+            cands.append((ni,) + got)
+            clean += got[1] == 0
+    tail = () if pdbs is None else (0,)
+    if not cands:
+        return (None, [], len(potential), 0) + tail
+
+    def criteria(c):                                       # pickOneNodeForPreemption
+        _, v, nviol = c
+        top = max((q.priority for q in v), default=-(2 ** 31))     # v[0]'s without budgets: the list is sorted
+        high = v[0].priority if v else -(2 ** 31)
+        total = sum(q.priority + 2 ** 31 for q in v)
+        early = min((start[q.name] for q in v if q.priority == top), default=2 ** 63)
+        return (nviol, high, total, len(v), -early)
+    best = min(range(len(cands)), key=lambda i: (criteria(cands[i]), i))
+    ni, v, nviol = cands[best]
+    return (ni.node.name, [q.name for q in v], len(potential), len(cands)) + (() if pdbs is None else (nviol,))
+
+
+def reprieve_all(lower: List[Pod], on: List[Pod], passes, real: Dict[str, Pod], pdbs) -> Tuple[List[Pod], int]:
+    """The reprieve loops over ``lower`` (MoreImportantPod order) onto ``on``:
+    (victims in list order, how many of them violate a budget).
+    filterPodsWithPDBViolation walks ``lower`` with a fresh copy of every
+    budget; the violating pods are tried first, then the others."""
+    allowed = [b.disruptions_allowed for b in pdbs or ()]
+    violating = []
+    for q in lower:
+        hit = False
+        for i in matching(real[q.name], pdbs or ()):
+            allowed[i] -= 1
+            hit = hit or allowed[i] < 0
+        if hit:
+            violating.append(q)
+    victims, num_violating = [], 0
+    for group in (violating, [q for q in lower if q not in violating]):
+        for q in group:                                    # reprievePod
+            if passes(on + [q]):
                 on.append(q)
             else:
                 victims.append(q)
-        return victims
-
-    cands = []
-    for ni in potential:
-        if len(cands) >= want:
-            break
-        v = select_victims(ni)
-        if v is not None:
-            cands.append((ni, v))
-    if not cands:
-        return None, [], len(potential), 0
-
-    def criteria(c):                                       # pickOneNodeForPreemption (no PDBs)
-        v = c[1]
-        high = v[0].priority if v else -(2 ** 31)
-        total = sum(q.priority + 2 ** 31 for q in v)
-        early = min((start[q.name] for q in v if q.priority == high), default=2 ** 63)
-        return (high, total, len(v), -early)
-    best = min(range(len(cands)), key=lambda i: (criteria(cands[i]), i))
-    return cands[best][0].node.name, [q.name for q in cands[best][1]], len(potential), len(cands)
+                num_violating += group is violating
+    return victims, num_violating

@@ -1,6 +1,6 @@
 """ksim_preempt_full: DefaultPreemption's dry run for every preemptor the
-per-pod cycle accepts (csrc/ksim_preempt.hip: k_preempt_nodes_full, the spread
-form and the volume form in one thread, and k_preempt_static_veto, VolumeBinding
+per-pod cycle accepts (csrc/ksim_preempt.hip: k_preempt_nodes<FullForm>, the row
+side and the volume side in one thread, and k_preempt_static_veto, VolumeBinding
 and VolumeZone on the candidates).
 
 No older entry point takes a pod with counted volumes beside required pod
@@ -142,6 +142,37 @@ def test_a_budget_that_allows_nothing_marks_every_victim(engines, name):
         assert _run(eng, b, with_pdb=True) == want + (len(want[1]),)
     finally:
         eng.set_bound_pod_pdbs([], [0], [])
+
+
+def test_a_budget_between_the_rows(engines):
+    """preemptfullcases.mixed_budget, the full form on shared volumes: b2 and b3
+    violate the budget (disruptionsAllowed 1 over b1, b2, b3); b2 is reprieved,
+    b3 stays out violating, then b1 is a victim because b3 is out (the shared
+    volume would attach again) and b4 is reprieved because b2 is back.  Against
+    the reference with its budget table (tests/test_preempt_budget_refs.py),
+    and without budgets on the same handle."""
+    import preemptpdbref
+    sc = cases.mixed_budget()
+    b = cases.build(sc)
+    p = b.enc.pods[0]
+    kinds = {int(k) for k in b.enc.uses["kind"][int(p["use_first"]):int(p["use_first"]) + int(p["use_count"])]}
+    assert {abi.USE_VOLUME, abi.USE_IPA_ANTI} <= kinds
+    names = b.cluster.node_names
+
+    def want(pdbs):
+        got = ref.dry_run(b.nodes, sc.pvs, sc.pvcs, sc.bound, sc.start, sc.order, sc.pods[0], cases.PRIO, sc.args,
+                          None, filter_order=sc.filter_order, classes=sc.classes, pdbs=pdbs)
+        return preemptpdbref.as_indices(got, names, sc.order)
+    assert [sc.order[n] for n in ("b1", "b2", "b3", "b4")] == [0, 1, 2, 3]
+    eng = engines(b)
+    try:
+        eng.set_bound_pod_pdbs([1], [0, 1, 2, 3, 3], [0, 0, 0])      # b1, b2, b3 in budget 0
+        got = _run(eng, b, with_pdb=True)
+        assert got == want(sc.budgets) and got[1] == [2, 0] and got[4] == 1
+    finally:
+        eng.set_bound_pod_pdbs([], [0], [])
+    plain = _run(eng, b, with_pdb=True)
+    assert plain == want([]) and plain[1] == [1, 3]
 
 
 # ---- without the combination the new call is the older one ---------------------------------------------

@@ -1,5 +1,5 @@
 """ksim_preempt_volumes: DefaultPreemption's dry run for preemptors with
-counted volumes (csrc/ksim_preempt.hip, k_preempt_nodes_vol: the volume form).
+counted volumes (csrc/ksim_preempt.hip, k_preempt_nodes<VolumeForm>: the volume form).
 
 The C oracle knows no volume limits and the three older entry points refuse
 these pods, so the reference is the object-level dry run tests/preemptvolref.py
@@ -292,6 +292,36 @@ def test_a_budget_that_allows_nothing_marks_every_victim(engines, name):
         assert _run(eng, b, with_pdb=True) == want + (len(want[1]),)
     finally:
         eng.set_bound_pod_pdbs([], [0], [])
+
+
+def test_a_budget_between_the_rows(engines):
+    """preemptvolcases.mixed_budget: four lower-priority pods on two shared
+    volumes two-and-two, one budget (disruptionsAllowed 1) over three of them.
+    b2 and b3 violate; b2 is reprieved, b3 stays out violating, then b1 is a
+    victim because b3 is out (the shared volume would attach again) and b4 is
+    reprieved because b2 is back: a reprieved row between violating and
+    non-violating rows, which neither derived fact above reaches.  Against the
+    reference with its budget table (tests/test_preempt_budget_refs.py), and
+    without budgets on the same handle."""
+    import preemptpdbref
+    sc = cases.mixed_budget()
+    b = model.build(sc)
+    names = b.cluster.node_names
+
+    def want(pdbs):
+        got = ref.dry_run(b.nodes, sc.pvs, sc.pvcs, sc.bound, sc.start, sc.order, sc.pods[0], cases.PRIO, sc.args,
+                          None, filter_order=sc.filter_order, pdbs=pdbs)
+        return preemptpdbref.as_indices(got, names, sc.order)
+    assert [sc.order[n] for n in ("b1", "b2", "b3", "b4")] == [0, 1, 2, 3]
+    eng = engines(b)
+    try:
+        eng.set_bound_pod_pdbs([1], [0, 1, 2, 3, 3], [0, 0, 0])      # b1, b2, b3 in budget 0
+        got = _run(eng, b, with_pdb=True)
+        assert got == want(sc.budgets) and got[1] == [2, 0] and got[4] == 1
+    finally:
+        eng.set_bound_pod_pdbs([], [0], [])
+    plain = _run(eng, b, with_pdb=True)
+    assert plain == want([]) and plain[1] == [1, 3]
 
 
 # ---- a handle keeps nothing of a volume dry run -----------------------------------------------------------

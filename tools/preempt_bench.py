@@ -6,6 +6,11 @@ priorities and start times filling 9.6 CPUs, a 2-CPU preemptor of priority
 Engine.preempt: the pod's upload, the filter pass, the two preemption kernels
 and the result copies, ending synchronized.
 
+--ports: the same cluster where the first bound pod of every node holds host
+port 8080, and a preemptor with that host port: every node is a potential node
+(Fit fails first) and a candidate once the holder is a victim, and each runs
+the ports form of the dry run.  The table carries the rows' port holdings.
+
 --anti: the same cluster spread over 50 zones, one pod of app=x in each zone
 (priority 10, on the zone's first node), and a preemptor with a required zone
 anti-affinity term against app=x: every node is a potential node (Fit fails
@@ -37,14 +42,14 @@ carries every row's class contributions and holdings.
 --pdbs K: K PodDisruptionBudgets with disruptionsAllowed 1 over the table,
 the bound pods of node v in budget v % K (ksim_set_bound_pod_pdbs), so all but
 the most important lower-priority pod of a node violate: the call takes the
-PDB form of the kernels.  With --anti, --spread, --volumes or --full too.
+PDB form of the kernels.  With --ports, --anti, --spread, --volumes or --full too.
 
 Prints one JSON line: the calls' median, min, max and the 10th / 90th
 percentiles in microseconds, per repeat (a fresh handle each) and over all.
 To compare two builds on one machine run it once per library
 (KSIM_LIB_VARIANT=<tag> loads libksim_engine_<tag>.so, tools/build_ref_flavor.sh).
 
-    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--anti | --spread | --volumes | --full] [--pdbs K]
+    python tools/preempt_bench.py [--nodes 5000] [--calls 200] [--warmup 20] [--repeats 3] [--ports | --anti | --spread | --volumes | --full] [--pdbs K]
 """
 import argparse
 import json
@@ -62,7 +67,7 @@ import numpy as np  # noqa: E402
 
 from ksim import abi, engine, profile  # noqa: E402
 from ksim.encode import encode_cluster, encode_pods  # noqa: E402
-from ksim.model import (Container, LabelSelector, Node, PersistentVolume, PersistentVolumeClaim, Pod,  # noqa: E402
+from ksim.model import (Container, ContainerPort, LabelSelector, Node, PersistentVolume, PersistentVolumeClaim, Pod,  # noqa: E402
                         PodAffinityTerm, TopologySpreadConstraint)
 
 ZONE, N_ZONES = "topology.kubernetes.io/zone", 50
@@ -86,6 +91,29 @@ def build(n_nodes: int):
     table = abi.BoundPods(node, prio, start, req)
     enc = encode_pods(cluster, [Pod("preemptor", priority=1000, containers=[Container({"cpu": "2000m"})])])
     assert int(enc.pods[0]["use_count"]) == 0
+    prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
+    return cluster, table, enc, prof
+
+
+def build_ports(n_nodes: int):
+    """build()'s load, host port 8080 on every node's first bound pod and on the preemptor."""
+    from ksim.preemption import bound_table
+    rng = np.random.default_rng(7)
+    nodes = [Node(name=f"n{i:05d}", labels={"kubernetes.io/hostname": f"n{i:05d}"},
+                  allocatable={"cpu": "10", "memory": "64Gi", "pods": "110"}) for i in range(n_nodes)]
+    bound, start = [], {}
+    for v in range(n_nodes):
+        for k in range(4):
+            ports = [ContainerPort(8080)] if k == 0 else []
+            bound.append(Pod(f"b{v}-{k}", node_name=nodes[v].name, priority=int(rng.choice([0, 10, 100, 500])),
+                             containers=[Container({"cpu": "2400m"}, ports)]))
+            start[bound[-1].name] = int(rng.integers(0, 1000))
+    cluster, _ = encode_cluster(nodes, bound)
+    enc = encode_pods(cluster, [Pod("preemptor", priority=1000,
+                                    containers=[Container({"cpu": "2000m"}, [ContainerPort(8080)])])])
+    assert [int(k) for k in enc.uses["kind"][:int(enc.pods[0]["use_count"])]] == [abi.USE_NODE_PORT]
+    table = bound_table(cluster, bound, start, cluster.topo)
+    assert int(table.adds_off[-1]) == n_nodes
     prof = profile.compile_profile(profile.SchedulerProfile(percentage_of_nodes_to_score=0))
     return cluster, table, enc, prof
 
@@ -191,6 +219,7 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--ports", action="store_true", help="a preemptor with a host port one bound pod per node holds")
     ap.add_argument("--anti", action="store_true", help="a preemptor with a required zone anti-affinity term")
     ap.add_argument("--spread", action="store_true", help="a preemptor with a DoNotSchedule zone spread constraint")
     ap.add_argument("--volumes", action="store_true", help="counted volumes on every bound pod and the preemptor")
@@ -198,10 +227,11 @@ def main():
                                                         "constraint on the preemptor (ksim_preempt_full)")
     ap.add_argument("--pdbs", type=int, default=0, help="this many budgets (disruptionsAllowed 1), each bound pod in one")
     args = ap.parse_args()
-    if args.anti + args.spread + args.volumes + args.full > 1:
-        ap.error("--anti, --spread, --volumes or --full, not two of them")
+    if args.ports + args.anti + args.spread + args.volumes + args.full > 1:
+        ap.error("--ports, --anti, --spread, --volumes or --full, not two of them")
     cluster, table, enc, prof = build_anti(args.nodes, args.spread) if args.anti or args.spread else \
-        build_volumes(args.nodes, args.full) if args.volumes or args.full else build(args.nodes)
+        build_volumes(args.nodes, args.full) if args.volumes or args.full else \
+        build_ports(args.nodes) if args.ports else build(args.nodes)
     kw = dict(hard_spread=True) if args.spread else dict(volumes=True) if args.volumes else \
         dict(full=True) if args.full else {}
     budgets = None
@@ -226,7 +256,7 @@ def main():
         eng.close()
         runs.append(summary(us))
         every += us
-    name = ("preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else
+    name = ("preempt_ports" if args.ports else "preempt_zone_anti" if args.anti else "preempt_zone_spread" if args.spread else
             "preempt_volumes" if args.volumes else "preempt_full" if args.full else "preempt_use_free") + ("_pdb" if budgets is not None else "")
     extra = dict(pdbs=args.pdbs, pdb_violations=result[4]) if budgets is not None else {}
     print(json.dumps(dict(bench=name, library=os.path.basename(engine.LIB_PATH), nodes=args.nodes,
