@@ -806,7 +806,9 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * out[33..34] the deferred-commit batches' second stretch (a batch goes on
  * committing pods behind its first pair cut while their guesses still hold;
  * KSIM_ONE_CUT=1 in the environment, read at every run, keeps every batch to
- * its first cut): [33] batches that committed pods there, [34] those pods.
+ * its first cut): [33] batches that committed pods there, [34] those pods;
+ * out[35..36] ksim_preempt_many's rows since ksim_create: [35] rows answered
+ * by the batched launches, [36] rows answered by the single-pod launches.
  * Returns the number of values written (<= n). */
 int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n);
 /* The deferred-commit runs' enqueue rule (host arithmetic, no device): with
@@ -1097,6 +1099,52 @@ int ksim_preempt_volumes(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_i
 int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_index, int32_t priority,
                       const ksim_pod_set* nominated, int32_t n_groups, const int32_t* nodes,
                       const int32_t* first, const int32_t* count, ksim_preempt_out* out);
+
+/* The batched dry run: n preemptors against the current snapshot in a few
+ * launches and one synchronization.  outs[i] receives, field for field (the
+ * victims' order and an n_victims above victims_cap included), what
+ *   ksim_preempt_full(h, pods, pod_index[i], priority[i], NULL, 0, NULL, NULL, NULL, &outs[i])
+ * writes on the same handle state; each outs[i] brings its own victims /
+ * victims_cap, and nothing is written past a row's cap.  The answers come in
+ * the caller's row order; pod_index need not be sorted and may name a pod
+ * more than once.  The snapshot, the class and attached counts, the domain
+ * tables, the topology flags, nextStartNodeIndex and the pod sequence are left
+ * as they were.
+ *   what-if     every row is the dry run WITHOUT nominated groups: a dry run
+ *               changes nothing on the device (evicted victims stay bound), so
+ *               the rows are independent, and a nomination an earlier row
+ *               would make does not feed a later row.  Callers that need the
+ *               PodNominator's chain keep ksim_preempt_nominated / _full.
+ *   routing     a row whose dry run reads no domain table (NodeResourcesFit
+ *               alone, host ports, counted volumes, volume groups; each with
+ *               or without budgets; ScheduleAnyway spread, preferred pod
+ *               affinity and image uses beside them, which no Filter reads) is
+ *               evaluated by the batched launches, up to
+ *               ksim_preempt_many_rows(n_nodes, n_bound) rows per launch group.
+ *               A row with required pod (anti-)affinity or DoNotSchedule spread
+ *               uses the profile filters on is answered inside the same call
+ *               by ksim_preempt_full's launches, one row after another (the
+ *               domain tables are per handle).  ksim_get_diag out[35..36]
+ *               count the two kinds.
+ * Everything is checked before anything runs; on an error no row is written.
+ * KSIM_E_INVALID (the message names the row): n < 0, a null array with n > 0,
+ * an index outside the set, a pod the per-pod calls refuse as invalid, no
+ * bound table, or a row that needs the class adds / the holdings the table
+ * lacks (ksim_preempt_full's rules).  KSIM_E_UNSUPPORTED: shard handles,
+ * NetworkBandwidth in the filter list, a KSIM_POD_NODE_NAMES row.  n == 0 is
+ * KSIM_OK. */
+#define KSIM_PREEMPT_MANY_ROWS 64   /* most preemptors one launch group evaluates */
+int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* pods, int32_t n,
+                      const int32_t* pod_index /* [n] */, const int32_t* priority /* [n] */,
+                      ksim_preempt_out* outs /* [n], each with its own victims / victims_cap */);
+/* Host arithmetic, no device (like ksim_feed_more_batches): the rows one launch
+ * group takes for a cluster of n_nodes nodes and a bound-pod table of n_bound
+ * rows, in [1, KSIM_PREEMPT_MANY_ROWS].  Every row of a group owns a slab of
+ * per-node results (32 bytes per node) and one of victim flags (one byte per
+ * bound pod); the group is sized so that rows x (32 n_nodes + n_bound) stays
+ * under 256 MiB (64 rows up to about 100,000 nodes with a million bound pods),
+ * and never below one row. */
+int32_t ksim_preempt_many_rows(int32_t n_nodes, int32_t n_bound);
 
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's

@@ -234,6 +234,23 @@ func (e *Engine) PreemptNominated(ps *C.ksim_pod_set, idx int, priority int32, n
 	})
 }
 
+// PreemptMany: the batched dry run.  outs[i] receives what the full dry run
+// without nominated groups answers for pod idx[i] at priority[i] on the
+// current snapshot (the what-if reading: no row sees another row's
+// nomination); every out brings its own victims / victims_cap.
+func (e *Engine) PreemptMany(ps *C.ksim_pod_set, idx, priority []int32, outs []C.ksim_preempt_out) error {
+	if len(priority) != len(idx) || len(outs) != len(idx) {
+		return fmt.Errorf("PreemptMany: %d pods, %d priorities, %d outs", len(idx), len(priority), len(outs))
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	return e.locked(func() C.int {
+		return C.ksim_preempt_many(e.h, ps, C.int32_t(len(idx)), (*C.int32_t)(unsafe.Pointer(&idx[0])),
+			(*C.int32_t)(unsafe.Pointer(&priority[0])), &outs[0])
+	})
+}
+
 // FwFilterNominated: RunFilterPluginsWithNominatedPods' first pass of the
 // cycle in flight on the grouped nodes (plugins.go calls it per node).
 func (e *Engine) FwFilterNominated(nominated *C.ksim_pod_set, nodes, first, count []int32, fail []uint8,

@@ -182,11 +182,22 @@ void drop_bound_pods(ksim_handle* h) {
   free_bufs(h->pre_add_bufs);
   free_bufs(h->pre_pdb_bufs);
   free_bufs(h->pre_vol_bufs);
+  drop_many_slabs(h);
   h->pre_voff = nullptr;
   h->pre_vols = nullptr;
   h->pre = DevPreempt{};
   h->pre_index.clear();
+  h->pre_dindex = nullptr;
+  h->pre_maxrow = 0;
   h->pre_n = 0;
+}
+
+// ksim_preempt_many's per-row slabs: sized by the bound table, so they go with it.
+void drop_many_slabs(ksim_handle* h) {
+  free_bufs(h->many_bufs);
+  h->many_res = nullptr;
+  h->many_vflag = nullptr;
+  h->many_slab_rows = 0;
 }
 
 bool is_sharded(const ksim_handle* h) { return h->comm != nullptr || h->shard_total != 0; }
@@ -2177,6 +2188,10 @@ void ksim_destroy(ksim_handle* h) {
   drop_loaded_pods(h);
   if (h->pod1_arena.p) (void)hipFree(h->pod1_arena.p);
   if (h->nom_arena.p) (void)hipFree(h->nom_arena.p);
+  if (h->many_arena.p) (void)hipFree(h->many_arena.p);
+  if (h->many_out.p) (void)hipFree(h->many_out.p);
+  if (h->many_stage.p) (void)hipHostFree(h->many_stage.p);
+  if (h->many_host.p) (void)hipHostFree(h->many_host.p);
   for (auto& a : h->fw_arena)
     if (a.p) (void)hipFree(a.p);
   if (h->fwh) (void)hipHostFree(h->fwh);
@@ -2373,7 +2388,7 @@ static void single_pod_set(const ksim_pod_set* ps, int32_t i, ksim_pod& pod, std
   copy_terms(pod.vz_first, pod.vz_count);
 }
 
-static int arena_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
+int ksim_host::arena_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
   if (bytes <= a.cap) return KSIM_OK;
   if (a.p) (void)hipFree(a.p);
   a.p = nullptr;
@@ -2593,6 +2608,53 @@ int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod
 
 int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P) {
   return upload_single(h, ps, pod_index, P, h->pod1_arena);
+}
+
+int ksim_host::pinbuf_reserve(ksim_handle* h, PinBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return KSIM_OK;
+  if (b.p) (void)hipHostFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
+  const hipError_t e = hipHostMalloc(&b.p, cap, hipHostMallocDefault);
+  if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (pinned buffer)");
+  b.cap = cap;
+  return KSIM_OK;
+}
+
+int ksim_host::upload_many(ksim_handle* h, const ksim_pod_set* ps, const int32_t* idx, int32_t n, size_t extra,
+                           std::vector<DevPods>& Ps, char** extra_host, char** extra_dev) {
+  std::vector<PodBlob> blobs((size_t)n);
+  std::vector<size_t> at((size_t)n);
+  size_t total = 0;
+  for (int32_t i = 0; i < n; i++) {
+    build_pod_blob(h, ps, idx[i], blobs[i]);
+    at[i] = total;
+    total += (blobs[i].bytes.size() + 63) & ~(size_t)63;
+  }
+  if (total + extra > h->many_arena.cap || total + extra > h->many_stage.cap)
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // reallocated: nothing may read them
+  int rc;
+  if ((rc = arena_reserve(h, h->many_arena, total + extra)) || (rc = pinbuf_reserve(h, h->many_stage, total + extra)))
+    return rc;
+  char* stage = (char*)h->many_stage.p;
+  std::memset(stage, 0, total + extra);
+  Ps.resize((size_t)n);
+  char* d = (char*)h->many_arena.p;
+  for (int32_t i = 0; i < n; i++) {
+    std::memcpy(stage + at[i], blobs[i].bytes.data(), blobs[i].bytes.size());
+    Ps[i] = blob_pods(h, blobs[i], d + at[i]);
+  }
+  h->many_stage_bytes = total + extra;
+  *extra_host = stage + total;
+  *extra_dev = d + total;
+  return KSIM_OK;
+}
+
+int ksim_host::upload_many_commit(ksim_handle* h) {
+  if (h->many_stage_bytes)
+    HIPCHK(h, hipMemcpyAsync(h->many_arena.p, h->many_stage.p, h->many_stage_bytes, hipMemcpyHostToDevice, h->stream));
+  return KSIM_OK;
 }
 
 // Copy one compat cycle's per-node outputs and scalars to the caller.
@@ -4151,7 +4213,7 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   DevState st;
   int rc = read_state(h, st);
   if (rc) return rc;
-  int64_t v[3 + 16 + 2 + 4 + 3 + 5 + 2] = {st.batches, st.truncations, st.cuts};
+  int64_t v[3 + 16 + 2 + 4 + 3 + 5 + 2 + 2] = {st.batches, st.truncations, st.cuts};
   if (h->has_cluster) HIPCHK(h, hcopy(h, v + 3, h->sc.dbg, 8 * 16, hipMemcpyDeviceToHost));
   if (unsigned long long* cp = cp_clock_buffer())   // KSIM_CP_CLOCKS builds: the chain + pairs phase clocks
     HIPCHK(h, hcopy(h, v + 3, cp, 8 * 8, hipMemcpyDeviceToHost));
@@ -4170,7 +4232,9 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   v[32] = h->feed_odd_ends;
   v[33] = st.stretches;
   v[34] = st.stretch_pods;
-  const int32_t m = n < 35 ? n : 35;
+  v[35] = h->many_rows;
+  v[36] = h->many_single;
+  const int32_t m = n < 37 ? n : 37;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
 }

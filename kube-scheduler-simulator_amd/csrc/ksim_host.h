@@ -29,6 +29,13 @@ struct DevArena {
   size_t cap = 0;
 };
 
+// Pinned host memory reused across calls, grown on demand (pinbuf_reserve; the
+// stream must be idle when it grows).
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
 // One pod (re-based) as a device pod set of its own, packed the way it is
 // uploaded: every piece at a 64-byte aligned offset of one blob.
 struct PodBlob {
@@ -185,6 +192,24 @@ struct ksim_handle {
   DevPreempt pre{};
   std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
   int32_t pre_n = 0;
+  // ksim_preempt_many.  With the bound table (dropped where pre_bufs is): the
+  // device copy of pre_index (in pre_bufs), the most bound pods one node holds,
+  // and, allocated at the first call that needs them, the per-row slabs of one
+  // launch group (many_slab_rows rows of PreemptNode[n] and of uint8_t[pre_n]).
+  // With the handle: the call's preemptor records and row table (one upload
+  // out of the pinned many_stage), the result buffer (pick records, then the
+  // victims lists) and its pinned host copy many_host; every call ends
+  // synchronized, so neither is in flight when the next call writes it.
+  const int32_t* pre_dindex = nullptr;
+  int32_t pre_maxrow = 0;
+  std::vector<DevBuf> many_bufs;
+  PreemptNode* many_res = nullptr;
+  uint8_t* many_vflag = nullptr;
+  int32_t many_slab_rows = 0;
+  DevArena many_arena, many_out;
+  PinBuf many_stage, many_host;
+  size_t many_stage_bytes = 0;          // of the call in flight
+  int64_t many_rows = 0, many_single = 0;   // rows answered by the batched / the single-pod launches (ksim_get_diag)
   // extender round trip (ksim_eval_pod_filter -> ksim_eval_pod_finish)
   DevPods pod1{};
   bool ext_pending = false;
@@ -348,6 +373,7 @@ int dev_alloc(ksim_handle* h, std::vector<DevBuf>& owner, T*& dst, size_t bytes,
 
 void drop_graphs(ksim_handle* h);
 void drop_loaded_pods(ksim_handle* h);
+void drop_many_slabs(ksim_handle* h);
 void drop_bound_pods(ksim_handle* h);
 bool is_sharded(const ksim_handle* h);
 int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i);
@@ -359,5 +385,15 @@ int set_run(ksim_handle* h, int32_t first, int32_t end);
 int pin_reserve(ksim_handle* h, size_t bytes);
 int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena);
 int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P);
-
+// Pods idx[0 .. n) of ps, each as upload_single would upload it, packed into
+// h->many_stage with `extra` more bytes behind them (64-byte aligned), and
+// h->many_arena grown to hold it all.  Ps[i]: pod i's device set; extra_host /
+// extra_dev: the extra bytes in the staging and where they land.  Nothing is
+// copied yet: the caller fills the extra bytes, then upload_many_commit
+// enqueues the one copy.
+int upload_many(ksim_handle* h, const ksim_pod_set* ps, const int32_t* idx, int32_t n, size_t extra,
+                std::vector<DevPods>& Ps, char** extra_host, char** extra_dev);
+int upload_many_commit(ksim_handle* h);
+int arena_reserve(ksim_handle* h, DevArena& a, size_t bytes);
+int pinbuf_reserve(ksim_handle* h, PinBuf& b, size_t bytes);
 }  // namespace ksim_host

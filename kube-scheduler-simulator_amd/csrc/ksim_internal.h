@@ -376,6 +376,47 @@ struct PreemptPlan {
 // in s.dom): the node kernel of the plan's form (ksim_preempt.hip), the static veto (vb / vz), the pick.
 void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& plan, hipStream_t stream);
 
+// The batched dry run (ksim_preempt_many): one launch group answers up to
+// kPreemptManyRows preemptors whose plans read no domain table, thread =
+// (node, row).  Every row owns what its dry run writes: a slab of per-node
+// results and one of victim flags, so rows of different priority never share a
+// mutable word.  One record per row, read at a block-uniform address.
+constexpr int kPreemptManyRows = 64;                         // KSIM_PREEMPT_MANY_ROWS
+constexpr size_t kPreemptManySlabBytes = (size_t)256 << 20;  // the slabs of one group stay under this
+constexpr int kPickWords = 8;                                // int32 words per pick record (five used)
+struct PreemptRow {
+  DevPods P;                           // the preemptor as pod 0 of a set of its own
+  PreemptVol vm;                       // voff: null for a row without volume uses
+  PreemptNode* res;                    // [n] the row's slab
+  uint8_t* vflag;                      // [n_bound] likewise
+  int32_t* victims;                    // [cap] the nominated node's victims, caller indices
+  int32_t cap;
+  int32_t prio;
+  uint32_t ports;                      // PreemptPlan::ports
+  int32_t vb, vz;                      // PreemptPlan::vb / vz
+};
+// Rows per launch group for a cluster of n nodes and a table of n_bound rows
+// (ksim_preempt_many_rows): rows x (sizeof(PreemptNode) n + n_bound) <= kPreemptManySlabBytes.
+constexpr int32_t preempt_many_rows(int64_t n, int64_t n_bound) {
+  const int64_t per = (int64_t)sizeof(PreemptNode) * (n > 0 ? n : 0) + (n_bound > 0 ? n_bound : 0);
+  const int64_t fit = per > 0 ? (int64_t)kPreemptManySlabBytes / per : kPreemptManyRows;
+  return (int32_t)(fit < 1 ? 1 : fit > kPreemptManyRows ? kPreemptManyRows : fit);
+}
+struct PreemptMany {
+  const PreemptRow* rows;              // the group's rows (device)
+  int32_t n_rows;
+  bool volume;                         // the group's form: VolumeForm, else FreeForm / PortsForm
+  PreemptNode* res;                    // [n_rows][n] the group's result slabs (row r's record names res + r n)
+  int32_t* pick;                       // [n_rows][kPickWords] the group's pick records
+  const int32_t* index;                // [n_bound] CSR position -> bound-pod table index (device)
+  uint64_t rank_lo, rank_hi;           // BatchProg's filter positions (FilterPlan)
+};
+// One group: the node kernel of the group's form (status step, victims, static
+// veto), the pick of every row, the victims lists.  pre: the table's shared,
+// read-only arrays (res / vflag / pick / nslot of it are not read).
+void launch_preempt_many(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& common, const PreemptMany& g,
+                         hipStream_t stream);
+
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);
 // topo: the pod carries uses; the PreFilter pass of its cycle runs first (the

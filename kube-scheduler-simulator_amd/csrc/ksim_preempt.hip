@@ -40,6 +40,17 @@
 // candidates in nodeTree order (upstream scans from a random offset; offset 0
 // here) until numCandidates were found and one of them has no PDB violation,
 // and picks one by pickOneNodeForPreemption's criteria.
+//
+// The batched dry run (ksim_preempt_many) answers many preemptors against one
+// snapshot: k_preempt_many_nodes runs the forms without a row side on a grid of
+// (node block, preemptor), each preemptor on result and flag slabs of its own
+// (two preemptors of different priority clear and mark different rows of one
+// node), with the filter status computed in the kernel instead of a filter
+// pass of its own; k_preempt_pick runs one block per preemptor, and
+// k_preempt_many_victims compacts each nominated node's victims on the device.
+// select_victims is the same code for both: a trial reads its pod, priority
+// and slabs through its PreemptCommon, the handle's own in k_preempt_nodes and
+// the row's view in k_preempt_many_nodes.
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
@@ -848,11 +859,113 @@ __device__ __forceinline__ bool better(const PreemptNode& a, int32_t na, const P
   return na < nb;                                        // the first candidate in scan order
 }
 
+// ---- the batched dry run (ksim_preempt_many) --------------------------------------
+// The node's TopoRow for the status step of a row whose plan reads no domain
+// table: the filters left (NodePorts, the volume limit plugins) read the
+// node's class counts of the uses in `read` and nothing else of the row, and
+// neither the domain tables nor the topology flags (load_topo_row's node_count
+// branch, entry for entry).
+__device__ __forceinline__ void load_count_row(const DevCluster& c, const ksim_topo_use* U, int nu, uint32_t read,
+                                               int32_t node, TopoRow& t) {
+#pragma unroll
+  for (int i = 0; i < KSIM_MAX_USES; i++) {
+    t.v[i] = 0;
+    t.x[i] = 0;
+    if (i < nu && ((read >> i) & 1u)) t.x[i] = class_count(c, load_use(U, i).cls, node);
+  }
+}
+
+// Per (node, row): the per-pod cycle's filter status of the row's preemptor on
+// the node (run_filter_plan, the status pass's own function, the code kept in
+// a register), then SelectVictimsOnNode as k_preempt_nodes runs it, on the
+// row's own slabs, then the static veto.  Grid ((n + 255) / 256, rows).  The
+// row record, its pod, plan and uses sit at block-uniform addresses: scalar
+// loads.  VOL: the group's form is VolumeForm, else FreeForm or, behind one
+// block-uniform branch, PortsForm.
+template <bool VOL, bool PDB>
+__global__ __launch_bounds__(256) void k_preempt_many_nodes(PreemptCommon a0, const PreemptRow* __restrict__ rows,
+                                                            uint64_t rank_lo, uint64_t rank_hi) {
+  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  // the node's row does not depend on the preemptor: its loads go out before the row record's chain
+  const int32_t xr = node < a0.c.n ? node : a0.c.n - 1;
+  const NodeRow r = load_row(a0.c, xr);
+  const PreemptRow& row = rows[blockIdx.y];
+  if (node >= a0.c.n) return;
+  PreemptCommon a = a0;                                  // the row's view: its pod, slabs, priority and port uses
+  a.P = row.P;
+  a.pre.res = row.res;
+  a.pre.vflag = row.vflag;
+  a.prio = row.prio;
+  a.port_mask = row.ports;
+  const ksim_pod& p = a.P.pods[0];
+  const PodPlan& pp = a.P.plans[0];
+  const ksim_topo_use* U = a.P.uses + p.use_first;
+  TopoRow t;
+  load_count_row(a.c, U, p.use_count, pp.m.port | pp.m.vol, node, t);
+  uint32_t det;
+  const uint32_t f = run_filter_plan(a.c, a.P, FilterPlan{rank_lo, rank_hi, pp.filter_en}, nullptr, 0u, p, r, U, pp.m,
+                                     t, det);
+  PreemptNode out{};
+  Trial x{a, p, pp, U, node, -1, 0, 0};
+  bool at_ipa = false, at_pts = false;
+  if constexpr (VOL) {
+    if (VolumeForm::potential(f, a, row.vm, at_ipa, at_pts)) select_victims<VolumeForm, PDB>(x, row.vm, at_ipa, at_pts, out);
+  } else {
+    const PreemptDom none{};
+    if (failed_fit_or_ports(f, a)) {
+      if (a.port_mask)                                   // block-uniform
+        select_victims<PortsForm, PDB>(x, none, at_ipa, at_pts, out);
+      else
+        select_victims<FreeForm, PDB>(x, none, at_ipa, at_pts, out);
+    }
+  }
+  if ((row.vb | row.vz) && out.cand) {                   // k_preempt_static_veto's rule
+    bool bad = false;
+    if (row.vb && p.vb_count) bad = volume_binding_fails(a.c, a.P, p.vb_first, p.vb_count, node) != 0;
+    if (!bad && row.vz && p.vz_count) bad = !volume_groups_match(a.c, a.P, p.vz_first, p.vz_count, node);
+    if (bad) out.cand = 0;
+  }
+  row.res[node] = out;
+}
+
+// The nominated node's victims of every row, in the dry run's list order
+// (preempt_read_back's): the rows flagged victim and violating, then the plain
+// victims, each in CSR order, as indices into the caller's table (index).  One
+// wave per row: it walks the node's range in the row's flag slab 64 rows at a
+// time and compacts by ballot and a running count.  Nothing is written at or
+// past the row's cap.
+__global__ __launch_bounds__(64) void k_preempt_many_victims(const PreemptRow* __restrict__ rows,
+                                                             const int32_t* __restrict__ pick,
+                                                             const int32_t* __restrict__ off,
+                                                             const int32_t* __restrict__ index) {
+  const PreemptRow& row = rows[blockIdx.x];
+  const int32_t node = pick[(size_t)blockIdx.x * kPickWords];
+  if (node < 0 || row.cap <= 0) return;
+  const int lane = threadIdx.x;
+  const int32_t j0 = off[node], j1 = off[node + 1];
+  int32_t k = 0;                                         // victims written so far (wave-uniform)
+  for (int pass = 0; pass < 2; pass++) {
+    const uint8_t want = pass == 0 ? (uint8_t)(1 | kPreemptViolating) : (uint8_t)1;
+    for (int32_t base = j0; base < j1 && k < row.cap; base += 64) {
+      const int32_t j = base + lane;
+      const bool hit = j < j1 && row.vflag[j] == want;
+      const uint64_t m = __ballot(hit);
+      const int32_t at = k + (int32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (hit && at < row.cap) row.victims[at] = index[j];
+      k += (int32_t)__popcll(m);
+    }
+  }
+}
+
 constexpr int kPickThreads = 1024;
 
-// min_pct / min_abs: DefaultPreemptionArgs (calculateNumCandidates)
+// min_pct / min_abs: DefaultPreemptionArgs (calculateNumCandidates).  Block r
+// scans the results at pre.res + r n and writes the record at pre.pick +
+// r kPickWords (the batched dry run's rows; one block for a single dry run).
 __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, DevPreempt pre, int32_t min_pct,
                                                                int32_t min_abs) {
+  pre.res += (size_t)blockIdx.x * c.n;
+  pre.pick += (size_t)blockIdx.x * kPickWords;
   __shared__ int32_t sh[3][kPickThreads / 64];
   __shared__ PreemptNode s_best[kPickThreads];
   __shared__ int32_t s_node[kPickThreads];
@@ -964,6 +1077,22 @@ void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, const PreemptPla
   else launch_nodes<FreeForm>(ca, fa.ds, stream);
   if (q.vb || q.vz) k_preempt_static_veto<<<(a.c.n + 255) / 256, 256, 0, stream>>>(a.c, a.P, a.st, pre, q.vb, q.vz);
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+}
+
+void launch_preempt_many(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& q, const PreemptMany& g,
+                         hipStream_t stream) {
+  if (g.n_rows <= 0) return;
+  // every row's own fields (its pod, slabs, priority, port uses) come from its record
+  const PreemptCommon ca{a.c, DevPods{}, a.st, a.s, pre, q.fit, 0, q.port, 0u};
+  const bool pdb = pre.poff != nullptr;
+  auto nodes = g.volume ? (pdb ? k_preempt_many_nodes<true, true> : k_preempt_many_nodes<true, false>)
+                        : (pdb ? k_preempt_many_nodes<false, true> : k_preempt_many_nodes<false, false>);
+  nodes<<<dim3((a.c.n + 255) / 256, g.n_rows), 256, 0, stream>>>(ca, g.rows, g.rank_lo, g.rank_hi);
+  DevPreempt slabs = pre;                               // block r: the slab and the record of row r
+  slabs.res = g.res;
+  slabs.pick = g.pick;
+  k_preempt_pick<<<g.n_rows, kPickThreads, 0, stream>>>(a.c, slabs, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+  k_preempt_many_victims<<<g.n_rows, 64, 0, stream>>>(g.rows, g.pick, pre.off, g.index);
 }
 
 }  // namespace ksim

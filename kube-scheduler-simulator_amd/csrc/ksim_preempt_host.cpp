@@ -53,8 +53,10 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
   free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
   free_bufs(h->pre_vol_bufs);                  // and the volume holdings
+  drop_many_slabs(h);                          // and ksim_preempt_many's slabs are sized by it
   h->pre_voff = nullptr;
   h->pre_vols = nullptr;
+  h->pre_dindex = nullptr;
   DevPreempt d{};
   if ((rc = dev_alloc(h, h->pre_bufs, d.off, 4 * off.size(), off.data())) ||
       (rc = dev_alloc(h, h->pre_bufs, d.prio, 4 * prio.size(), prio.data())) ||
@@ -68,12 +70,15 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   HIPCHK(h, hipMemsetAsync(d.nslot, 0xff, 4 * (size_t)std::max(N, 1), h->stream));   // -1: no group
   d.nreq = nullptr;
   if ((rc = dev_alloc(h, h->pre_bufs, d.afftot, 8 * (size_t)KSIM_MAX_USES)) ||
-      (rc = dev_alloc(h, h->pre_bufs, h->pre_smin, 8 * 3 * (size_t)KSIM_MAX_USES)))
+      (rc = dev_alloc(h, h->pre_bufs, h->pre_smin, 8 * 3 * (size_t)KSIM_MAX_USES)) ||
+      (rc = dev_alloc(h, h->pre_bufs, h->pre_dindex, 4 * (size_t)std::max(n, 1), n > 0 ? ix.data() : nullptr)))
     return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->pre = d;
   h->pre_index = ix;
   h->pre_n = n;
+  h->pre_maxrow = 0;
+  for (int32_t v = 0; v < N; v++) h->pre_maxrow = std::max(h->pre_maxrow, off[v + 1] - off[v]);
   return KSIM_OK;
 }
 
@@ -474,6 +479,132 @@ extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32
                                    const ksim_pod_set* nps, int32_t n_groups, const int32_t* gnodes,
                                    const int32_t* first, const int32_t* count, ksim_preempt_out* out) {
   return preempt_run(h, ps, pod_index, priority, {nps, n_groups, gnodes, first, count}, out, PreemptEntry::spread);
+}
+
+// ---- the batched dry run --------------------------------------------------------
+extern "C" int32_t ksim_preempt_many_rows(int32_t n_nodes, int32_t n_bound) {
+  return preempt_many_rows(n_nodes, n_bound);
+}
+
+// The slabs of one launch group of `rows` rows (kept with the bound table).
+static int many_slabs(ksim_handle* h, int32_t rows) {
+  if (rows <= h->many_slab_rows) return KSIM_OK;
+  int rc;
+  drop_many_slabs(h);                          // (every call ends synchronized: nothing reads them)
+  if ((rc = dev_alloc(h, h->many_bufs, h->many_res, sizeof(PreemptNode) * (size_t)rows * std::max(h->dc.n, 1))) ||
+      (rc = dev_alloc(h, h->many_bufs, h->many_vflag, (size_t)rows * std::max(h->pre_n, 1))))
+    return rc;
+  h->many_slab_rows = rows;
+  return KSIM_OK;
+}
+
+// Every row is ksim_preempt_full's dry run without nominated groups, against
+// the same snapshot: a dry run changes nothing on the device, so the rows are
+// independent.  A row whose plan reads no domain table (Fit, host ports,
+// counted volumes, volume groups; uses no Filter reads beside them) is one
+// blockIdx.y of a launch group; a row that reads them (required pod
+// (anti-)affinity, DoNotSchedule spread) runs the single-pod launches, since
+// the domain tables are the handle's.  Everything is validated before
+// anything runs.
+extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
+                                 const int32_t* priority, ksim_preempt_out* outs) {
+  if (!h) return KSIM_E_INVALID;
+  if (n < 0) return set_err(h, KSIM_E_INVALID, "ksim_preempt_many: negative row count");
+  if (n == 0) return KSIM_OK;
+  if (!ps || !pod_index || !priority || !outs) return set_err(h, KSIM_E_INVALID, "ksim_preempt_many: null argument");
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  const NominatedGroups none{nullptr, 0, nullptr, nullptr, nullptr};
+  std::vector<PreemptPlan> plans((size_t)n);
+  for (int32_t i = 0; i < n; i++)
+    if ((rc = preempt_check_args(h, ps, pod_index[i], none, &outs[i], PreemptEntry::full)) ||
+        (rc = preempt_plan(h, ps, pod_index[i], priority[i], PreemptEntry::full, plans[i]))) {
+      h->err = "ksim_preempt_many row " + std::to_string(i) + ": " + h->err;
+      return rc;
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  // the rows of the launch groups, by form (ports / free, then volume), each in the caller's order
+  std::vector<int32_t> brow, bidx;             // table position -> caller's row, its pod
+  for (int form = 0; form < 2; form++)
+    for (int32_t i = 0; i < n; i++)
+      if (!plans[i].reads_domains() && (plans[i].vol.voff != nullptr) == (form == 1)) {
+        brow.push_back(i);
+        bidx.push_back(pod_index[i]);
+      }
+  const int32_t N = h->dc.n, nb = (int32_t)brow.size();
+  std::vector<uint8_t> single((size_t)n, 1);
+  if (nb > 0) {
+    std::vector<DevPods> Ps;
+    char *thost = nullptr, *tdev = nullptr;
+    if ((rc = upload_many(h, ps, bidx.data(), nb, sizeof(PreemptRow) * (size_t)nb, Ps, &thost, &tdev))) return rc;
+    const int32_t R = preempt_many_rows(N, h->pre_n);
+    int32_t n_free = 0;
+    while (n_free < nb && plans[brow[n_free]].vol.voff == nullptr) n_free++;
+    if ((rc = many_slabs(h, std::min(R, std::max(n_free, nb - n_free))))) return rc;
+    // the result buffer: the pick records, then every row's victims list (no longer than a node's rows)
+    std::vector<int32_t> vat((size_t)nb + 1, 0), dcap((size_t)nb);
+    for (int32_t k = 0; k < nb; k++) {
+      const ksim_preempt_out& o = outs[brow[k]];
+      dcap[k] = o.victims && o.victims_cap > 0 ? std::min(o.victims_cap, h->pre_maxrow) : 0;
+      vat[(size_t)k + 1] = vat[k] + dcap[k];
+    }
+    const size_t words = (size_t)kPickWords * nb + (size_t)vat[nb];
+    if (4 * words > h->many_out.cap || 4 * words > h->many_host.cap) HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = arena_reserve(h, h->many_out, 4 * words)) || (rc = pinbuf_reserve(h, h->many_host, 4 * words))) return rc;
+    int32_t* dout = (int32_t*)h->many_out.p;
+    std::vector<PreemptRow> table((size_t)nb);
+    for (int32_t k = 0, g0 = 0; k < nb; k++) {
+      if (k == n_free || k - g0 == R) g0 = k;  // a group ends with its form or at R rows
+      const PreemptPlan& q = plans[brow[k]];
+      PreemptRow& r = table[k];
+      r.P = Ps[k];
+      r.vm = q.vol;
+      r.res = h->many_res + (size_t)(k - g0) * N;
+      r.vflag = h->many_vflag + (size_t)(k - g0) * std::max(h->pre_n, 1);
+      r.victims = dout + (size_t)kPickWords * nb + vat[k];
+      r.cap = dcap[k];
+      r.prio = q.prio;
+      r.ports = q.ports;
+      r.vb = q.vb, r.vz = q.vz;
+    }
+    std::memcpy(thost, table.data(), sizeof(PreemptRow) * (size_t)nb);
+    if ((rc = upload_many_commit(h))) return rc;
+    const LaunchArgs a = make_args(h, DevPods{}, nullptr);
+    DevPreempt pre = h->pre;
+    pre.res = nullptr, pre.vflag = nullptr, pre.pick = nullptr, pre.nslot = nullptr;   // per row; no groups
+    for (int32_t g0 = 0; g0 < nb;) {           // no host synchronization between the groups
+      const bool vol = g0 >= n_free;
+      const int32_t g1 = std::min(g0 + R, vol ? nb : n_free);
+      const PreemptMany g{(const PreemptRow*)tdev + g0, g1 - g0, vol, h->many_res, dout + (size_t)kPickWords * g0,
+                          h->pre_dindex, h->bp.rank_lo, h->bp.rank_hi};
+      launch_preempt_many(a, pre, plans[brow[g0]], g, h->stream);
+      HIPCHK(h, hipGetLastError());
+      g0 = g1;
+    }
+    const int32_t* hout = (const int32_t*)h->many_host.p;
+    HIPCHK(h, hipMemcpyAsync(h->many_host.p, dout, 4 * words, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int32_t k = 0; k < nb; k++) {
+      const int32_t* pick = hout + (size_t)kPickWords * k;
+      ksim_preempt_out& o = outs[brow[k]];
+      o.nominated = pick[0];
+      o.n_victims = pick[1];
+      o.n_potential = pick[2];
+      o.n_candidates = pick[3];
+      o.n_pdb_violations = pick[4];
+      if (pick[0] >= 0 && dcap[k] > 0)
+        std::memcpy(o.victims, hout + (size_t)kPickWords * nb + vat[k],
+                    4 * (size_t)std::min(pick[1], dcap[k]));
+      single[brow[k]] = 0;
+    }
+    h->many_rows += nb;
+  }
+  for (int32_t i = 0; i < n; i++) {            // the rows that read domain tables, after the groups
+    if (!single[i]) continue;
+    if ((rc = preempt_run(h, ps, pod_index[i], priority[i], none, &outs[i], PreemptEntry::full))) return rc;
+    h->many_single++;
+  }
+  return KSIM_OK;
 }
 
 // ---- selector / affinity-term matching (ksim_match.hip) ------

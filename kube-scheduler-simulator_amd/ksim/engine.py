@@ -33,6 +33,7 @@ EXPORTS = [
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
     "ksim_set_bound_pod_volumes", "ksim_preempt_volumes", "ksim_preempt_full",
+    "ksim_preempt_many", "ksim_preempt_many_rows",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -120,6 +121,10 @@ def _load(path):
         L.ksim_preempt_volumes.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     if hasattr(L, "ksim_preempt_full"):         # likewise
         L.ksim_preempt_full.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    if hasattr(L, "ksim_preempt_many"):         # likewise
+        L.ksim_preempt_many.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.ksim_preempt_many_rows.argtypes = [i32, i32]
+        L.ksim_preempt_many_rows.restype = i32
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -526,6 +531,39 @@ class Engine:
                        *(a.ctypes.data_as(ctypes.c_void_p) for a in (nodes, first, count)), ctypes.byref(out.c)))
         return result()
 
+    def preempt_many(self, pods, indices, priorities, with_pdb: bool = False, outs=None) -> list:
+        """The batched dry run (ksim_preempt_many): one answer per row, each
+        the tuple ``preempt(pods, indices[i], priorities[i], full=True,
+        with_pdb=with_pdb)`` returns on the same engine state, in the caller's
+        row order.  Every row is the what-if reading: no nominated groups, and
+        no row sees a nomination another row would make.  ``outs``: one
+        ``abi.PreemptOut`` per row to receive the answers (its victims array and
+        cap as the caller sized them); by default each is sized as ``preempt``
+        sizes its own."""
+        indices = np.ascontiguousarray(indices, np.int32)
+        priorities = np.ascontiguousarray(priorities, np.int32)
+        if indices.shape != priorities.shape or indices.ndim != 1:
+            raise ValueError("one priority per pod index")
+        n = int(indices.size)
+        if outs is None:
+            cap = max(getattr(self, "_bound_n", 1), 1)
+            outs = [abi.PreemptOut(cap) for _ in range(n)]
+        if len(outs) != n:
+            raise ValueError("one PreemptOut per row")
+        self._sync()
+        self._ran = True
+        ps = pods.pod_set()
+        arr = (abi._PreemptOutC * max(n, 1))()
+        for i, o in enumerate(outs):
+            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(o.c), ctypes.sizeof(abi._PreemptOutC))
+        try:
+            self._chk(self.L.ksim_preempt_many(self.h, ctypes.byref(ps), n, indices.ctypes.data_as(ctypes.c_void_p),
+                                               priorities.ctypes.data_as(ctypes.c_void_p), arr))
+        finally:
+            for i, o in enumerate(outs):
+                ctypes.memmove(ctypes.byref(o.c), ctypes.byref(arr[i]), ctypes.sizeof(abi._PreemptOutC))
+        return [o.result_with_pdb() if with_pdb else o.result() for o in outs]
+
     def match_terms(self, mp: abi.MatchProblem, n_words: int, counts: Optional[np.ndarray]) -> np.ndarray:
         """ksim_match_terms: [n_sigs][n_words] matcher bits; ``counts``
         ([n_classes][n_nodes] int32, or None) receives the class counts."""
@@ -619,8 +657,8 @@ class Engine:
 
     def diag(self) -> dict:
         """Batch-path diagnostics of the last schedule_loaded call."""
-        out = np.zeros(35, np.int64)
-        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 35)
+        out = np.zeros(37, np.int64)
+        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 37)
         if n < 0:
             self._chk(n)
         d = {"batches": int(out[0]), "truncations": int(out[1]), "cuts": int(out[2]),
@@ -634,7 +672,9 @@ class Engine:
              "feed_syncs": int(out[28]), "feed_past_end": int(out[29]), "feed_fallbacks": int(out[30]),
              "feed_topups": int(out[31]), "feed_odd_ends": int(out[32]),
              # deferred-commit batches that committed pods past their first pair cut, and those pods
-             "stretches": int(out[33]), "stretch_pods": int(out[34])}
+             "stretches": int(out[33]), "stretch_pods": int(out[34]),
+             # ksim_preempt_many's rows answered by the batched / by the single-pod launches
+             "preempt_many_rows": int(out[35]), "preempt_many_single": int(out[36])}
         if out[6]:
             d["chain_us"] = {"setup": out[3] / out[6] / 100.0, "rounds": out[4] / out[6] / 100.0,
                              "epilogue": out[5] / out[6] / 100.0, "rounds_per_batch": out[7] / out[6]}
