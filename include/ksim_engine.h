@@ -808,7 +808,9 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
  * KSIM_ONE_CUT=1 in the environment, read at every run, keeps every batch to
  * its first cut): [33] batches that committed pods there, [34] those pods;
  * out[35..36] ksim_preempt_many's rows since ksim_create: [35] rows answered
- * by the batched launches, [36] rows answered by the single-pod launches.
+ * by the batched launches, [36] rows answered by the single-pod launches;
+ * out[37] ksim_preempt_many_dom's rows that read domain tables (all answered by
+ * the batched launches; its other rows count in [35]).
  * Returns the number of values written (<= n). */
 int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n);
 /* The deferred-commit runs' enqueue rule (host arithmetic, no device): with
@@ -1124,7 +1126,8 @@ int ksim_preempt_full(ksim_handle* h, const ksim_pod_set* pods, int32_t pod_inde
  *               A row with required pod (anti-)affinity or DoNotSchedule spread
  *               uses the profile filters on is answered inside the same call
  *               by ksim_preempt_full's launches, one row after another (the
- *               domain tables are per handle).  ksim_get_diag out[35..36]
+ *               domain tables are per handle; ksim_preempt_many_dom below
+ *               batches these rows too).  ksim_get_diag out[35..36]
  *               count the two kinds.
  * Everything is checked before anything runs; on an error no row is written.
  * KSIM_E_INVALID (the message names the row): n < 0, a null array with n > 0,
@@ -1145,6 +1148,39 @@ int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* pods, int32_t n,
  * under 256 MiB (64 rows up to about 100,000 nodes with a million bound pods),
  * and never below one row. */
 int32_t ksim_preempt_many_rows(int32_t n_nodes, int32_t n_bound);
+
+/* ksim_preempt_many with the rows that read domain tables batched too.  The
+ * contract is ksim_preempt_many's, word for word: outs[i] is what
+ *   ksim_preempt_full(h, pods, pod_index[i], priority[i], NULL, 0, NULL, NULL, NULL, &outs[i])
+ * writes (the what-if reading), everything is checked before anything runs,
+ * an error names the row, the refusals are the same, and the snapshot, the
+ * class and attached counts, the handle's own domain tables and topology
+ * flags, nextStartNodeIndex and the pod sequence are left as they were.
+ *   routing     no row takes the single-pod launches.  A row with required pod
+ *               (anti-)affinity, existing pods' anti-affinity or DoNotSchedule
+ *               spread gets a PreFilter state of its own for the call (its
+ *               domain tables, critical-path minima, affinity totals and
+ *               topology flags), filled on the device, and runs in launch
+ *               groups of its own form (with or without counted volumes)
+ *               between the other groups and the one copy back: still one
+ *               synchronization per call.
+ *   counters    ksim_get_diag out[35] counts this call's rows without domain
+ *               reads, as ksim_preempt_many's; out[36] never moves in this
+ *               call; out[37] counts the rows with domain reads, answered by
+ *               the batched launches. */
+int ksim_preempt_many_dom(ksim_handle* h, const ksim_pod_set* pods, int32_t n,
+                          const int32_t* pod_index /* [n] */, const int32_t* priority /* [n] */,
+                          ksim_preempt_out* outs /* [n], each with its own victims / victims_cap */);
+/* Host arithmetic, no device: the rows one launch group of domain rows takes,
+ * in [1, KSIM_PREEMPT_MANY_ROWS].  Beside its result and flag slabs every such
+ * row owns KSIM_MAX_USES domain tables of n_values entries (8 bytes each;
+ * n_values: the most value ids of any label column, hostname included, plus
+ * the absent value); the group is sized so that
+ *   rows x (32 n_nodes + n_bound + 8 KSIM_MAX_USES n_values)
+ * stays under 256 MiB (64 rows at 10,000 nodes, 100,000 bound pods and 10,001
+ * values), and never below one row.  The tables are allocated at the first
+ * call that needs them and freed with the bound table. */
+int32_t ksim_preempt_many_dom_rows(int32_t n_nodes, int32_t n_bound, int32_t n_values);
 
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's

@@ -251,6 +251,22 @@ func (e *Engine) PreemptMany(ps *C.ksim_pod_set, idx, priority []int32, outs []C
 	})
 }
 
+// PreemptManyDom: PreemptMany's answers, with the rows that carry required pod
+// (anti-)affinity or DoNotSchedule spread batched as well (each on a PreFilter
+// state of its own) instead of answered by single dry runs inside the call.
+func (e *Engine) PreemptManyDom(ps *C.ksim_pod_set, idx, priority []int32, outs []C.ksim_preempt_out) error {
+	if len(priority) != len(idx) || len(outs) != len(idx) {
+		return fmt.Errorf("PreemptManyDom: %d pods, %d priorities, %d outs", len(idx), len(priority), len(outs))
+	}
+	if len(idx) == 0 {
+		return nil
+	}
+	return e.locked(func() C.int {
+		return C.ksim_preempt_many_dom(e.h, ps, C.int32_t(len(idx)), (*C.int32_t)(unsafe.Pointer(&idx[0])),
+			(*C.int32_t)(unsafe.Pointer(&priority[0])), &outs[0])
+	})
+}
+
 // FwFilterNominated: RunFilterPluginsWithNominatedPods' first pass of the
 // cycle in flight on the grouped nodes (plugins.go calls it per node).
 func (e *Engine) FwFilterNominated(nominated *C.ksim_pod_set, nodes, first, count []int32, fail []uint8,

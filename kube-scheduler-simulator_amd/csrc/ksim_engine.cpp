@@ -198,6 +198,10 @@ void drop_many_slabs(ksim_handle* h) {
   h->many_res = nullptr;
   h->many_vflag = nullptr;
   h->many_slab_rows = 0;
+  free_bufs(h->many_dom_bufs);                 // ksim_preempt_many_dom's tables: sized by the cluster's vmax
+  h->many_dom = nullptr;
+  h->many_heads = nullptr;
+  h->many_dom_rows = 0;
 }
 
 bool is_sharded(const ksim_handle* h) { return h->comm != nullptr || h->shard_total != 0; }
@@ -4213,7 +4217,7 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   DevState st;
   int rc = read_state(h, st);
   if (rc) return rc;
-  int64_t v[3 + 16 + 2 + 4 + 3 + 5 + 2 + 2] = {st.batches, st.truncations, st.cuts};
+  int64_t v[3 + 16 + 2 + 4 + 3 + 5 + 2 + 3] = {st.batches, st.truncations, st.cuts};
   if (h->has_cluster) HIPCHK(h, hcopy(h, v + 3, h->sc.dbg, 8 * 16, hipMemcpyDeviceToHost));
   if (unsigned long long* cp = cp_clock_buffer())   // KSIM_CP_CLOCKS builds: the chain + pairs phase clocks
     HIPCHK(h, hcopy(h, v + 3, cp, 8 * 8, hipMemcpyDeviceToHost));
@@ -4234,7 +4238,8 @@ extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {
   v[34] = st.stretch_pods;
   v[35] = h->many_rows;
   v[36] = h->many_single;
-  const int32_t m = n < 37 ? n : 37;
+  v[37] = h->many_dom_answered;
+  const int32_t m = n < 38 ? n : 38;
   for (int32_t i = 0; i < m; i++) out[i] = v[i];
   return m;
 }

@@ -206,10 +206,17 @@ struct ksim_handle {
   PreemptNode* many_res = nullptr;
   uint8_t* many_vflag = nullptr;
   int32_t many_slab_rows = 0;
+  // ksim_preempt_many_dom's PreFilter states of one launch group of domain rows
+  // (many_dom_rows rows of int64[KSIM_MAX_USES][vmax] and of PreemptDomHead), kept and dropped with the slabs above
+  std::vector<DevBuf> many_dom_bufs;
+  int64_t* many_dom = nullptr;
+  PreemptDomHead* many_heads = nullptr;
+  int32_t many_dom_rows = 0;
   DevArena many_arena, many_out;
   PinBuf many_stage, many_host;
   size_t many_stage_bytes = 0;          // of the call in flight
   int64_t many_rows = 0, many_single = 0;   // rows answered by the batched / the single-pod launches (ksim_get_diag)
+  int64_t many_dom_answered = 0;        // ksim_preempt_many_dom's domain rows, by the batched launches
   // extender round trip (ksim_eval_pod_filter -> ksim_eval_pod_finish)
   DevPods pod1{};
   bool ext_pending = false;

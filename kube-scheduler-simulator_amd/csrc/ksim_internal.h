@@ -417,6 +417,43 @@ struct PreemptMany {
 void launch_preempt_many(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& common, const PreemptMany& g,
                          hipStream_t stream);
 
+// ksim_preempt_many_dom: a row whose plan reads domain tables gets a PreFilter
+// state of its own, the per-handle words of a single dry run once per row: the
+// domain tables (dom, load_topo_row's indexing: [KSIM_MAX_USES][vmax]) and the
+// small words beside them.  What a row reads of both is zero when its group starts.
+struct PreemptDomHead {
+  int64_t min_match[KSIM_MAX_USES];    // DevScratch.min_match: per DoNotSchedule use, the minimum over the present pairs
+  int64_t smin[KSIM_MAX_USES][3];      // PreemptPlan.smin: {min1, the arg-min's value id, min2}
+  int64_t afftot[KSIM_MAX_USES];       // DevPreempt.afftot
+  uint32_t topo_flags;                 // DevState.topo_flags (kTopoAffinityNonEmpty alone: nothing scores)
+  uint32_t _pad;
+};
+// Row k's record beside PreemptRow k (the same blockIdx.y).
+struct PreemptDomRow {
+  int64_t* dom;                        // [KSIM_MAX_USES][vmax] the row's tables
+  PreemptDomHead* head;
+  uint32_t aff, anti, exist, hard;     // PreemptPlan's masks of the row
+};
+// Rows per launch group of domain rows (ksim_preempt_many_dom_rows): the
+// results, the flags and the tables of a group stay under kPreemptManySlabBytes.
+constexpr int32_t preempt_many_dom_rows(int64_t n, int64_t n_bound, int64_t n_values) {
+  const int64_t per = (int64_t)sizeof(PreemptNode) * (n > 0 ? n : 0) + (n_bound > 0 ? n_bound : 0) +
+                      8 * (int64_t)KSIM_MAX_USES * (n_values > 0 ? n_values : 0);
+  const int64_t fit = per > 0 ? (int64_t)kPreemptManySlabBytes / per : kPreemptManyRows;
+  return (int32_t)(fit < 1 ? 1 : fit > kPreemptManyRows ? kPreemptManyRows : fit);
+}
+struct PreemptManyDom {
+  const PreemptDomRow* drows;          // the group's rows (device), beside PreemptMany.rows
+  bool full;                           // the group's form: FullForm, else SpreadForm (hard may be empty)
+  bool spread;                         // some row of the group has a DoNotSchedule use (k_preempt_many_mins runs)
+};
+// One group of domain rows: what the rows read of their tables and heads zeroed
+// (k_preempt_many_zero), every row's PreFilter pass (k_preempt_many_dom) and
+// minima (k_preempt_many_mins), then the node kernel of the group's row form,
+// the picks and the victims lists.
+void launch_preempt_many_dom(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& common,
+                             const PreemptMany& g, const PreemptManyDom& d, hipStream_t stream);
+
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);
 // topo: the pod carries uses; the PreFilter pass of its cycle runs first (the

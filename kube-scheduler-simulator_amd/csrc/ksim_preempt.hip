@@ -50,7 +50,12 @@
 // k_preempt_many_victims compacts each nominated node's victims on the device.
 // select_victims is the same code for both: a trial reads its pod, priority
 // and slabs through its PreemptCommon, the handle's own in k_preempt_nodes and
-// the row's view in k_preempt_many_nodes.
+// the row's view in k_preempt_many_nodes.  ksim_preempt_many_dom also batches
+// the preemptors with a row side: each gets a PreFilter state of its own for
+// the call (k_preempt_many_dom: its domain tables, affinity totals and
+// topology flags; k_preempt_many_mins: its critical-path minima), and
+// k_preempt_many_dom_nodes runs SpreadForm or FullForm through a row's view
+// that also swaps those in.
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
@@ -774,28 +779,20 @@ __global__ __launch_bounds__(256) void k_preempt_totals(DevCluster c, DevPods P,
 // smin[3 i ..] = {the minimum, the value id of one arg-min, the minimum
 // over the present values other than that one}; math.MaxInt32 where there is
 // none.  Launched after the status pass, before k_preempt_nodes.
-__global__ __launch_bounds__(256) void k_preempt_spread_mins(DevCluster c, DevPods P,
-                                                             const DevState* __restrict__ st, DevScratch s,
-                                                             int64_t* __restrict__ smin, uint32_t hard) {
+// block_spread_mins is the block's walk (k_preempt_many_mins runs it too):
+// over the present entries of d[0 .. V), those three in every thread (-1: no arg-min).
+__device__ __forceinline__ void block_spread_mins(const int64_t* __restrict__ d, int32_t V, int64_t& m1, int32_t& v1,
+                                                  int64_t& m2) {
   __shared__ int64_t sh_m[4];
   __shared__ int32_t sh_v[4];
   __shared__ int64_t s_m1;
   __shared__ int32_t s_v1;
   constexpr int64_t kNone = 2147483647;
-  int i = 0;                                           // this block's use
-  for (int k = blockIdx.x; i < KSIM_MAX_USES; i++)
-    if (((hard >> i) & 1u) && k-- == 0) break;
-  if (i >= KSIM_MAX_USES) return;
-  const int32_t pi = st->cursor;
-  const ksim_pod& p = P.pods[pi];
-  const ksim_topo_use u = load_use(P.uses + p.use_first, i);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int32_t V = u.col != KSIM_COL_NONE ? c.col_nvals[u.col] : 0;
-  const int64_t* d = ((P.plans[pi].m.ptab >> i) & 1u) ? P.ptab + u._pad : s.dom + (size_t)i * c.vmax;
   // the pair (count, value id), smallest count first, then the smallest id
   auto less = [](int64_t ma, int32_t va, int64_t mb, int32_t vb) { return ma < mb || (ma == mb && va < vb); };
-  int64_t m1 = kNone, m2 = kNone;
-  int32_t v1 = -1;
+  m1 = kNone, m2 = kNone;
+  v1 = -1;
   for (int pass = 0; pass < 2; pass++) {               // pass 1: the same over the values other than v1
     int64_t m = kNone;
     int32_t at = INT32_MAX;
@@ -840,7 +837,23 @@ __global__ __launch_bounds__(256) void k_preempt_spread_mins(DevCluster c, DevPo
       m2 = s_m1;
     }
   }
-  if (tid == 0) {
+}
+__global__ __launch_bounds__(256) void k_preempt_spread_mins(DevCluster c, DevPods P,
+                                                             const DevState* __restrict__ st, DevScratch s,
+                                                             int64_t* __restrict__ smin, uint32_t hard) {
+  int i = 0;                                           // this block's use
+  for (int k = blockIdx.x; i < KSIM_MAX_USES; i++)
+    if (((hard >> i) & 1u) && k-- == 0) break;
+  if (i >= KSIM_MAX_USES) return;
+  const int32_t pi = st->cursor;
+  const ksim_pod& p = P.pods[pi];
+  const ksim_topo_use u = load_use(P.uses + p.use_first, i);
+  const int32_t V = u.col != KSIM_COL_NONE ? c.col_nvals[u.col] : 0;
+  const int64_t* d = ((P.plans[pi].m.ptab >> i) & 1u) ? P.ptab + u._pad : s.dom + (size_t)i * c.vmax;
+  int64_t m1, m2;
+  int32_t v1;
+  block_spread_mins(d, V, m1, v1, m2);
+  if (threadIdx.x == 0) {
     smin[3 * i] = m1;
     smin[3 * i + 1] = v1;
     smin[3 * i + 2] = m2;
@@ -955,6 +968,196 @@ __global__ __launch_bounds__(64) void k_preempt_many_victims(const PreemptRow* _
       k += (int32_t)__popcll(m);
     }
   }
+}
+
+// ---- the batched dry run's domain rows (ksim_preempt_many_dom) --------------------
+// A row whose plan reads domain tables runs on a PreFilter state of its own
+// (PreemptDomRow: tables in load_topo_row's indexing, and a head with the words
+// a single dry run keeps per handle).  Four kernels per group, each on a grid
+// with the row in blockIdx.y.
+constexpr int kManyLdsDom = 128;   // tables of key columns with <= kManyLdsDom value ids are LDS-staged
+
+// Before a group's PreFilter pass: what its rows read of their states is zero,
+// whatever the group before left there.  Block (i, row) clears the entries of
+// use i's table that load_topo_row can reach (the value ids of its key column)
+// when the use has a table at all; block (0, row) also clears the head.  Grid
+// (KSIM_MAX_USES, rows).
+__global__ __launch_bounds__(256) void k_preempt_many_zero(DevCluster c, const PreemptRow* __restrict__ rows,
+                                                           const PreemptDomRow* __restrict__ drows) {
+  const int i = blockIdx.x;
+  const PreemptDomRow& dr = drows[blockIdx.y];
+  const DevPods& P = rows[blockIdx.y].P;
+  if (i == 0) {
+    int64_t* w = reinterpret_cast<int64_t*>(dr.head);
+    for (int x = threadIdx.x; x < (int)(sizeof(PreemptDomHead) / 8); x += blockDim.x) w[x] = 0;
+  }
+  if (!((P.plans[0].m.dom >> i) & 1u)) return;              // block-uniform
+  const int32_t V = c.col_nvals[load_use(P.uses + P.pods[0].use_first, i).col];
+  int64_t* d = dr.dom + (size_t)i * c.vmax;
+  for (int32_t v = threadIdx.x; v < V; v += blockDim.x) d[v] = 0;
+}
+
+// k_topo_prefilter's rule for the row's preemptor, for the uses a Filter reads
+// (the status step never scores): per node, its class count into the entry of
+// its value in every such table, a DoNotSchedule use's with the presence mark
+// and only from the nodes PodTopologySpread counts (every hard key on the
+// node, and the use's node inclusion policies); kTopoAffinityNonEmpty; and in
+// the same pass k_preempt_totals' sums (afftot[i]: the class count over the
+// nodes that carry the key, hostname-keyed uses included): a block sum in
+// LDS, then one atomic per block and affinity use.  Integer atomics throughout, so the
+// result does not depend on the order.  Grid ((n + 255) / 256, rows).
+__global__ __launch_bounds__(256) void k_preempt_many_dom(DevCluster c, const PreemptRow* __restrict__ rows,
+                                                          const PreemptDomRow* __restrict__ drows) {
+  __shared__ unsigned long long s_dom[KSIM_MAX_USES][kManyLdsDom];
+  __shared__ unsigned long long s_tot[KSIM_MAX_USES];
+  __shared__ uint32_t s_flags;
+  const PreemptDomRow& dr = drows[blockIdx.y];
+  const DevPods& P = rows[blockIdx.y].P;           // block-uniform: scalar loads
+  const ksim_pod& p = P.pods[0];
+  const UseMasks& m = P.plans[0].m;
+  const ksim_topo_use* U = P.uses + p.use_first;
+  const uint32_t rd = m.hard | m.aff | m.anti | m.exist;   // the uses whose label and count the pass reads
+  const uint32_t need = rd & m.dom;                         // ... and those with a table
+  uint32_t lds = 0;                                         // uses whose table is staged in LDS
+  for (uint32_t b = need; b; b &= b - 1) {
+    const int i = __builtin_ctz(b);
+    if (c.col_nvals[load_use(U, i).col] <= kManyLdsDom) lds |= 1u << i;
+  }
+  const int tid = threadIdx.x;
+  for (int x = tid; x < KSIM_MAX_USES * kManyLdsDom; x += blockDim.x) s_dom[x / kManyLdsDom][x % kManyLdsDom] = 0;
+  if (tid < KSIM_MAX_USES) s_tot[tid] = 0;
+  if (tid == 0) s_flags = 0;
+  __syncthreads();
+  const int32_t node = blockIdx.x * blockDim.x + tid;
+  uint32_t flags = 0;
+  if (node < c.n) {
+    uint32_t val[KSIM_MAX_USES];
+    int64_t cnt[KSIM_MAX_USES];
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {               // every load of the node first
+      val[i] = 0;
+      cnt[i] = 0;
+      if ((rd >> i) & 1u) {
+        const ksim_topo_use u = load_use(U, i);
+        if (u.col != KSIM_COL_NONE) val[i] = c.labels[(size_t)u.col * c.n + node];
+        cnt[i] = class_count(c, u.cls, node);
+      }
+    }
+    bool all_hard = true;                                   // nodeLabelsMatchSpreadConstraints
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      if (((m.hard >> i) & 1u) && val[i] == 0) all_hard = false;
+      if (((m.aff >> i) & 1u) && val[i] != 0 && cnt[i] > 0) {
+        flags |= kTopoAffinityNonEmpty;
+        atomicAdd(&s_tot[i], (unsigned long long)cnt[i]);   // the block's sum, in LDS
+      }
+    }
+    // matchNodeInclusionPolicies, once per node for every spread use
+    const bool aff_ok = (m.honor_aff & m.hard) ? required_node_affinity_match(c, P, p, node) : true;
+    const bool taint_ok = (m.honor_taints & m.hard) ? !node_has_untolerated_taint(c, p, node) : true;
+#pragma unroll
+    for (int i = 0; i < KSIM_MAX_USES; i++) {
+      const uint32_t v = val[i];
+      if (!((need >> i) & 1u) || v == 0) continue;          // no table, or the node has no pair for this key
+      const bool incl = (!((m.honor_aff >> i) & 1u) || aff_ok) && (!((m.honor_taints >> i) & 1u) || taint_ok);
+      int64_t add = cnt[i];
+      if ((m.hard >> i) & 1u)                               // TpPairToMatchNum[pair] += count (+ presence mark)
+        add = all_hard && incl ? add + (1ll << kDomMarkShift) : 0;
+      if (add == 0) continue;
+      if ((lds >> i) & 1u)
+        atomicAdd(&s_dom[i][v], (unsigned long long)add);
+      else
+        atomicAdd(reinterpret_cast<unsigned long long*>(dr.dom + (size_t)i * c.vmax + v), (unsigned long long)add);
+    }
+  }
+  if (flags) atomicOr(&s_flags, flags);
+  __syncthreads();
+  for (int x = tid; x < KSIM_MAX_USES * kManyLdsDom; x += blockDim.x) {
+    if (!((lds >> (x / kManyLdsDom)) & 1u)) continue;
+    const unsigned long long v = s_dom[x / kManyLdsDom][x % kManyLdsDom];
+    if (v) atomicAdd(reinterpret_cast<unsigned long long*>(dr.dom + (size_t)(x / kManyLdsDom) * c.vmax + x % kManyLdsDom), v);
+  }
+  if (tid < KSIM_MAX_USES && s_tot[tid])
+    atomicAdd(reinterpret_cast<unsigned long long*>(&dr.head->afftot[tid]), s_tot[tid]);
+  if (tid == 0 && s_flags) atomicOr(&dr.head->topo_flags, s_flags);
+}
+
+// k_preempt_spread_mins over the row's own table: block (i, row) takes use i
+// when it is a DoNotSchedule use of the row, and also leaves the minimum where
+// the status step's pts_filter reads it (k_topo_min's word).  Grid
+// (KSIM_MAX_USES, rows).
+__global__ __launch_bounds__(256) void k_preempt_many_mins(DevCluster c, const PreemptRow* __restrict__ rows,
+                                                           const PreemptDomRow* __restrict__ drows) {
+  const int i = blockIdx.x;
+  const PreemptDomRow& dr = drows[blockIdx.y];
+  if (!((dr.hard >> i) & 1u)) return;                       // block-uniform
+  const DevPods& P = rows[blockIdx.y].P;
+  const ksim_topo_use u = load_use(P.uses + P.pods[0].use_first, i);
+  const int32_t V = u.col != KSIM_COL_NONE ? c.col_nvals[u.col] : 0;
+  int64_t m1, m2;
+  int32_t v1;
+  block_spread_mins(dr.dom + (size_t)i * c.vmax, V, m1, v1, m2);
+  if (threadIdx.x == 0) {
+    dr.head->smin[i][0] = m1;
+    dr.head->smin[i][1] = v1;
+    dr.head->smin[i][2] = m2;
+    dr.head->min_match[i] = m1;
+  }
+}
+
+// k_preempt_many_nodes for a group of rows with a row side: the status step
+// reads the row's tables, minima and topology flags, and the trial state is
+// RowForm<true> (hard may be empty: affinity alone) or FullForm, through the
+// row's view of PreemptCommon (its tables and afftot swapped in beside its pod
+// and slabs).  ipa_index / pts_index: PreemptDom's and PreemptSpread's.
+template <class FORM, bool PDB>
+__global__ __launch_bounds__(256) void k_preempt_many_dom_nodes(PreemptCommon a0, const PreemptRow* __restrict__ rows,
+                                                                const PreemptDomRow* __restrict__ drows,
+                                                                int32_t ipa_index, int32_t pts_index, uint64_t rank_lo,
+                                                                uint64_t rank_hi) {
+  const int32_t node = blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t xr = node < a0.c.n ? node : a0.c.n - 1;
+  const NodeRow r = load_row(a0.c, xr);
+  const PreemptRow& row = rows[blockIdx.y];
+  const PreemptDomRow& dr = drows[blockIdx.y];
+  if (node >= a0.c.n) return;
+  PreemptCommon a = a0;
+  a.P = row.P;
+  a.pre.res = row.res;
+  a.pre.vflag = row.vflag;
+  a.pre.afftot = dr.head->afftot;
+  a.s.dom = dr.dom;
+  a.s.min_match = dr.head->min_match;
+  a.prio = row.prio;
+  a.port_mask = row.ports;
+  const ksim_pod& p = a.P.pods[0];
+  const PodPlan& pp = a.P.plans[0];
+  const ksim_topo_use* U = a.P.uses + p.use_first;
+  uint32_t f;
+  {
+    TopoRow t;
+    load_topo_row(a.c, U, p.use_count, pp.m, a.s, a.P.ptab, node, t);
+    uint32_t det;
+    f = run_filter_plan(a.c, a.P, FilterPlan{rank_lo, rank_hi, pp.filter_en}, a.s.min_match, dr.head->topo_flags, p, r,
+                        U, pp.m, t, det);
+  }
+  PreemptNode out{};
+  Trial x{a, p, pp, U, node, -1, 0, 0};
+  bool at_ipa = false, at_pts = false;
+  const PreemptSpread ds{{dr.aff, dr.anti, dr.exist, ipa_index}, dr.hard, pts_index, &dr.head->smin[0][0]};
+  if constexpr (std::is_same_v<FORM, FullForm>) {
+    const PreemptFull fa{ds, row.vm};
+    if (FullForm::potential(f, a, fa, at_ipa, at_pts)) select_victims<FullForm, PDB>(x, fa, at_ipa, at_pts, out);
+  } else {
+    if (FORM::potential(f, a, ds, at_ipa, at_pts)) select_victims<FORM, PDB>(x, ds, at_ipa, at_pts, out);
+  }
+  if ((row.vb | row.vz) && out.cand) {                   // k_preempt_static_veto's rule
+    bool bad = false;
+    if (row.vb && p.vb_count) bad = volume_binding_fails(a.c, a.P, p.vb_first, p.vb_count, node) != 0;
+    if (!bad && row.vz && p.vz_count) bad = !volume_groups_match(a.c, a.P, p.vz_first, p.vz_count, node);
+    if (bad) out.cand = 0;
+  }
+  row.res[node] = out;
 }
 
 constexpr int kPickThreads = 1024;
@@ -1079,6 +1282,15 @@ void launch_preempt(const LaunchArgs& a, const DevPreempt& pre, const PreemptPla
   k_preempt_pick<<<1, kPickThreads, 0, stream>>>(a.c, pre, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
 }
 
+// The end of a launch group of either kind: every row's pick, then its victims list.
+static void launch_many_picks(const LaunchArgs& a, const DevPreempt& pre, const PreemptMany& g, hipStream_t stream) {
+  DevPreempt slabs = pre;                               // block r: the slab and the record of row r
+  slabs.res = g.res;
+  slabs.pick = g.pick;
+  k_preempt_pick<<<g.n_rows, kPickThreads, 0, stream>>>(a.c, slabs, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
+  k_preempt_many_victims<<<g.n_rows, 64, 0, stream>>>(g.rows, g.pick, pre.off, g.index);
+}
+
 void launch_preempt_many(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& q, const PreemptMany& g,
                          hipStream_t stream) {
   if (g.n_rows <= 0) return;
@@ -1088,11 +1300,22 @@ void launch_preempt_many(const LaunchArgs& a, const DevPreempt& pre, const Preem
   auto nodes = g.volume ? (pdb ? k_preempt_many_nodes<true, true> : k_preempt_many_nodes<true, false>)
                         : (pdb ? k_preempt_many_nodes<false, true> : k_preempt_many_nodes<false, false>);
   nodes<<<dim3((a.c.n + 255) / 256, g.n_rows), 256, 0, stream>>>(ca, g.rows, g.rank_lo, g.rank_hi);
-  DevPreempt slabs = pre;                               // block r: the slab and the record of row r
-  slabs.res = g.res;
-  slabs.pick = g.pick;
-  k_preempt_pick<<<g.n_rows, kPickThreads, 0, stream>>>(a.c, slabs, a.prof.preempt_min_pct, a.prof.preempt_min_abs);
-  k_preempt_many_victims<<<g.n_rows, 64, 0, stream>>>(g.rows, g.pick, pre.off, g.index);
+  launch_many_picks(a, pre, g, stream);
+}
+
+void launch_preempt_many_dom(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& q, const PreemptMany& g,
+                             const PreemptManyDom& d, hipStream_t stream) {
+  if (g.n_rows <= 0) return;
+  const PreemptCommon ca{a.c, DevPods{}, a.st, a.s, pre, q.fit, 0, q.port, 0u};
+  const bool pdb = pre.poff != nullptr;
+  const dim3 grid((a.c.n + 255) / 256, g.n_rows);
+  k_preempt_many_zero<<<dim3(KSIM_MAX_USES, g.n_rows), 256, 0, stream>>>(a.c, g.rows, d.drows);
+  k_preempt_many_dom<<<grid, 256, 0, stream>>>(a.c, g.rows, d.drows);
+  if (d.spread) k_preempt_many_mins<<<dim3(KSIM_MAX_USES, g.n_rows), 256, 0, stream>>>(a.c, g.rows, d.drows);
+  auto nodes = d.full ? (pdb ? k_preempt_many_dom_nodes<FullForm, true> : k_preempt_many_dom_nodes<FullForm, false>)
+                      : (pdb ? k_preempt_many_dom_nodes<SpreadForm, true> : k_preempt_many_dom_nodes<SpreadForm, false>);
+  nodes<<<grid, 256, 0, stream>>>(ca, g.rows, d.drows, q.ipa, q.pts, g.rank_lo, g.rank_hi);
+  launch_many_picks(a, pre, g, stream);
 }
 
 }  // namespace ksim

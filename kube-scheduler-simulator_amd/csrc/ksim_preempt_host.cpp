@@ -485,33 +485,52 @@ extern "C" int ksim_preempt_spread(ksim_handle* h, const ksim_pod_set* ps, int32
 extern "C" int32_t ksim_preempt_many_rows(int32_t n_nodes, int32_t n_bound) {
   return preempt_many_rows(n_nodes, n_bound);
 }
+extern "C" int32_t ksim_preempt_many_dom_rows(int32_t n_nodes, int32_t n_bound, int32_t n_values) {
+  return preempt_many_dom_rows(n_nodes, n_bound, n_values);
+}
 
-// The slabs of one launch group of `rows` rows (kept with the bound table).
-static int many_slabs(ksim_handle* h, int32_t rows) {
-  if (rows <= h->many_slab_rows) return KSIM_OK;
+// The slabs of one launch group of `rows` rows (kept with the bound table),
+// and for `dom_rows` of them the PreFilter states of domain rows.
+static int many_slabs(ksim_handle* h, int32_t rows, int32_t dom_rows) {
   int rc;
-  drop_many_slabs(h);                          // (every call ends synchronized: nothing reads them)
-  if ((rc = dev_alloc(h, h->many_bufs, h->many_res, sizeof(PreemptNode) * (size_t)rows * std::max(h->dc.n, 1))) ||
-      (rc = dev_alloc(h, h->many_bufs, h->many_vflag, (size_t)rows * std::max(h->pre_n, 1))))
-    return rc;
-  h->many_slab_rows = rows;
+  if (rows > h->many_slab_rows) {              // (every call ends synchronized: nothing reads them)
+    free_bufs(h->many_bufs);
+    h->many_slab_rows = 0;
+    if ((rc = dev_alloc(h, h->many_bufs, h->many_res, sizeof(PreemptNode) * (size_t)rows * std::max(h->dc.n, 1))) ||
+        (rc = dev_alloc(h, h->many_bufs, h->many_vflag, (size_t)rows * std::max(h->pre_n, 1))))
+      return rc;
+    h->many_slab_rows = rows;
+  }
+  if (dom_rows > h->many_dom_rows) {
+    free_bufs(h->many_dom_bufs);
+    h->many_dom_rows = 0;
+    if ((rc = dev_alloc(h, h->many_dom_bufs, h->many_dom, 8 * (size_t)dom_rows * KSIM_MAX_USES * h->dc.vmax)) ||
+        (rc = dev_alloc(h, h->many_dom_bufs, h->many_heads, sizeof(PreemptDomHead) * (size_t)dom_rows)))
+      return rc;
+    h->many_dom_rows = dom_rows;
+  }
   return KSIM_OK;
 }
 
 // Every row is ksim_preempt_full's dry run without nominated groups, against
 // the same snapshot: a dry run changes nothing on the device, so the rows are
-// independent.  A row whose plan reads no domain table (Fit, host ports,
-// counted volumes, volume groups; uses no Filter reads beside them) is one
-// blockIdx.y of a launch group; a row that reads them (required pod
-// (anti-)affinity, DoNotSchedule spread) runs the single-pod launches, since
-// the domain tables are the handle's.  Everything is validated before
-// anything runs.
-extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
-                                 const int32_t* priority, ksim_preempt_out* outs) {
+// independent.  The rows run in launch groups, one blockIdx.y each, every group
+// uniform in its form:
+//   0  FreeForm / PortsForm   Fit, host ports (uses no Filter reads beside them)
+//   1  VolumeForm             counted volumes
+//   2  SpreadForm             required pod (anti-)affinity, DoNotSchedule spread
+//   3  FullForm               ... beside counted volumes
+// A row of form 2 or 3 reads domain tables.  With `domains` (ksim_preempt_many_dom)
+// it gets a PreFilter state of its own for its group; without (ksim_preempt_many)
+// it runs the single-pod launches on the handle's tables after the groups.
+// Everything is validated before anything runs.  fn: the entry point, as the
+// error texts name it.
+static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
+                            const int32_t* priority, ksim_preempt_out* outs, bool domains, const std::string& fn) {
   if (!h) return KSIM_E_INVALID;
-  if (n < 0) return set_err(h, KSIM_E_INVALID, "ksim_preempt_many: negative row count");
+  if (n < 0) return set_err(h, KSIM_E_INVALID, fn + ": negative row count");
   if (n == 0) return KSIM_OK;
-  if (!ps || !pod_index || !priority || !outs) return set_err(h, KSIM_E_INVALID, "ksim_preempt_many: null argument");
+  if (!ps || !pod_index || !priority || !outs) return set_err(h, KSIM_E_INVALID, fn + ": null argument");
   int rc = ensure_ready(h);
   if (rc) return rc;
   const NominatedGroups none{nullptr, 0, nullptr, nullptr, nullptr};
@@ -519,28 +538,43 @@ extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t
   for (int32_t i = 0; i < n; i++)
     if ((rc = preempt_check_args(h, ps, pod_index[i], none, &outs[i], PreemptEntry::full)) ||
         (rc = preempt_plan(h, ps, pod_index[i], priority[i], PreemptEntry::full, plans[i]))) {
-      h->err = "ksim_preempt_many row " + std::to_string(i) + ": " + h->err;
+      h->err = fn + " row " + std::to_string(i) + ": " + h->err;
       return rc;
     }
   HIPCHK(h, hipSetDevice(h->device));
-  // the rows of the launch groups, by form (ports / free, then volume), each in the caller's order
-  std::vector<int32_t> brow, bidx;             // table position -> caller's row, its pod
-  for (int form = 0; form < 2; form++)
+  auto form_of = [](const PreemptPlan& q) {    // launch_preempt's choice of form
+    const bool vol = q.vol.voff != nullptr;
+    return q.reads_domains() ? (vol && q.vol.uses ? 3 : 2) : (vol ? 1 : 0);
+  };
+  // the rows of the launch groups, by form, each in the caller's order
+  std::vector<int32_t> brow, bidx, bform;      // table position -> caller's row, its pod, its form
+  for (int form = 0; form < (domains ? 4 : 2); form++)
     for (int32_t i = 0; i < n; i++)
-      if (!plans[i].reads_domains() && (plans[i].vol.voff != nullptr) == (form == 1)) {
+      if (form_of(plans[i]) == form) {
         brow.push_back(i);
         bidx.push_back(pod_index[i]);
+        bform.push_back(form);
       }
   const int32_t N = h->dc.n, nb = (int32_t)brow.size();
   std::vector<uint8_t> single((size_t)n, 1);
   if (nb > 0) {
     std::vector<DevPods> Ps;
     char *thost = nullptr, *tdev = nullptr;
-    if ((rc = upload_many(h, ps, bidx.data(), nb, sizeof(PreemptRow) * (size_t)nb, Ps, &thost, &tdev))) return rc;
-    const int32_t R = preempt_many_rows(N, h->pre_n);
-    int32_t n_free = 0;
-    while (n_free < nb && plans[brow[n_free]].vol.voff == nullptr) n_free++;
-    if ((rc = many_slabs(h, std::min(R, std::max(n_free, nb - n_free))))) return rc;
+    const size_t row_bytes = (sizeof(PreemptRow) * (size_t)nb + 63) / 64 * 64;   // then the domain rows' records
+    if ((rc = upload_many(h, ps, bidx.data(), nb, row_bytes + sizeof(PreemptDomRow) * (size_t)nb, Ps, &thost, &tdev)))
+      return rc;
+    const int32_t R = preempt_many_rows(N, h->pre_n), RD = preempt_many_dom_rows(N, h->pre_n, h->dc.vmax);
+    // a group ends with its form or at its form's row count
+    std::vector<int32_t> gfirst((size_t)nb);    // table position -> its group's first position
+    int32_t most = 0, most_dom = 0, n_dom = 0;
+    for (int32_t k = 0, g0 = 0; k < nb; k++) {
+      const bool dom = bform[k] >= 2;
+      if (bform[k] != bform[g0] || k - g0 == (dom ? RD : R)) g0 = k;
+      gfirst[k] = g0;
+      most = std::max(most, k - g0 + 1);
+      if (dom) most_dom = std::max(most_dom, k - g0 + 1), n_dom++;
+    }
+    if ((rc = many_slabs(h, most, most_dom))) return rc;
     // the result buffer: the pick records, then every row's victims list (no longer than a node's rows)
     std::vector<int32_t> vat((size_t)nb + 1, 0), dcap((size_t)nb);
     for (int32_t k = 0; k < nb; k++) {
@@ -552,32 +586,51 @@ extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t
     if (4 * words > h->many_out.cap || 4 * words > h->many_host.cap) HIPCHK(h, hipStreamSynchronize(h->stream));
     if ((rc = arena_reserve(h, h->many_out, 4 * words)) || (rc = pinbuf_reserve(h, h->many_host, 4 * words))) return rc;
     int32_t* dout = (int32_t*)h->many_out.p;
+    const size_t dom_words = (size_t)KSIM_MAX_USES * h->dc.vmax;   // of one row's tables
     std::vector<PreemptRow> table((size_t)nb);
-    for (int32_t k = 0, g0 = 0; k < nb; k++) {
-      if (k == n_free || k - g0 == R) g0 = k;  // a group ends with its form or at R rows
+    std::vector<PreemptDomRow> dtable((size_t)nb);
+    for (int32_t k = 0; k < nb; k++) {
+      const int32_t at = k - gfirst[k];        // the row's place in its group: its slabs
       const PreemptPlan& q = plans[brow[k]];
       PreemptRow& r = table[k];
       r.P = Ps[k];
       r.vm = q.vol;
-      r.res = h->many_res + (size_t)(k - g0) * N;
-      r.vflag = h->many_vflag + (size_t)(k - g0) * std::max(h->pre_n, 1);
+      r.res = h->many_res + (size_t)at * N;
+      r.vflag = h->many_vflag + (size_t)at * std::max(h->pre_n, 1);
       r.victims = dout + (size_t)kPickWords * nb + vat[k];
       r.cap = dcap[k];
       r.prio = q.prio;
       r.ports = q.ports;
       r.vb = q.vb, r.vz = q.vz;
+      PreemptDomRow& d = dtable[k];
+      d = PreemptDomRow{};
+      if (bform[k] >= 2) {
+        d.dom = h->many_dom + (size_t)at * dom_words;
+        d.head = h->many_heads + at;
+        d.aff = q.aff, d.anti = q.anti, d.exist = q.exist, d.hard = q.hard;
+      }
     }
     std::memcpy(thost, table.data(), sizeof(PreemptRow) * (size_t)nb);
+    std::memcpy(thost + row_bytes, dtable.data(), sizeof(PreemptDomRow) * (size_t)nb);
     if ((rc = upload_many_commit(h))) return rc;
     const LaunchArgs a = make_args(h, DevPods{}, nullptr);
     DevPreempt pre = h->pre;
     pre.res = nullptr, pre.vflag = nullptr, pre.pick = nullptr, pre.nslot = nullptr;   // per row; no groups
+    pre.afftot = nullptr;                      // (a domain row's is in its head)
     for (int32_t g0 = 0; g0 < nb;) {           // no host synchronization between the groups
-      const bool vol = g0 >= n_free;
-      const int32_t g1 = std::min(g0 + R, vol ? nb : n_free);
-      const PreemptMany g{(const PreemptRow*)tdev + g0, g1 - g0, vol, h->many_res, dout + (size_t)kPickWords * g0,
+      int32_t g1 = g0 + 1;
+      while (g1 < nb && gfirst[g1] == g0) g1++;
+      const int form = bform[g0];
+      const PreemptMany g{(const PreemptRow*)tdev + g0, g1 - g0, form == 1, h->many_res, dout + (size_t)kPickWords * g0,
                           h->pre_dindex, h->bp.rank_lo, h->bp.rank_hi};
-      launch_preempt_many(a, pre, plans[brow[g0]], g, h->stream);
+      if (form >= 2) {
+        bool spread = false;
+        for (int32_t k = g0; k < g1; k++) spread |= plans[brow[k]].hard != 0;
+        const PreemptManyDom d{(const PreemptDomRow*)(tdev + row_bytes) + g0, form == 3, spread};
+        launch_preempt_many_dom(a, pre, plans[brow[g0]], g, d, h->stream);
+      } else {
+        launch_preempt_many(a, pre, plans[brow[g0]], g, h->stream);
+      }
       HIPCHK(h, hipGetLastError());
       g0 = g1;
     }
@@ -597,14 +650,25 @@ extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t
                     4 * (size_t)std::min(pick[1], dcap[k]));
       single[brow[k]] = 0;
     }
-    h->many_rows += nb;
+    h->many_rows += nb - n_dom;
+    h->many_dom_answered += n_dom;
   }
-  for (int32_t i = 0; i < n; i++) {            // the rows that read domain tables, after the groups
+  for (int32_t i = 0; i < n && !domains; i++) {   // the rows that read domain tables, after the groups
     if (!single[i]) continue;
     if ((rc = preempt_run(h, ps, pod_index[i], priority[i], none, &outs[i], PreemptEntry::full))) return rc;
     h->many_single++;
   }
   return KSIM_OK;
+}
+
+extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
+                                 const int32_t* priority, ksim_preempt_out* outs) {
+  return preempt_many_run(h, ps, n, pod_index, priority, outs, false, "ksim_preempt_many");
+}
+
+extern "C" int ksim_preempt_many_dom(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
+                                     const int32_t* priority, ksim_preempt_out* outs) {
+  return preempt_many_run(h, ps, n, pod_index, priority, outs, true, "ksim_preempt_many_dom");
 }
 
 // ---- selector / affinity-term matching (ksim_match.hip) ------

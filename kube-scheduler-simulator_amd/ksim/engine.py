@@ -33,7 +33,7 @@ EXPORTS = [
     "ksim_match_terms", "ksim_set_eval_range", "ksim_fw_prefilter", "ksim_fw_score", "ksim_fw_normalize",
     "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
     "ksim_set_bound_pod_volumes", "ksim_preempt_volumes", "ksim_preempt_full",
-    "ksim_preempt_many", "ksim_preempt_many_rows",
+    "ksim_preempt_many", "ksim_preempt_many_rows", "ksim_preempt_many_dom", "ksim_preempt_many_dom_rows",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -76,6 +76,12 @@ def lib():
     if _LIB is None:
         _LIB = _load(LIB_PATH)
     return _LIB
+
+
+def preempt_many_dom_rows(n_nodes: int, n_bound: int, n_values: int) -> int:
+    """ksim_preempt_many_dom_rows: the rows one launch group of domain rows takes
+    (host arithmetic; ``n_values``: the most value ids of any label column plus one)."""
+    return int(lib().ksim_preempt_many_dom_rows(n_nodes, n_bound, n_values))
 
 
 def _load(path):
@@ -125,6 +131,10 @@ def _load(path):
         L.ksim_preempt_many.argtypes = [vp, vp, i32, vp, vp, vp]
         L.ksim_preempt_many_rows.argtypes = [i32, i32]
         L.ksim_preempt_many_rows.restype = i32
+    if hasattr(L, "ksim_preempt_many_dom"):     # likewise
+        L.ksim_preempt_many_dom.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.ksim_preempt_many_dom_rows.argtypes = [i32, i32, i32]
+        L.ksim_preempt_many_dom_rows.restype = i32
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -531,7 +541,8 @@ class Engine:
                        *(a.ctypes.data_as(ctypes.c_void_p) for a in (nodes, first, count)), ctypes.byref(out.c)))
         return result()
 
-    def preempt_many(self, pods, indices, priorities, with_pdb: bool = False, outs=None) -> list:
+    def preempt_many(self, pods, indices, priorities, with_pdb: bool = False, outs=None,
+                     domains: bool = False) -> list:
         """The batched dry run (ksim_preempt_many): one answer per row, each
         the tuple ``preempt(pods, indices[i], priorities[i], full=True,
         with_pdb=with_pdb)`` returns on the same engine state, in the caller's
@@ -539,7 +550,10 @@ class Engine:
         no row sees a nomination another row would make.  ``outs``: one
         ``abi.PreemptOut`` per row to receive the answers (its victims array and
         cap as the caller sized them); by default each is sized as ``preempt``
-        sizes its own."""
+        sizes its own.  ``domains``: through ksim_preempt_many_dom, which gives
+        the same answers and also batches the rows with required pod
+        (anti-)affinity or DoNotSchedule spread instead of answering them by
+        single dry runs inside the call."""
         indices = np.ascontiguousarray(indices, np.int32)
         priorities = np.ascontiguousarray(priorities, np.int32)
         if indices.shape != priorities.shape or indices.ndim != 1:
@@ -557,8 +571,9 @@ class Engine:
         for i, o in enumerate(outs):
             ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(o.c), ctypes.sizeof(abi._PreemptOutC))
         try:
-            self._chk(self.L.ksim_preempt_many(self.h, ctypes.byref(ps), n, indices.ctypes.data_as(ctypes.c_void_p),
-                                               priorities.ctypes.data_as(ctypes.c_void_p), arr))
+            call = self.L.ksim_preempt_many_dom if domains else self.L.ksim_preempt_many
+            self._chk(call(self.h, ctypes.byref(ps), n, indices.ctypes.data_as(ctypes.c_void_p),
+                           priorities.ctypes.data_as(ctypes.c_void_p), arr))
         finally:
             for i, o in enumerate(outs):
                 ctypes.memmove(ctypes.byref(o.c), ctypes.byref(arr[i]), ctypes.sizeof(abi._PreemptOutC))
@@ -657,8 +672,8 @@ class Engine:
 
     def diag(self) -> dict:
         """Batch-path diagnostics of the last schedule_loaded call."""
-        out = np.zeros(37, np.int64)
-        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 37)
+        out = np.zeros(38, np.int64)
+        n = self.L.ksim_get_diag(self.h, out.ctypes.data_as(ctypes.c_void_p), 38)
         if n < 0:
             self._chk(n)
         d = {"batches": int(out[0]), "truncations": int(out[1]), "cuts": int(out[2]),
@@ -674,7 +689,9 @@ class Engine:
              # deferred-commit batches that committed pods past their first pair cut, and those pods
              "stretches": int(out[33]), "stretch_pods": int(out[34]),
              # ksim_preempt_many's rows answered by the batched / by the single-pod launches
-             "preempt_many_rows": int(out[35]), "preempt_many_single": int(out[36])}
+             "preempt_many_rows": int(out[35]), "preempt_many_single": int(out[36]),
+             # ksim_preempt_many_dom's rows with domain reads (all by the batched launches)
+             "preempt_many_dom": int(out[37])}
         if out[6]:
             d["chain_us"] = {"setup": out[3] / out[6] / 100.0, "rounds": out[4] / out[6] / 100.0,
                              "epilogue": out[5] / out[6] / 100.0, "rounds_per_batch": out[7] / out[6]}
