@@ -673,7 +673,8 @@ int ksim_get_next_start(ksim_handle* h, int32_t* next_start) {
 int ksim_set_next_start(ksim_handle* h, int32_t next_start) {
   if (const int prc = flush_pend_bind(h)) return prc;   // a queued Reserve lands first
   if (!h) return KSIM_E_INVALID;
-  if (h->has_cluster && (next_start < 0 || next_start >= std::max(h->dc.n, 1)))
+  // a global position: a node shard scans the whole ring (dc.n_total == dc.n unsharded)
+  if (h->has_cluster && (next_start < 0 || next_start >= std::max(h->dc.n_total, 1)))
     return set_err(h, KSIM_E_INVALID, "next_start out of range");
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hcopy(h, &h->st->next_start, &next_start, 4, hipMemcpyHostToDevice));
