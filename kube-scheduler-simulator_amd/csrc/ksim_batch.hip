@@ -1795,14 +1795,6 @@ void launch_sweep_flush(const DevCluster& c, const DevPods& P, const SweepLane* 
   k_sweep_top_commit<true, false><<<dim3(kBatchPods, lanes), 1024, 0, stream>>>(c, P, tab);
 }
 
-// In-process shard group: M = max over the group's pmax arrays, written back to each.
-__global__ __launch_bounds__(kBatchPods) void k_group_max(GroupPtrs g) {
-  const int j = threadIdx.x;
-  uint64_t m = 0;
-  for (int r = 0; r < g.n; r++) m = umax64(m, g.p[r][j]);
-  for (int r = 0; r < g.n; r++) g.p[r][j] = m;
-}
-
 const char* const kBatchKernelNames[kKernelsPerBatch] = {"k_batch_top", "k_batch_chain_pairs", "k_batch_commit"};
 
 // Evaluation and per-pod top-T (xsend: the sharded record, else null).
@@ -1878,7 +1870,5 @@ void launch_shard_chain(const LaunchArgs& a, int32_t world, hipStream_t stream) 
 void launch_shard_commit(const LaunchArgs& a, hipStream_t stream) {
   k_batch_commit<<<1, kBatchPods, 0, stream>>>(a.c, a.P, a.st, a.s.gkey, a.s.chain_end, a.s.pmax, a.chosen, nullptr);
 }
-
-void launch_group_max(const GroupPtrs& g, hipStream_t stream) { k_group_max<<<1, kBatchPods, 0, stream>>>(g); }
 
 }  // namespace ksim

@@ -121,14 +121,19 @@ int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t b
 
 namespace {
 
+// The shard-group graphs a leader holds (group_graph).
+void drop_group_graphs(ksim_handle* h) {
+  for (auto& kv : h->sg_graphs) (void)hipGraphExecDestroy(kv.second);
+  h->sg_graphs.clear();
+}
+
 // The per-pod cycle graphs (their kernels take the profile by value).
 void drop_cycle_graphs(ksim_handle* h) {
   for (auto& g : h->graph_cycle) {
     if (g) (void)hipGraphExecDestroy(g);
     g = nullptr;
   }
-  for (auto& kv : h->sg_graphs) (void)hipGraphExecDestroy(kv.second);
-  h->sg_graphs.clear();
+  drop_group_graphs(h);
   h->graph_gen++;
 }
 
@@ -633,6 +638,41 @@ int read_state(ksim_handle* h, DevState& st) {
   return KSIM_OK;
 }
 
+// reps x body(i) on `stream` (idle: the caller has synchronised it) as an
+// instantiated graph in *out.  body returns KSIM_OK or a code; a capture that
+// began is always ended.  On failure *out is null and `what` names the call
+// that failed (a body that failed reads as an invalidated capture).
+template <class B>
+hipError_t capture_graph(hipStream_t stream, int reps, B&& body, hipGraphExec_t* out, const char*& what) {
+  *out = nullptr;
+  what = "hipStreamBeginCapture";
+  hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) return e;
+  bool ok = true;
+  for (int i = 0; ok && i < reps; i++) ok = body(i) == KSIM_OK;
+  hipGraph_t g = nullptr;
+  what = "hipStreamEndCapture";
+  e = hipStreamEndCapture(stream, &g);            // ends a capture even after a failed launch
+  if (e == hipSuccess && !(ok && g)) e = hipErrorStreamCaptureInvalidated;
+  if (e == hipSuccess) {
+    what = "hipGraphInstantiate";
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) *out = nullptr;
+  }
+  if (g) (void)hipGraphDestroy(g);
+  return e;
+}
+
+// A single handle's graph of reps x launch(i): a failure is the handle's error.
+template <class L>
+int capture_launches(ksim_handle* h, int reps, L&& launch, hipGraphExec_t* out) {
+  const char* what;
+  const hipError_t e = capture_graph(h->stream, reps, [&](int i) { return launch(i), (int)KSIM_OK; }, out, what);
+  if (e != hipSuccess) return hip_fail(h, e, what);
+  h->graph_captures++;
+  return KSIM_OK;
+}
+
 int capture(ksim_handle* h, bool batch, bool topo, hipGraphExec_t* out, bool fast = false, bool fuse_min = false,
             bool fuse_ext = false, bool ptab = false, bool stab = false) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -642,24 +682,14 @@ int capture(ksim_handle* h, bool batch, bool topo, hipGraphExec_t* out, bool fas
   a.fuse_min = fuse_min;
   a.fuse_ext = fuse_ext;
   a.ptab = ptab;
-  hipGraph_t g = nullptr;
-  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  if (batch)
-    for (int i = 0; i < kGraphBatches; i++) {
-      if (adapt_mode(h))
-        launch_batch_adapt(a, h->stream);
-      else
-        launch_batch(a, h->stream);
-    }
-  else
-    for (int i = 0; i < kGraphCycles; i++) launch_cycle(a, h->stream, false, topo);
-  hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
-  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e != hipSuccess) return hip_fail(h, e, "hipGraphInstantiate");
-  h->graph_captures++;
-  return KSIM_OK;
+  if (!batch) return capture_launches(h, kGraphCycles, [&](int) { launch_cycle(a, h->stream, false, topo); }, out);
+  const bool adapt = adapt_mode(h);
+  return capture_launches(h, kGraphBatches, [&](int) {
+    if (adapt)
+      launch_batch_adapt(a, h->stream);
+    else
+      launch_batch(a, h->stream);
+  }, out);
 }
 
 
@@ -675,18 +705,8 @@ int run_tbatch(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
   HIPCHK(h, hipMemsetAsync(h->sc.tb_vhold, 0, 4 * (size_t)kTbPods * kVarSlots * 2 * KSIM_MAX_SCORE, h->stream));
   if (!h->graph_tbatch) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kGraphBatches; i++) launch_tbatch(la, h->stream);
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
-    e = hipGraphInstantiate(&h->graph_tbatch, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-      h->graph_tbatch = nullptr;
-      return hip_fail(h, e, "hipGraphInstantiate");
-    }
-    h->graph_captures++;
+    if ((rc = capture_launches(h, kGraphBatches, [&](int) { launch_tbatch(la, h->stream); }, &h->graph_tbatch)))
+      return rc;
   }
   int32_t cursor = a;
   while (cursor < b) {
@@ -743,8 +763,7 @@ int sync_one_cut(ksim_handle* h) {
   for (auto& kv : h->sweep_graphs)
     if (kv.second) (void)hipGraphExecDestroy(kv.second);
   h->sweep_graphs.clear();
-  for (auto& kv : h->sg_graphs) (void)hipGraphExecDestroy(kv.second);   // a replica group's (its leader's)
-  h->sg_graphs.clear();
+  drop_group_graphs(h);                           // a replica group's (its leader's)
   h->one_cut = want;
   return KSIM_OK;
 }
@@ -1002,19 +1021,7 @@ int lazy_end_run(ksim_handle* h, int64_t f) {
 
 // kGraphBatches (tail: kLazySlots) batches of the flavour from ring phase 0.
 int capture_lazy(ksim_handle* h, const LaunchArgs& la, bool rt, int batches, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  for (int i = 0; i < batches; i++) lazy_launch(h, lazy_batch(h, la, i, rt), h->stream);
-  hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
-  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e != hipSuccess) {
-    *out = nullptr;
-    return hip_fail(h, e, "hipGraphInstantiate");
-  }
-  h->graph_captures++;
-  return KSIM_OK;
+  return capture_launches(h, batches, [&](int i) { lazy_launch(h, lazy_batch(h, la, i, rt), h->stream); }, out);
 }
 
 // KSIM_FEED_FLUSH=1 (read at every run): every stretch ends with a flush and
@@ -1350,19 +1357,10 @@ int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lan
   hipGraphExec_t& graph = h->sweep_graphs[{lanes, def}];
   if (!graph && count >= kBatchPods * kGraphBatches) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kGraphBatches; i++)
-      launch_sweep_batch(c, P, tab + (size_t)(i & 3) * kSweepMaxLanes, lanes, def, h->stream);
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (e != hipSuccess) return hip_fail(h, e, "hipStreamEndCapture");
-    e = hipGraphInstantiate(&graph, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-      graph = nullptr;
-      return hip_fail(h, e, "hipGraphInstantiate");
-    }
-    h->graph_captures++;
+    if ((rc = capture_launches(h, kGraphBatches, [&](int i) {
+           launch_sweep_batch(c, P, tab + (size_t)(i & 3) * kSweepMaxLanes, lanes, def, h->stream);
+         }, &graph)))
+      return rc;
   }
   auto phase_tab = [&](int64_t i) { return tab + (size_t)(i & 3) * kSweepMaxLanes; };
   int64_t i = 0;
@@ -1512,14 +1510,159 @@ int for_each_run(ksim_handle* h, int32_t first, int32_t count, F&& fn, bool adap
 }
 
 // ---- node-sharded batch path ----------------------------------
-// One batch on every shard of a group, phases separated by the two exchanges:
-// all-gather of the per-shard candidate records, all-reduce (max) of the pair
-// keys.  `hs` is either {this rank's handle} with an RCCL communicator (one
+// The shard-group runtime: five protocols (the P100 batch, the replicated
+// deferred-commit batch, the replicated topology batch, the per-pod cycle, the
+// ADAPT batch) over one exchange layer (group_all_gather, group_all_reduce),
+// one graph cache (group_graph) and one run loop (group_run).
+//
+// A group is either {this rank's handle} with an RCCL communicator (one
 // process per GPU) or an in-process group of shard handles on one device
-// (exchanges by device copies).  Everything runs on `stream`, asynchronously.
-// Replicated handles hold every node: each evaluates its range, and the pair
-// keys and binds of every guess are local, so the pair-key all-reduce is not
-// needed (one exchange per batch).
+// (exchanges by the group kernels).  Every member's kernels and the exchanges
+// run on the leader's stream, asynchronously.
+struct Group {
+  const std::vector<ksim_handle*>& hs;
+  ksim_handle* h0;                                // the leader: its stream, communicator and graph cache
+  hipStream_t stream;
+  int32_t world;
+  explicit Group(const std::vector<ksim_handle*>& v)
+      : hs(v), h0(v[0]), stream(v[0]->stream), world(v[0]->comm ? v[0]->world : (int32_t)v.size()) {}
+  int32_t rank(size_t i) const { return h0->comm ? h0->rank : (int32_t)i; }
+};
+
+template <class F>
+GroupPtrs group_ptrs(const Group& g, F&& ptr) {
+  GroupPtrs p{};
+  p.n = (int32_t)g.hs.size();
+  for (size_t i = 0; i < g.hs.size(); i++) p.p[i] = (uint64_t*)ptr(g.hs[i]);
+  return p;
+}
+
+// All-gather of `words` 8-byte words per member: src(h) -> dst(h) + rank * words.
+// RCCL across processes, k_group_gather in process.
+template <class S, class D>
+int group_all_gather(const Group& g, S&& src, D&& dst, size_t words) {
+  if (g.h0->comm) {
+    const ncclResult_t r = rccl().all_gather(src(g.h0), dst(g.h0), words, ncclUint64, g.h0->comm, g.stream);
+    if (r != ncclSuccess) return set_err(g.h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
+    return KSIM_OK;
+  }
+  if (g.hs.size() * g.hs.size() * words > ((size_t)1 << 30))   // the kernel's grid stride counts in 32 bits
+    return set_err(g.h0, KSIM_E_UNSUPPORTED, "shard group exchange too large for an in-process group");
+  launch_group_gather(group_ptrs(g, src), group_ptrs(g, dst), (int32_t)words, g.stream);
+  return KSIM_OK;
+}
+
+// Element-wise all-reduce of a per-member device buffer of `count` 8-byte
+// words: sum (int64) or max (uint64).  RCCL across processes, k_group_reduce
+// in process.
+template <class F>
+int group_all_reduce(const Group& g, F&& ptr, int64_t count, bool op_max) {
+  if (count <= 0) return KSIM_OK;
+  if (g.h0->comm) {
+    void* b = (void*)ptr(g.h0);
+    const ncclResult_t r = rccl().all_reduce(b, b, (size_t)count, op_max ? ncclUint64 : ncclInt64,
+                                             op_max ? ncclMax : ncclSum, g.h0->comm, g.stream);
+    if (r != ncclSuccess) return set_err(g.h0, KSIM_E_RCCL, std::string("ncclAllReduce: ") + rccl().error_string(r));
+  } else if (g.hs.size() > 1) {
+    launch_group_reduce(group_ptrs(g, ptr), count, op_max, g.stream);
+  }
+  return KSIM_OK;
+}
+
+constexpr auto sc_xsend = [](ksim_handle* h) { return h->sc.xsend; };
+constexpr auto sc_xrecv = [](ksim_handle* h) { return h->sc.xrecv; };
+constexpr auto sc_pmax = [](ksim_handle* h) { return h->sc.pmax; };
+
+// reps x body(i) of one kind as a graph on the leader (its stream carries every
+// member's kernels and the collectives), cached under `key` while the group is
+// the same handles at the graph generations they had at capture; nullptr when
+// capture is off or fails (the caller runs eagerly).
+template <class B>
+hipGraphExec_t group_graph(const Group& g, const GroupGraphKey& key, int reps, B&& body) {
+  ksim_handle* h0 = g.h0;
+  if (h0->sg_off || ab(kAbShardGraph)) return nullptr;
+  std::vector<std::pair<const ksim_handle*, int64_t>> sig;
+  for (auto* h : g.hs) sig.emplace_back(h, h->graph_gen);
+  if (sig != h0->sg_sig) {                     // another group, or some handle dropped its graphs
+    drop_group_graphs(h0);
+    h0->sg_sig = sig;
+  }
+  auto it = h0->sg_graphs.find(key);
+  if (it != h0->sg_graphs.end()) return it->second;
+  if (hipStreamSynchronize(g.stream) != hipSuccess) return nullptr;
+  hipGraphExec_t ge = nullptr;
+  const char* what;
+  const hipError_t e = capture_graph(g.stream, reps, body, &ge, what);
+  (void)hipGetLastError();
+  if (e != hipSuccess) {                       // e.g. a collective that cannot be captured
+    h0->sg_off = true;
+    h0->err.clear();
+    return nullptr;
+  }
+  h0->graph_captures++;
+  h0->sg_graphs.emplace(key, ge);
+  return ge;
+}
+
+// The start of every group run: the run's range on every member, streams idle.
+int group_begin(const Group& g, int32_t a, int32_t b) {
+  for (auto* h : g.hs) {
+    if (int rc = set_run(h, a, b)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return KSIM_OK;
+}
+
+// Pods [a, b) by stretches: enqueue(cursor) issues work that never passes the
+// run's end, then the leader's state tells how far it got.
+template <class E>
+int group_run(const Group& g, int32_t a, int32_t b, const char* stuck, E&& enqueue) {
+  if (int rc = group_begin(g, a, b)) return rc;
+  int32_t cursor = a;
+  while (cursor < b) {
+    if (int rc = enqueue(cursor)) return rc;
+    DevState st;
+    HIPCHK(g.h0, hipMemcpyAsync(&st, g.h0->st, sizeof(st), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(g.h0, hipStreamSynchronize(g.stream));
+    if (st.cursor <= cursor) return set_err(g.h0, KSIM_E_DEVICE, stuck);
+    cursor = st.cursor;
+  }
+  return KSIM_OK;
+}
+
+// group_run over batches that commit 1..kBatchPods pods each, so none is ever
+// issued past the run's end: whole graphs of kGraphBatches batches while at
+// least kBatchPods * kGraphBatches pods are left, then left / kBatchPods
+// single batches.
+template <class B>
+int group_run_batches(const Group& g, int32_t a, int32_t b, const GroupGraphKey& key, const char* stuck, B&& batch) {
+  hipGraphExec_t graph = nullptr;
+  return group_run(g, a, b, stuck, [&](int32_t cursor) {
+    const int32_t left = b - cursor;
+    if (cursor == a && left >= kBatchPods * kGraphBatches)   // the first stretch: set_run done
+      graph = group_graph(g, key, kGraphBatches, [&](int) { return batch(); });
+    if (graph && left >= kBatchPods * kGraphBatches) {
+      const int reps = left / (kBatchPods * kGraphBatches);
+      for (int r = 0; r < reps; r++) HIPCHK(g.h0, hipGraphLaunch(graph, g.stream));
+    } else {
+      const int32_t n = std::max(1, left / kBatchPods);
+      for (int32_t i = 0; i < n; i++)
+        if (int rc = batch()) return rc;
+    }
+    return (int)KSIM_OK;
+  });
+}
+
+// FAST keys for the run, on every shard of a group alike.
+bool group_fast(const Group& g, int32_t a, int32_t b) {
+  bool fast = run_fast(g.h0, a, b);
+  for (auto* h : g.hs) fast = fast && h->alloc_narrow;
+  return fast;
+}
+
+// Replicated handles hold every node: each evaluates its range (the only
+// handles whose evaluation range is narrowed; ADAPT replicas run whole and
+// never come here, so the ADAPT batch takes these arguments too).
 LaunchArgs shard_args(ksim_handle* h, bool fast) {
   LaunchArgs la = make_args(h, h->dp, h->d_chosen);
   la.fast = fast;
@@ -1530,49 +1673,29 @@ LaunchArgs shard_args(ksim_handle* h, bool fast) {
   return la;
 }
 
-int shard_batch(const std::vector<ksim_handle*>& hs, hipStream_t stream, bool fast) {
-  const int R = (int)hs.size();
-  ksim_handle* h0 = hs[0];
-  const size_t rec = (size_t)kBatchPods * kXRec;            // u64 per shard
-  for (auto* h : hs) launch_shard_eval(shard_args(h, fast), stream);
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(h0->sc.xsend, h0->sc.xrecv, rec, ncclUint64, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-  } else {
-    for (int src = 0; src < R; src++)
-      for (int dst = 0; dst < R; dst++)
-        HIPCHK(h0, hipMemcpyAsync(hs[dst]->sc.xrecv + (size_t)src * rec, hs[src]->sc.xsend, 8 * rec,
-                                  hipMemcpyDeviceToDevice, stream));
-  }
-  const int32_t world = h0->comm ? h0->world : R;
-  for (auto* h : hs) launch_shard_chain(shard_args(h, fast), world, stream);
-  if (h0->replicated) {
-    // every guess is local: the pair maxima are complete on every handle
-  } else if (h0->comm) {
-    const ncclResult_t r =
-        rccl().all_reduce(h0->sc.pmax, h0->sc.pmax, kBatchPods, ncclUint64, ncclMax, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllReduce: ") + rccl().error_string(r));
-  } else if (R > 1) {
-    GroupPtrs g{};
-    g.n = R;
-    for (int i = 0; i < R; i++) g.p[i] = hs[i]->sc.pmax;
-    launch_group_max(g, stream);
-  }
-  for (auto* h : hs) launch_shard_commit(shard_args(h, fast), stream);
-  HIPCHK(h0, hipGetLastError());
+// One batch on every shard of a group, phases separated by the two exchanges:
+// all-gather of the per-shard candidate records, all-reduce (max) of the pair
+// keys.  On replicated handles the pair keys and binds of every guess are
+// local, so the pair-key all-reduce is not needed (one exchange per batch).
+int shard_batch(const Group& g, bool fast) {
+  int rc;
+  for (auto* h : g.hs) launch_shard_eval(shard_args(h, fast), g.stream);
+  if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, (size_t)kBatchPods * kXRec))) return rc;
+  for (auto* h : g.hs) launch_shard_chain(shard_args(h, fast), g.world, g.stream);
+  if (!g.h0->replicated && (rc = group_all_reduce(g, sc_pmax, kBatchPods, true))) return rc;
+  for (auto* h : g.hs) launch_shard_commit(shard_args(h, fast), g.stream);
+  HIPCHK(g.h0, hipGetLastError());
   return KSIM_OK;
 }
-
-hipGraphExec_t shard_batch_graph(const std::vector<ksim_handle*>& hs, bool fast, bool adapt);
 
 // ---- replicated deferred-commit batches (ksim_internal.h) -----------------------
 // Replicated handles of a FAST P100 run: batch i is k_batch_top_commit over the
 // replica's node range (the commit of batch i-1 included, every replica binds
 // every placement), the records' all-gather, the global merge and the chain +
 // pairs: one exchange and three launches per batch instead of four.
-bool lazy_rep_ok(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b, bool fast) {
+bool lazy_rep_ok(const Group& g, int32_t a, int32_t b, bool fast) {
   if (!fast || !lazy_enabled()) return false;
-  for (auto* h : hs) {
+  for (auto* h : g.hs) {
     if (!h->replicated || h->dc.base != 0 || h->dc.n > kLazyMaxNodes || h->dc.n <= 0) return false;
     for (int32_t i = a; i < b; i++)
       if (!h->noadd[i]) return false;
@@ -1580,83 +1703,45 @@ bool lazy_rep_ok(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b, bool
   return true;
 }
 
-int shard_batch_lazy(const std::vector<ksim_handle*>& hs, hipStream_t stream, int64_t i) {
-  const int R = (int)hs.size();
-  ksim_handle* h0 = hs[0];
-  const size_t rec = (size_t)kBatchPods * kXRec;
-  for (auto* h : hs) launch_lazy_top_rep(lazy_batch(h, shard_args(h, true), i), h->sc.xsend, stream);
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(h0->sc.xsend, h0->sc.xrecv, rec, ncclUint64, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-  } else {
-    for (int src = 0; src < R; src++)
-      for (int dst = 0; dst < R; dst++)
-        HIPCHK(h0, hipMemcpyAsync(hs[dst]->sc.xrecv + (size_t)src * rec, hs[src]->sc.xsend, 8 * rec,
-                                  hipMemcpyDeviceToDevice, stream));
-  }
-  const int32_t world = h0->comm ? h0->world : R;
-  for (auto* h : hs) launch_lazy_chain_rep(lazy_batch(h, shard_args(h, true), i), world, stream);
-  HIPCHK(h0, hipGetLastError());
+int shard_batch_lazy(const Group& g, int64_t i) {
+  for (auto* h : g.hs) launch_lazy_top_rep(lazy_batch(h, shard_args(h, true), i), h->sc.xsend, g.stream);
+  if (int rc = group_all_gather(g, sc_xsend, sc_xrecv, (size_t)kBatchPods * kXRec)) return rc;
+  for (auto* h : g.hs) launch_lazy_chain_rep(lazy_batch(h, shard_args(h, true), i), g.world, g.stream);
+  HIPCHK(g.h0, hipGetLastError());
   return KSIM_OK;
 }
 
-hipGraphExec_t shard_lazy_graph(const std::vector<ksim_handle*>& hs) {
-  ksim_handle* h0 = hs[0];
-  if (h0->sg_off || ab(kAbShardGraph)) return nullptr;
-  std::vector<std::pair<const ksim_handle*, int64_t>> sig;
-  for (auto* h : hs) sig.emplace_back(h, h->graph_gen);
-  if (sig != h0->sg_sig) {
-    for (auto& kv : h0->sg_graphs) (void)hipGraphExecDestroy(kv.second);
-    h0->sg_graphs.clear();
-    h0->sg_sig = sig;
-  }
-  const auto key = std::make_tuple(true, (int64_t)-3, (int64_t)-1);
-  auto it = h0->sg_graphs.find(key);
-  if (it != h0->sg_graphs.end()) return it->second;
-  hipStream_t stream = h0->stream;
-  if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-  for (int i = 0; ok && i < kGraphBatches; i++) ok = shard_batch_lazy(hs, stream, i) == KSIM_OK;
-  const hipError_t e = hipStreamEndCapture(stream, &g);
-  ok = ok && e == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
-  if (g) (void)hipGraphDestroy(g);
-  (void)hipGetLastError();
-  if (!ok) {
-    h0->sg_off = true;
-    h0->err.clear();
-    return nullptr;
-  }
-  h0->graph_captures++;
-  h0->sg_graphs.emplace(key, ge);
-  return ge;
-}
-
-// set_run done on every handle.  As run_lazy, on the group's stream.
-int shard_run_lazy(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
-  ksim_handle* h0 = hs[0];
-  hipStream_t stream = h0->stream;
+// As run_lazy, on the group's stream.  The ring alignment of the graph and the
+// parity of the state read are this loop's own (not group_run's).
+int shard_run_lazy(const Group& g, int32_t a, int32_t b) {
+  ksim_handle* h0 = g.h0;
+  hipStream_t stream = g.stream;
   int rc;
-  for (auto* h : hs) {
+  if ((rc = group_begin(g, a, b))) return rc;
+  for (auto* h : g.hs) {
     if ((rc = lazy_begin(h))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
-  const hipGraphExec_t g = b - a >= kBatchPods * kGraphBatches ? shard_lazy_graph(hs) : nullptr;
+  GroupGraphKey key{};
+  key.kind = GroupGraphKind::kLazyBatch;
+  const hipGraphExec_t graph =
+      b - a >= kBatchPods * kGraphBatches
+          ? group_graph(g, key, kGraphBatches, [&](int i) { return shard_batch_lazy(g, i); })
+          : nullptr;
   int64_t i = 0;
   int32_t cursor = a;
   while (cursor < b) {
     int32_t nb = (b - cursor + kBatchPods - 1) / kBatchPods;
     const int32_t align = (int32_t)((kLazySlots - (i & 3)) & 3);
-    if (g && nb >= align + kGraphBatches) {
+    if (graph && nb >= align + kGraphBatches) {
       for (int32_t r = 0; r < align; r++, i++, nb--)
-        if ((rc = shard_batch_lazy(hs, stream, i))) return rc;
-      for (int32_t r = 0; r < nb / kGraphBatches; r++, i += kGraphBatches) HIPCHK(h0, hipGraphLaunch(g, stream));
+        if ((rc = shard_batch_lazy(g, i))) return rc;
+      for (int32_t r = 0; r < nb / kGraphBatches; r++, i += kGraphBatches) HIPCHK(h0, hipGraphLaunch(graph, stream));
     } else {
       for (int32_t r = 0; r < nb; r++, i++)
-        if ((rc = shard_batch_lazy(hs, stream, i))) return rc;
+        if ((rc = shard_batch_lazy(g, i))) return rc;
     }
-    for (auto* h : hs) launch_lazy_flush(lazy_batch(h, shard_args(h, true), i), stream);
+    for (auto* h : g.hs) launch_lazy_flush(lazy_batch(h, shard_args(h, true), i), stream);
     HIPCHK(h0, hipGetLastError());
     DevState st;
     HIPCHK(h0, hipMemcpyAsync(&st, (i & 1) ? h0->lazy_st1 : h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
@@ -1665,291 +1750,104 @@ int shard_run_lazy(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
     cursor = st.cursor;
     i++;
   }
-  for (auto* h : hs) {
+  for (auto* h : g.hs) {
     if ((rc = lazy_end(h, i - 1))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return KSIM_OK;
 }
 
-// Pods [a, b) on the sharded batch path (every pod must be batchable).  No
-// batch is ever issued past the run's end (each commits 1..kBatchPods pods):
-// whole graphs of kGraphBatches batches while at least kBatchPods *
-// kGraphBatches pods are left, then left / kBatchPods single batches.
-int shard_run(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
-  ksim_handle* h0 = hs[0];
-  hipStream_t stream = h0->stream;
-  bool fast = run_fast(h0, a, b);                      // every shard of an in-process group alike
-  for (auto* h : hs) fast = fast && h->alloc_narrow;
-  for (auto* h : hs) {
-    int rc;
-    if ((rc = set_run(h, a, b))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  if (lazy_rep_ok(hs, a, b, fast)) return shard_run_lazy(hs, a, b);
-  const hipGraphExec_t g = b - a >= kBatchPods * kGraphBatches ? shard_batch_graph(hs, fast, false) : nullptr;
-  int32_t cursor = a;
-  while (cursor < b) {
-    const int32_t left = b - cursor;
-    if (g && left >= kBatchPods * kGraphBatches) {
-      const int reps = left / (kBatchPods * kGraphBatches);
-      for (int r = 0; r < reps; r++) HIPCHK(h0, hipGraphLaunch(g, stream));
-    } else {
-      const int32_t n = std::max(1, left / kBatchPods);
-      for (int32_t i = 0; i < n; i++) {
-        int rc = shard_batch(hs, stream, fast);
-        if (rc) return rc;
-      }
-    }
-    DevState st;
-    HIPCHK(h0, hipMemcpyAsync(&st, h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
-    HIPCHK(h0, hipStreamSynchronize(stream));
-    if (st.cursor <= cursor) return set_err(h0, KSIM_E_DEVICE, "sharded batch path made no progress");
-    cursor = st.cursor;
-  }
-  return KSIM_OK;
+// Pods [a, b) on the sharded batch path (every pod must be batchable).
+int shard_run(const Group& g, int32_t a, int32_t b) {
+  const bool fast = group_fast(g, a, b);
+  if (lazy_rep_ok(g, a, b, fast)) return shard_run_lazy(g, a, b);
+  GroupGraphKey key{};
+  key.kind = GroupGraphKind::kBatch;
+  key.fast = fast;
+  return group_run_batches(g, a, b, key, "sharded batch path made no progress", [&] { return shard_batch(g, fast); });
 }
 
 // ---- replicated topology batches (ksim_tbatch.hip launch_tb_rep_*) -------------
-template <typename F>
-int x_allreduce(const std::vector<ksim_handle*>& hs, F&& ptr, int64_t count, bool op_max, hipStream_t stream);
-
-// All-gather of `bytes` per handle: src(h) -> dst(h) + rank * bytes.
-template <typename S, typename D>
-int x_allgather_bytes(const std::vector<ksim_handle*>& hs, S&& src, D&& dst, size_t bytes, hipStream_t stream) {
-  ksim_handle* h0 = hs[0];
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(src(h0), dst(h0), bytes, ncclUint8, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-    return KSIM_OK;
-  }
-  for (size_t a = 0; a < hs.size(); a++)
-    for (size_t b = 0; b < hs.size(); b++)
-      HIPCHK(h0, hipMemcpyAsync((char*)dst(hs[b]) + a * bytes, src(hs[a]), bytes, hipMemcpyDeviceToDevice, stream));
-  return KSIM_OK;
-}
-
 // One topology batch on every replica of a group: each evaluates its node
 // range; three exchanges (the filter's per-pod counters and extrema, the
 // per-pod top-T records with the extremum holder counts, the pair maxima and
 // pinv); every replica commits every placement.
-int shard_tbatch(const std::vector<ksim_handle*>& hs, hipStream_t stream) {
-  ksim_handle* h0 = hs[0];
-  const int32_t world = h0->comm ? h0->world : (int32_t)hs.size();
+int shard_tbatch(const Group& g) {
+  static_assert(sizeof(WinState) % 8 == 0, "the window states are exchanged in 8-byte words");
   int rc;
-  for (auto* h : hs) launch_tb_rep_filter(shard_args(h, false), stream);
-  if ((rc = x_allgather_bytes(hs, [](ksim_handle* h) { return (void*)h->sc.tb_win; },
-                              [](ksim_handle* h) { return (void*)h->sc.tb_xrecv; }, sizeof(WinState) * kTbPods, stream)))
+  for (auto* h : g.hs) launch_tb_rep_filter(shard_args(h, false), g.stream);
+  if ((rc = group_all_gather(g, [](ksim_handle* h) { return h->sc.tb_win; },
+                             [](ksim_handle* h) { return h->sc.tb_xrecv; }, sizeof(WinState) / 8 * kTbPods)))
     return rc;
-  for (auto* h : hs) launch_tb_rep_select(shard_args(h, false), world, stream);
-  if ((rc = x_allgather_bytes(hs, [](ksim_handle* h) { return (void*)h->sc.xsend; },
-                              [](ksim_handle* h) { return (void*)h->sc.xrecv; }, 8 * (size_t)kTbPods * kTbXRec,
-                              stream)))
-    return rc;
-  for (auto* h : hs) launch_tb_rep_pairs(shard_args(h, false), world, stream);
-  if ((rc = x_allreduce(hs, [](ksim_handle* h) { return h->sc.tb_pp; }, 2 * kTbPods, true, stream))) return rc;
-  for (auto* h : hs) launch_tb_rep_commit(shard_args(h, false), stream);
-  HIPCHK(h0, hipGetLastError());
+  for (auto* h : g.hs) launch_tb_rep_select(shard_args(h, false), g.world, g.stream);
+  if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, (size_t)kTbPods * kTbXRec))) return rc;
+  for (auto* h : g.hs) launch_tb_rep_pairs(shard_args(h, false), g.world, g.stream);
+  if ((rc = group_all_reduce(g, [](ksim_handle* h) { return h->sc.tb_pp; }, 2 * kTbPods, true))) return rc;
+  for (auto* h : g.hs) launch_tb_rep_commit(shard_args(h, false), g.stream);
+  HIPCHK(g.h0, hipGetLastError());
   return KSIM_OK;
 }
 
 // Topology batch pods [a, b) on the replicas of a group (as run_tbatch: the
 // batches the run lengths predict, then the state).
-int shard_run_tbatch(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
-  ksim_handle* h0 = hs[0];
-  hipStream_t stream = h0->stream;
-  int rc;
-  for (auto* h : hs) {
-    if ((rc = set_run(h, a, b))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->sc.tb_win, 0, sizeof(WinState) * kTbPods, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  int32_t cursor = a;
-  while (cursor < b) {
+int shard_run_tbatch(const Group& g, int32_t a, int32_t b) {
+  for (auto* h : g.hs) HIPCHK(h, hipMemsetAsync(h->sc.tb_win, 0, sizeof(WinState) * kTbPods, h->stream));
+  return group_run(g, a, b, "replicated topology batches made no progress", [&](int32_t cursor) {
     int32_t nbat = 0;
-    for (int32_t i = cursor; i < b; nbat++) i += std::min(std::min(kTbPods, b - i), std::max(h0->tlen_plain[i], 1));
+    for (int32_t i = cursor; i < b; nbat++) i += std::min(std::min(kTbPods, b - i), std::max(g.h0->tlen_plain[i], 1));
     for (int32_t i = 0; i < nbat; i++)
-      if ((rc = shard_tbatch(hs, stream))) return rc;
-    DevState st;
-    HIPCHK(h0, hipMemcpyAsync(&st, h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
-    HIPCHK(h0, hipStreamSynchronize(stream));
-    if (st.cursor <= cursor) return set_err(h0, KSIM_E_DEVICE, "replicated topology batches made no progress");
-    cursor = st.cursor;
-  }
-  return KSIM_OK;
+      if (int rc = shard_tbatch(g)) return rc;
+    return (int)KSIM_OK;
+  });
 }
 
 // ---- node-sharded per-pod cycle (C1 extrema, C2 argmax, C3 window) ----
-// Element-wise all-reduce of a per-handle device buffer of `count` 8-byte words:
-// sum (int64) or max (uint64).  RCCL across processes, a group kernel in-process.
-template <typename F>
-int x_allreduce(const std::vector<ksim_handle*>& hs, F&& ptr, int64_t count, bool op_max, hipStream_t stream) {
-  if (count <= 0) return KSIM_OK;
-  ksim_handle* h0 = hs[0];
-  if (h0->comm) {
-    void* b = (void*)ptr(h0);
-    const ncclResult_t r = rccl().all_reduce(b, b, (size_t)count, op_max ? ncclUint64 : ncclInt64,
-                                             op_max ? ncclMax : ncclSum, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllReduce: ") + rccl().error_string(r));
-  } else if (hs.size() > 1) {
-    GroupPtrs g{};
-    g.n = (int32_t)hs.size();
-    for (size_t i = 0; i < hs.size(); i++) g.p[i] = (uint64_t*)ptr(hs[i]);
-    launch_group_reduce(g, count, op_max, stream);
-  }
-  return KSIM_OK;
-}
-
-// All-gather of two words per shard: s.xsend[0..1] -> s.xrecv[world][2].
-int x_allgather2(const std::vector<ksim_handle*>& hs, hipStream_t stream) {
-  ksim_handle* h0 = hs[0];
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(h0->sc.xsend, h0->sc.xrecv, 2, ncclUint64, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-    return KSIM_OK;
-  }
-  GroupPtrs src{}, dst{};
-  src.n = dst.n = (int32_t)hs.size();
-  for (size_t i = 0; i < hs.size(); i++) {
-    src.p[i] = hs[i]->sc.xsend;
-    dst.p[i] = hs[i]->sc.xrecv;
-  }
-  launch_group_gather(src, dst, 2, stream);
-  return KSIM_OK;
-}
-
 // One per-pod cycle (the pod at the shards' common cursor) across node shards,
 // with exchanges of xdom / xreg words (at least the pod's own lengths: words
-// past them are summed but never read).
-int shard_cycle(const std::vector<ksim_handle*>& hs, bool topo, int64_t xdom, int64_t xreg, hipStream_t stream) {
-  ksim_handle* h0 = hs[0];
-  const int R = (int)hs.size();
-  const int32_t world = h0->comm ? h0->world : R;
+// past them are summed but never read).  The two-word all-gathers:
+// s.xsend[0..1] -> s.xrecv[world][2].
+int shard_cycle(const Group& g, bool topo, int64_t xdom, int64_t xreg) {
+  hipStream_t stream = g.stream;
   int rc;
   if (topo) {
-    for (auto* h : hs) launch_pshard_topo(make_args(h, h->dp, h->d_chosen), stream);
-    if ((rc = x_allreduce(hs, [](ksim_handle* h) { return h->sc.xdom; }, xdom, false, stream))) return rc;
+    for (auto* h : g.hs) launch_pshard_topo(make_args(h, h->dp, h->d_chosen), stream);
+    if ((rc = group_all_reduce(g, [](ksim_handle* h) { return h->sc.xdom; }, xdom, false))) return rc;
   }
-  for (auto* h : hs) launch_pshard_filter(make_args(h, h->dp, h->d_chosen), topo, stream);
-  if ((rc = x_allgather2(hs, stream))) return rc;      // C3: feasible counts per shard
-  for (int i = 0; i < R; i++)
-    launch_pshard_window(make_args(hs[i], hs[i]->dp, hs[i]->d_chosen), h0->comm ? h0->rank : i, world, stream);
-  if ((rc = x_allreduce(hs, [](ksim_handle* h) { return h->sc.xreg; }, xreg, false, stream))) return rc;
-  for (auto* h : hs) launch_pshard_extrema(make_args(h, h->dp, h->d_chosen), xreg > 0, stream);
-  if ((rc = x_allreduce(hs, [](ksim_handle* h) { return h->sc.win->ext; }, kExtWords, true, stream))) return rc;
-  for (auto* h : hs) launch_pshard_select(make_args(h, h->dp, h->d_chosen), stream);
-  if ((rc = x_allgather2(hs, stream))) return rc;      // C2: every shard's (total, TB) best
-  for (auto* h : hs) launch_pshard_bind(make_args(h, h->dp, h->d_chosen), world, stream);
-  HIPCHK(h0, hipGetLastError());
+  for (auto* h : g.hs) launch_pshard_filter(make_args(h, h->dp, h->d_chosen), topo, stream);
+  if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, 2))) return rc;      // C3: feasible counts per shard
+  for (size_t i = 0; i < g.hs.size(); i++)
+    launch_pshard_window(make_args(g.hs[i], g.hs[i]->dp, g.hs[i]->d_chosen), g.rank(i), g.world, stream);
+  if ((rc = group_all_reduce(g, [](ksim_handle* h) { return h->sc.xreg; }, xreg, false))) return rc;
+  for (auto* h : g.hs) launch_pshard_extrema(make_args(h, h->dp, h->d_chosen), xreg > 0, stream);
+  if ((rc = group_all_reduce(g, [](ksim_handle* h) { return h->sc.win->ext; }, kExtWords, true))) return rc;
+  for (auto* h : g.hs) launch_pshard_select(make_args(h, h->dp, h->d_chosen), stream);
+  if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, 2))) return rc;      // C2: every shard's (total, TB) best
+  for (auto* h : g.hs) launch_pshard_bind(make_args(h, h->dp, h->d_chosen), g.world, stream);
+  HIPCHK(g.h0, hipGetLastError());
   return KSIM_OK;
-}
-
-int shard_cycle(const std::vector<ksim_handle*>& hs, int32_t pod, hipStream_t stream) {
-  const ksim_handle* h0 = hs[0];
-  return shard_cycle(hs, h0->topo[pod] != 0, h0->xdom_len[pod], h0->xreg_len[pod], stream);
-}
-
-// kGraphCycles sharded cycles of one shape as a graph on the leader (its
-// stream carries every shard's kernels and the collectives), or nullptr when
-// capture is off or fails (the caller runs the cycles eagerly).
-hipGraphExec_t shard_graph(const std::vector<ksim_handle*>& hs, bool topo, int64_t xdom, int64_t xreg) {
-  ksim_handle* h0 = hs[0];
-  if (h0->sg_off || ab(kAbShardGraph)) return nullptr;
-  std::vector<std::pair<const ksim_handle*, int64_t>> sig;
-  for (auto* h : hs) sig.emplace_back(h, h->graph_gen);
-  if (sig != h0->sg_sig) {                     // another group, or some handle dropped its graphs
-    for (auto& kv : h0->sg_graphs) (void)hipGraphExecDestroy(kv.second);
-    h0->sg_graphs.clear();
-    h0->sg_sig = sig;
-  }
-  const auto key = std::make_tuple(topo, xdom, xreg);
-  auto it = h0->sg_graphs.find(key);
-  if (it != h0->sg_graphs.end()) return it->second;
-  hipStream_t stream = h0->stream;
-  if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-  for (int i = 0; ok && i < kGraphCycles; i++) ok = shard_cycle(hs, topo, xdom, xreg, stream) == KSIM_OK;
-  const hipError_t e = hipStreamEndCapture(stream, &g);   // ends a capture even after a failed launch
-  ok = ok && e == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
-  if (g) (void)hipGraphDestroy(g);
-  (void)hipGetLastError();
-  if (!ok) {
-    h0->sg_off = true;
-    h0->err.clear();
-    return nullptr;
-  }
-  h0->graph_captures++;
-  h0->sg_graphs.emplace(key, ge);
-  return ge;
-}
-
-// kGraphBatches sharded batches (every shard's kernels and the exchanges on
-// the leader's stream, RCCL collectives included) as a graph, cached with the
-// per-pod shard graphs; nullptr when capture is off or fails (eager batches).
-int shard_batch_adapt(const std::vector<ksim_handle*>& hs, hipStream_t stream, bool fast);
-
-hipGraphExec_t shard_batch_graph(const std::vector<ksim_handle*>& hs, bool fast, bool adapt) {
-  ksim_handle* h0 = hs[0];
-  if (h0->sg_off || ab(kAbShardGraph)) return nullptr;
-  std::vector<std::pair<const ksim_handle*, int64_t>> sig;
-  for (auto* h : hs) sig.emplace_back(h, h->graph_gen);
-  if (sig != h0->sg_sig) {
-    for (auto& kv : h0->sg_graphs) (void)hipGraphExecDestroy(kv.second);
-    h0->sg_graphs.clear();
-    h0->sg_sig = sig;
-  }
-  const auto key = std::make_tuple(fast, (int64_t)(adapt ? -2 : -1), (int64_t)-1);   // per-pod keys: lengths >= 0
-  auto it = h0->sg_graphs.find(key);
-  if (it != h0->sg_graphs.end()) return it->second;
-  hipStream_t stream = h0->stream;
-  if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-  for (int i = 0; ok && i < kGraphBatches; i++)
-    ok = (adapt ? shard_batch_adapt(hs, stream, fast) : shard_batch(hs, stream, fast)) == KSIM_OK;
-  const hipError_t e = hipStreamEndCapture(stream, &g);
-  ok = ok && e == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
-  if (g) (void)hipGraphDestroy(g);
-  (void)hipGetLastError();
-  if (!ok) {
-    h0->sg_off = true;
-    h0->err.clear();
-    return nullptr;
-  }
-  h0->graph_captures++;
-  h0->sg_graphs.emplace(key, ge);
-  return ge;
 }
 
 // Pods [a, b) on the sharded per-pod path, one cycle each: whole graphs of
 // kGraphCycles cycles shaped for the run's largest exchanges, then single
 // cycles for the rest.
-int shard_run_perpod(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
-  ksim_handle* h0 = hs[0];
-  hipStream_t stream = h0->stream;
-  for (auto* h : hs) {
-    int rc;
-    if ((rc = set_run(h, a, b))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+int shard_run_perpod(const Group& g, int32_t a, int32_t b) {
+  const ksim_handle* h0 = g.h0;
+  if (int rc = group_begin(g, a, b)) return rc;
   int32_t i = a;
   if (b - a >= kGraphCycles) {
-    const bool topo = h0->topo[a] != 0;          // runs are uniform in topo (for_each_run)
-    int64_t xdom = 0, xreg = 0;
+    GroupGraphKey key{};
+    key.kind = GroupGraphKind::kPerPod;
+    key.topo = h0->topo[a] != 0;                 // runs are uniform in topo (for_each_run)
     for (int32_t k = a; k < b; k++) {
-      xdom = std::max(xdom, h0->xdom_len[k]);
-      xreg = std::max(xreg, h0->xreg_len[k]);
+      key.xdom = std::max(key.xdom, h0->xdom_len[k]);
+      key.xreg = std::max(key.xreg, h0->xreg_len[k]);
     }
-    if (hipGraphExec_t g = shard_graph(hs, topo, xdom, xreg))
-      for (; i + kGraphCycles <= b; i += kGraphCycles) HIPCHK(h0, hipGraphLaunch(g, stream));
+    if (hipGraphExec_t graph = group_graph(g, key, kGraphCycles,
+                                           [&](int) { return shard_cycle(g, key.topo, key.xdom, key.xreg); }))
+      for (; i + kGraphCycles <= b; i += kGraphCycles) HIPCHK(g.h0, hipGraphLaunch(graph, g.stream));
   }
-  for (; i < b; i++) {
-    int rc = shard_cycle(hs, i, stream);
-    if (rc) return rc;
-  }
+  for (; i < b; i++)
+    if (int rc = shard_cycle(g, h0->topo[i] != 0, h0->xdom_len[i], h0->xreg_len[i])) return rc;
   return KSIM_OK;
 }
 
@@ -1962,15 +1860,12 @@ int32_t adapt_shard_chunk(int32_t n_total, int32_t world) {
   return (q + 63) / 64 * 64;
 }
 
-bool adapt_shard_layout(const std::vector<ksim_handle*>& hs) {
-  const ksim_handle* h0 = hs[0];
-  const int32_t world = h0->comm ? h0->world : (int32_t)hs.size();
-  const int32_t N = h0->dc.n_total, chunk = adapt_shard_chunk(N, world);
-  if ((int64_t)(world - 1) * chunk >= N) return false;
-  for (size_t i = 0; i < hs.size(); i++) {
-    const int32_t r = h0->comm ? h0->rank : (int32_t)i;
-    const int32_t base = r * chunk, n = std::min(chunk, N - base);
-    if (hs[i]->dc.base != base || hs[i]->dc.n != n) return false;
+bool adapt_shard_layout(const Group& g) {
+  const int32_t N = g.h0->dc.n_total, chunk = adapt_shard_chunk(N, g.world);
+  if ((int64_t)(g.world - 1) * chunk >= N) return false;
+  for (size_t i = 0; i < g.hs.size(); i++) {
+    const int32_t base = g.rank(i) * chunk, n = std::min(chunk, N - base);
+    if (g.hs[i]->dc.base != base || g.hs[i]->dc.n != n) return false;
   }
   return true;
 }
@@ -1991,94 +1886,47 @@ int adapt_shard_buffers(ksim_handle* h, int32_t world, int32_t W) {
   return KSIM_OK;
 }
 
-// One ADAPT batch on every shard of a group (exchanges: bitmaps, records, M).
-int shard_batch_adapt(const std::vector<ksim_handle*>& hs, hipStream_t stream, bool fast) {
-  auto args = [&](ksim_handle* h) {
-    LaunchArgs la = make_args(h, h->dp, h->d_chosen);
-    la.fast = fast;
-    return la;
-  };
-  const int R = (int)hs.size();
-  ksim_handle* h0 = hs[0];
-  const int32_t world = h0->comm ? h0->world : R;
-  const int32_t W = adapt_shard_chunk(h0->dc.n_total, world) / 64;
-  const size_t mw = (size_t)kBatchPods * W;                   // bitmap words per shard
-  for (auto* h : hs) launch_adapt_sh_mask(args(h), h->ash_send, W, stream);
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(h0->ash_send, h0->ash_recv, mw, ncclUint64, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-  } else {
-    for (int src = 0; src < R; src++)
-      for (int dst = 0; dst < R; dst++)
-        HIPCHK(h0, hipMemcpyAsync(hs[dst]->ash_recv + (size_t)src * mw, hs[src]->ash_send, 8 * mw,
-                                  hipMemcpyDeviceToDevice, stream));
-  }
-  for (auto* h : hs) launch_adapt_sh_window(args(h), h->ash_recv, W, h->ash_gmask, stream);
-  const size_t rec = (size_t)kBatchPods * kXRec;
-  if (h0->comm) {
-    const ncclResult_t r = rccl().all_gather(h0->sc.xsend, h0->sc.xrecv, rec, ncclUint64, h0->comm, stream);
-    if (r != ncclSuccess) return set_err(h0, KSIM_E_RCCL, std::string("ncclAllGather: ") + rccl().error_string(r));
-  } else {
-    for (int src = 0; src < R; src++)
-      for (int dst = 0; dst < R; dst++)
-        HIPCHK(h0, hipMemcpyAsync(hs[dst]->sc.xrecv + (size_t)src * rec, hs[src]->sc.xsend, 8 * rec,
-                                  hipMemcpyDeviceToDevice, stream));
-  }
-  for (auto* h : hs) launch_adapt_sh_pairs(args(h), h->ash_gmask, world, stream);
+// One ADAPT batch on every shard of a group (exchanges: bitmaps of W words per
+// pod, records, M).
+int shard_batch_adapt(const Group& g, int32_t W, bool fast) {
   int rc;
-  if ((rc = x_allreduce(hs, [](ksim_handle* h) { return h->sc.pmax; }, 2 * kBatchPods, true, stream))) return rc;
-  for (auto* h : hs) launch_adapt_sh_commit(args(h), stream);
-  HIPCHK(h0, hipGetLastError());
+  for (auto* h : g.hs) launch_adapt_sh_mask(shard_args(h, fast), h->ash_send, W, g.stream);
+  if ((rc = group_all_gather(g, [](ksim_handle* h) { return h->ash_send; },
+                             [](ksim_handle* h) { return h->ash_recv; }, (size_t)kBatchPods * W)))
+    return rc;
+  for (auto* h : g.hs) launch_adapt_sh_window(shard_args(h, fast), h->ash_recv, W, h->ash_gmask, g.stream);
+  if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, (size_t)kBatchPods * kXRec))) return rc;
+  for (auto* h : g.hs) launch_adapt_sh_pairs(shard_args(h, fast), h->ash_gmask, g.world, g.stream);
+  if ((rc = group_all_reduce(g, sc_pmax, 2 * kBatchPods, true))) return rc;
+  for (auto* h : g.hs) launch_adapt_sh_commit(shard_args(h, fast), g.stream);
+  HIPCHK(g.h0, hipGetLastError());
   return KSIM_OK;
 }
 
 // Pods [a, b) on the sharded ADAPT batch path.
-int shard_run_adapt(const std::vector<ksim_handle*>& hs, int32_t a, int32_t b) {
-  ksim_handle* h0 = hs[0];
-  hipStream_t stream = h0->stream;
-  const int32_t world = h0->comm ? h0->world : (int32_t)hs.size();
-  const int32_t W = adapt_shard_chunk(h0->dc.n_total, world) / 64;
-  bool fast = run_fast(h0, a, b);                      // every shard alike
-  for (auto* h : hs) fast = fast && h->alloc_narrow;
-  for (auto* h : hs) {
-    int rc;
-    if ((rc = adapt_shard_buffers(h, world, W))) return rc;
-    if ((rc = set_run(h, a, b))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  const hipGraphExec_t g = b - a >= kBatchPods * kGraphBatches ? shard_batch_graph(hs, fast, true) : nullptr;
-  int32_t cursor = a;
-  while (cursor < b) {
-    const int32_t left = b - cursor;
-    if (g && left >= kBatchPods * kGraphBatches) {   // as shard_run
-      const int reps = left / (kBatchPods * kGraphBatches);
-      for (int r = 0; r < reps; r++) HIPCHK(h0, hipGraphLaunch(g, stream));
-    } else {
-      const int32_t n = std::max(1, left / kBatchPods);
-      for (int32_t i = 0; i < n; i++) {
-        int rc = shard_batch_adapt(hs, stream, fast);
-        if (rc) return rc;
-      }
-    }
-    DevState st;
-    HIPCHK(h0, hipMemcpyAsync(&st, h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
-    HIPCHK(h0, hipStreamSynchronize(stream));
-    if (st.cursor <= cursor) return set_err(h0, KSIM_E_DEVICE, "sharded ADAPT batch path made no progress");
-    cursor = st.cursor;
-  }
-  return KSIM_OK;
+int shard_run_adapt(const Group& g, int32_t a, int32_t b) {
+  const int32_t W = adapt_shard_chunk(g.h0->dc.n_total, g.world) / 64;
+  const bool fast = group_fast(g, a, b);
+  for (auto* h : g.hs)
+    if (int rc = adapt_shard_buffers(h, g.world, W)) return rc;
+  GroupGraphKey key{};
+  key.kind = GroupGraphKind::kAdaptBatch;
+  key.fast = fast;
+  return group_run_batches(g, a, b, key, "sharded ADAPT batch path made no progress",
+                           [&] { return shard_batch_adapt(g, W, fast); });
 }
 
 // A sharded run: batchable stretches on the batch protocol, the rest cycle by cycle.
 int shard_schedule(const std::vector<ksim_handle*>& hs, int32_t first, int32_t count) {
-  if (profile_nb(hs[0]->prof))
-    return set_err(hs[0], KSIM_E_UNSUPPORTED, "NetworkBandwidth profiles run on unsharded handles");
-  if (hs[0]->replicated) {
+  const Group g(hs);
+  if (profile_nb(g.h0->prof))
+    return set_err(g.h0, KSIM_E_UNSUPPORTED, "NetworkBandwidth profiles run on unsharded handles");
+  const bool adapt = adapt_mode(g.h0);
+  if (g.h0->replicated) {
     // P100 batch stretches on the replicated exchange; everything else runs
     // whole on every replica (the same cycles, so the replicas stay equal)
-    const bool adapt = adapt_mode(hs[0]);
-    return for_each_run(hs[0], first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
-      if (batch && !adapt) return topo ? shard_run_tbatch(hs, a, b) : shard_run(hs, a, b);
+    return for_each_run(g.h0, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
+      if (batch && !adapt) return topo ? shard_run_tbatch(g, a, b) : shard_run(g, a, b);
       for (auto* h : hs) {
         int rc = run_range(h, a, b, batch, topo);
         if (rc) return rc;
@@ -2086,11 +1934,10 @@ int shard_schedule(const std::vector<ksim_handle*>& hs, int32_t first, int32_t c
       return (int)KSIM_OK;
     }, true);
   }
-  const bool adapt = adapt_mode(hs[0]);
-  const bool adapt_batch = adapt && adapt_shard_layout(hs);
-  return for_each_run(hs[0], first, count, [&](int32_t a, int32_t b, bool batch, bool) {
-    if (!batch) return shard_run_perpod(hs, a, b);
-    return adapt ? shard_run_adapt(hs, a, b) : shard_run(hs, a, b);
+  const bool adapt_batch = adapt && adapt_shard_layout(g);
+  return for_each_run(g.h0, first, count, [&](int32_t a, int32_t b, bool batch, bool) {
+    if (!batch) return shard_run_perpod(g, a, b);
+    return adapt ? shard_run_adapt(g, a, b) : shard_run(g, a, b);
   }, adapt_batch);
 }
 

@@ -44,6 +44,24 @@ struct PodBlob {
   int32_t n_nn, n_exprs, n_terms, n_uses, n_adds;
 };
 
+// What a shard-group graph holds (ksim_engine.cpp group_graph): its protocol
+// and the launch arguments that protocol bakes into the graph.
+enum class GroupGraphKind : int32_t {
+  kPerPod,       // kGraphCycles per-pod cycles: topo, xdom, xreg (the exchange lengths)
+  kBatch,        // kGraphBatches P100 batches: fast
+  kAdaptBatch,   // kGraphBatches ADAPT batches: fast
+  kLazyBatch,    // kGraphBatches replicated deferred-commit batches
+};
+
+struct GroupGraphKey {
+  GroupGraphKind kind = GroupGraphKind::kPerPod;
+  bool topo = false, fast = false;
+  int64_t xdom = 0, xreg = 0;
+  bool operator<(const GroupGraphKey& o) const {
+    return std::tie(kind, topo, fast, xdom, xreg) < std::tie(o.kind, o.topo, o.fast, o.xdom, o.xreg);
+  }
+};
+
 struct ksim_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -342,13 +360,13 @@ struct ksim_handle {
   // last run's start): the setting the handle's deferred-commit graphs hold
   bool one_cut = false;
   int64_t graph_captures = 0;                  // graphs captured since ksim_create (ksim_get_diag)
-  // node-sharded per-pod cycles (group leader): graphs of kGraphCycles cycles
-  // per shape (topology, exchange lengths), valid while every handle of the
-  // group keeps the graph generation it had at capture
+  // shard-group graphs (group leader; ksim_engine.cpp group_graph): one graph
+  // per GroupGraphKey, valid while the group is the handles of sg_sig, each at
+  // the graph generation it had at capture; drop_group_graphs destroys them
   int64_t graph_gen = 0;                       // bumped whenever this handle's cycle graphs are dropped
   std::vector<std::pair<const ksim_handle*, int64_t>> sg_sig;
-  std::map<std::tuple<bool, int64_t, int64_t>, hipGraphExec_t> sg_graphs;
-  bool sg_off = false;                         // capture failed once (e.g. a collective that cannot be captured)
+  std::map<GroupGraphKey, hipGraphExec_t> sg_graphs;
+  bool sg_off = false;                         // group_graph failed once (e.g. a collective that cannot be captured)
   int64_t match_ns = 0;                        // device time of the last ksim_match_terms (HIP events)
 };
 

@@ -477,7 +477,6 @@ void launch_adapt_sh_pairs(const LaunchArgs& a, const uint64_t* gmask, int32_t w
 void launch_adapt_sh_commit(const LaunchArgs& a, hipStream_t stream);
 void launch_shard_chain(const LaunchArgs& a, int32_t world, hipStream_t stream);
 void launch_shard_commit(const LaunchArgs& a, hipStream_t stream);
-void launch_group_max(const GroupPtrs& g, hipStream_t stream);
 // Sharded per-pod cycle (node shards; the caller exchanges between the phases,
 // see ksim_kernels.hip §C):
 //   launch_pshard_topo     prefilter + pack           (all-reduce sum s.xdom)

@@ -1782,7 +1782,10 @@ void launch_group_reduce(const GroupPtrs& g, int64_t count, bool op_max, hipStre
 }
 
 void launch_group_gather(const GroupPtrs& src, const GroupPtrs& dst, int32_t words, hipStream_t stream) {
-  k_group_gather<<<1, 256, 0, stream>>>(src, dst, words);
+  const int64_t total = (int64_t)src.n * src.n * words;   // at most 2^30 (group_all_gather checks)
+  if (total <= 0) return;
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
+  k_group_gather<<<blocks, 256, 0, stream>>>(src, dst, words);
 }
 
 }  // namespace ksim

@@ -362,3 +362,91 @@ def test_rccl_world1_replicated_config3():
     ochosen, ost = Oracle(cluster, prof).schedule(pods, nthreads=8)
     np.testing.assert_array_equal(chosen, ochosen)
     assert st.perpod_cycles == 0 and st.batches < pods.n_pods
+
+
+# ---- the shard-group graph cache: one entry per kind, kept across calls, dropped with a generation ----
+
+def _scene_batch():
+    cluster, pods = gen.config2(n_nodes=200, n_pods=4352)      # 17 x 256 pods: one graph of 16 batches + a tail
+    prof = _prof()
+    return cluster, pods, prof, _group(cluster, pods, prof, 2)
+
+
+def _scene_adapt_batch():
+    cluster, pods = gen.config2(n_nodes=2000, n_pods=4352)
+    prof = _adapt_prof()
+    assert partition(2000, 2)[1][0] % 64 == 0                   # the aligned layout (test_group_adapt_batch)
+    return cluster, pods, prof, _group(cluster, pods, prof, 2)
+
+
+def _scene_perpod():
+    # test_group_perpod_config1's scene: two PreferNoSchedule taints on the
+    # cluster and at most one toleration per pod, so every pod's normalized
+    # scores vary and every pod takes the per-pod cycle: 128 pods, one graph
+    cluster, pods = gen.config1(n_pods=128)
+    prof = _prof_pct(0)
+    return cluster, pods, prof, _group(cluster, pods, prof, 2)
+
+
+def _scene_replicated():
+    cluster, pods = gen.config2(n_nodes=1031, n_pods=4352)     # a ragged split (test_group_replicated)
+    prof = _prof()
+    return cluster, pods, prof, _replicas(cluster, pods, prof, 3)
+
+
+def _captures(engines):
+    return [e.diag()["graph_captures"] for e in engines]
+
+
+def _rerun(engines, count):
+    for e in engines:
+        e.reset_cluster()
+    return group_schedule_loaded(engines, 0, count)[0]
+
+
+@pytest.mark.parametrize("scene", [_scene_batch, _scene_adapt_batch, _scene_perpod, _scene_replicated],
+                         ids=["batch", "adapt_batch", "perpod", "replicated_deferred"])
+def test_group_graph_cache(scene):
+    """The leader's graphs are captured once, replayed by a second call, and
+    captured again (as many) after any member's graph generation moved."""
+    cluster, pods, prof, engines = scene()
+    g0 = _captures(engines)
+    chosen, _ = group_schedule_loaded(engines, 0, pods.n_pods)
+    np.testing.assert_array_equal(chosen, Oracle(cluster, prof).schedule(pods, nthreads=8)[0])
+    g1 = _captures(engines)
+    c1 = g1[0] - g0[0]
+    print(f"{scene.__name__}: captures on the first call {c1}")
+    assert c1 >= 1
+    np.testing.assert_array_equal(_rerun(engines, pods.n_pods), chosen)
+    assert _captures(engines) == g1
+    engines[-1].set_profile(prof)          # the same profile: the member's cycle graphs go, its generation moves
+    engines[-1].load_pods(pods)            # (a profile unloads the queue)
+    np.testing.assert_array_equal(_rerun(engines, pods.n_pods), chosen)
+    assert _captures(engines)[0] == g1[0] + c1
+
+
+def test_group_graph_cache_two_kinds():
+    """A queue whose first stretch is per-pod and whose second is batch: both
+    graphs stay in the leader's cache, a second call captures nothing."""
+    from ksim.encode import encode_cluster, encode_pods
+    from ksim.model import NodeSelectorTerm, PreferredTerm, Requirement
+    nodes, objs = gen.config1_objects(n_nodes=200, n_pods=128 + 4352)
+    for n in nodes:
+        n.taints = []
+    for j, p in enumerate(objs):
+        p.tolerations, p.required_terms = [], None
+        # preferred node affinity: normalized scores that vary, the per-pod cycle on node shards
+        p.preferred_terms = [PreferredTerm(10, NodeSelectorTerm([Requirement("disk", "In", ["ssd"])]))] if j < 128 else []
+    cluster, _ = encode_cluster(nodes)
+    pods = encode_pods(cluster, objs)
+    prof = _prof()
+    engines = _group(cluster, pods, prof, 2)
+    g0 = _captures(engines)
+    chosen, st = group_schedule_loaded(engines, 0, pods.n_pods)
+    np.testing.assert_array_equal(chosen, Oracle(cluster, prof).schedule(pods, nthreads=8)[0])
+    g1 = _captures(engines)
+    print(f"two kinds: captures on the first call {g1[0] - g0[0]}")
+    # one graph of 128 cycles and one of 16 batches (a queue of one kind captures one: test_group_graph_cache)
+    assert st.batches > 0 and g1[0] - g0[0] >= 2
+    np.testing.assert_array_equal(_rerun(engines, pods.n_pods), chosen)
+    assert _captures(engines) == g1
