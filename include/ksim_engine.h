@@ -746,7 +746,8 @@ int ksim_comm_unique_id(uint8_t* id /* [KSIM_COMM_ID_BYTES] */);
 int ksim_comm_init(ksim_handle* h, int32_t rank, int32_t world, const uint8_t* id);
 /* An in-process group of shard handles on one device (exchanges by device
  * copies): the same protocol without a communicator.  hs[i] must tile the
- * cluster in order; chosen / stats as ksim_schedule_loaded (evals summed). */
+ * cluster in order; chosen / stats as ksim_schedule_loaded (evals summed;
+ * perpod_cycles counts the pods the group's runs took off the batch path). */
 int ksim_group_schedule_loaded(ksim_handle** hs, int32_t n, int32_t first, int32_t count,
                                int32_t* chosen, ksim_batch_stats* stats);
 

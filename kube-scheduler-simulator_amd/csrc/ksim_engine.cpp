@@ -3845,6 +3845,8 @@ int ksim_group_schedule_loaded(ksim_handle** hs, int32_t n, int32_t first, int32
     HIPCHK(h0, hipEventElapsedTime(&ms, h0->ev0, h0->ev1));
     stats->pods = count;
     stats->device_ms = ms;
+    // as ksim_schedule_loaded on a sharded handle: the pods the group's runs took off the batch path
+    for (int32_t i = first; i < first + count; i++) stats->perpod_cycles += pod_on_batch(h0, i) ? 0 : 1;
   }
   return KSIM_OK;
 }
