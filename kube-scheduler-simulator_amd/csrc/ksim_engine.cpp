@@ -127,27 +127,23 @@ void drop_group_graphs(ksim_handle* h) {
   h->sg_graphs.clear();
 }
 
-// The per-pod cycle graphs (their kernels take the profile by value).
+// The handle's own graphs whose key `pred` picks (ksim_host.h GraphKey): the
+// one place that destroys them, whatever the scope.
+template <class P>
+void drop_graphs_if(ksim_handle* h, P&& pred) {
+  for (auto it = h->graphs.begin(); it != h->graphs.end();)
+    it = pred(it->first) ? ((void)hipGraphExecDestroy(it->second), h->graphs.erase(it)) : std::next(it);
+}
+
+constexpr auto is_lazy = [](const GraphKey& k) { return k.kind == GraphKind::kLazy; };
+constexpr auto is_table = [](const GraphKey& k) { return k.kind == GraphKind::kLazy && k.arg[1] > 0; };
+
+// The per-pod cycle graphs (their kernels take the profile by value), and the
+// group graphs, which hold the same cycles.
 void drop_cycle_graphs(ksim_handle* h) {
-  for (auto& g : h->graph_cycle) {
-    if (g) (void)hipGraphExecDestroy(g);
-    g = nullptr;
-  }
+  drop_graphs_if(h, [](const GraphKey& k) { return k.kind == GraphKind::kCycle; });
   drop_group_graphs(h);
   h->graph_gen++;
-}
-
-// A deferred-commit graph with its tail graph.
-void drop_lazy_pair(hipGraphExec_t& g, hipGraphExec_t& g4) {
-  if (g) (void)hipGraphExecDestroy(g);
-  if (g4) (void)hipGraphExecDestroy(g4);
-  g = g4 = nullptr;
-}
-
-void drop_lazy_graphs(ksim_handle* h) {
-  drop_lazy_pair(h->graph_lazy, h->graph_lazy4);
-  drop_lazy_pair(h->graph_lazy_adapt, h->graph_lazy4_adapt);
-  drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
 }
 
 }  // namespace
@@ -155,19 +151,8 @@ void drop_lazy_graphs(ksim_handle* h) {
 namespace ksim_host {
 
 void drop_graphs(ksim_handle* h) {
-  drop_cycle_graphs(h);
-  for (auto& kv : h->sweep_graphs)               // they hold the static columns and the queue
-    if (kv.second) (void)hipGraphExecDestroy(kv.second);
-  h->sweep_graphs.clear();
-  if (h->graph_batch) (void)hipGraphExecDestroy(h->graph_batch);
-  if (h->graph_batch_fast) (void)hipGraphExecDestroy(h->graph_batch_fast);
-  if (h->graph_batch_stab) (void)hipGraphExecDestroy(h->graph_batch_stab);
-  h->graph_batch_stab = nullptr;
-  if (h->graph_tbatch) (void)hipGraphExecDestroy(h->graph_tbatch);
-  drop_lazy_graphs(h);
-  h->graph_batch_fast = nullptr;
-  h->graph_batch = nullptr;
-  h->graph_tbatch = nullptr;
+  drop_graphs_if(h, [](const GraphKey&) { return true; });
+  drop_cycle_graphs(h);                            // the group graphs and the generation
 }
 
 // The loaded queue, with everything compiled against the rows it was loaded
@@ -446,10 +431,38 @@ bool run_stab(const ksim_handle* h, int32_t a, int32_t b) {
 }
 
 // The key kernels of a batch run: FAST, FAST with the static table, or generic.
-void pick_keys(const ksim_handle* h, int32_t a, int32_t b, LaunchArgs& la) {
-  la.fast = run_fast(h, a, b);
-  la.stab = !la.fast && run_stab(h, a, b);
-  la.fast = la.fast || la.stab;
+void pick_keys(const ksim_handle* h, int32_t a, int32_t b, bool& fast, bool& stab) {
+  fast = run_fast(h, a, b);
+  stab = !fast && run_stab(h, a, b);
+  fast = fast || stab;
+}
+
+// What a run [a, b) of one handle launches, decided once (plan_run) for
+// everything that runs, times or asks about it: run_range, ksim_time_kernels,
+// ksim_time_eval, ksim_sweep_loaded.  A form's number is that of the kernel
+// family its times are filed under (kFamilies).
+enum class RunForm : int {
+  kPerPod,       // per-pod cycles (launch_cycle)
+  kBatch,        // three-launch P100 batches (launch_batch)
+  kAdaptBatch,   // three-launch ADAPT batches (launch_batch_adapt)
+  kTbatch,       // topology batches (launch_tbatch)
+  kLazy,         // deferred-commit P100 batches (launch_batch_lazy)
+  kLazyAdapt,    // deferred-commit ADAPT batches (launch_batch_adapt_lazy)
+};
+
+struct RunPlan {
+  RunForm form = RunForm::kPerPod;
+  bool topo = false;                               // per-pod: the topology kernels run
+  bool fast = false, stab = false;                 // LaunchArgs: the batch key kernels (pick_keys)
+  bool fuse_min = false, fuse_ext = false, ptab = false;   // LaunchArgs: the per-pod cycle's variants
+  bool rt = false;                                 // kLazy: the request-class table (reqtab_ok)
+  int family() const { return (int)form; }
+  bool lazy() const { return form == RunForm::kLazy || form == RunForm::kLazyAdapt; }
+  bool adapt() const { return form == RunForm::kAdaptBatch || form == RunForm::kLazyAdapt; }
+};
+
+void apply_plan(const RunPlan& p, LaunchArgs& la) {
+  std::tie(la.fast, la.stab, la.fuse_min, la.fuse_ext, la.ptab) = std::tie(p.fast, p.stab, p.fuse_min, p.fuse_ext, p.ptab);
 }
 
 // NetworkBandwidth in the profile (Filter or Score)
@@ -632,11 +645,13 @@ int set_run(ksim_handle* h, int32_t first, int32_t end) {
 
 namespace {
 
-int read_state(ksim_handle* h, DevState& st) {
-  HIPCHK(h, hipMemcpyAsync(&st, h->st, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+int read_state_at(ksim_handle* h, const DevState* src, DevState& st) {
+  HIPCHK(h, hipMemcpyAsync(&st, src, sizeof(st), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return KSIM_OK;
 }
+
+int read_state(ksim_handle* h, DevState& st) { return read_state_at(h, h->st, st); }
 
 // reps x body(i) on `stream` (idle: the caller has synchronised it) as an
 // instantiated graph in *out.  body returns KSIM_OK or a code; a capture that
@@ -673,25 +688,28 @@ int capture_launches(ksim_handle* h, int reps, L&& launch, hipGraphExec_t* out) 
   return KSIM_OK;
 }
 
-int capture(ksim_handle* h, bool batch, bool topo, hipGraphExec_t* out, bool fast = false, bool fuse_min = false,
-            bool fuse_ext = false, bool ptab = false, bool stab = false) {
+// The handle's graph under `key`: the cached one, or (unless !may_capture:
+// then none) reps x launch(i) captured now on the synchronised stream and kept.
+// A failed capture leaves no entry.  Runs look their graph up once, at their start.
+template <class L>
+int handle_graph(ksim_handle* h, const GraphKey& key, int reps, L&& launch, hipGraphExec_t* out,
+                 bool may_capture = true) {
+  const auto it = h->graphs.find(key);
+  *out = it == h->graphs.end() ? nullptr : it->second;
+  if (*out || !may_capture) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  LaunchArgs a = make_args(h, h->dp, h->d_chosen);
-  a.fast = fast;
-  a.stab = stab;
-  a.fuse_min = fuse_min;
-  a.fuse_ext = fuse_ext;
-  a.ptab = ptab;
-  if (!batch) return capture_launches(h, kGraphCycles, [&](int) { launch_cycle(a, h->stream, false, topo); }, out);
-  const bool adapt = adapt_mode(h);
-  return capture_launches(h, kGraphBatches, [&](int) {
-    if (adapt)
-      launch_batch_adapt(a, h->stream);
-    else
-      launch_batch(a, h->stream);
-  }, out);
+  if (int rc = capture_launches(h, reps, launch, out)) return rc;
+  h->graphs.emplace(key, *out);
+  return KSIM_OK;
 }
 
+// The state a run of topology batches starts from (run_tbatch, ksim_time_kernels).
+int tbatch_begin(ksim_handle* h) {
+  HIPCHK(h, hipMemsetAsync(h->sc.tb_win, 0, sizeof(WinState) * kTbPods, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->sc.tb_dom, 0, sizeof(TbDom) * kTbPods * kVarDom, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->sc.tb_vhold, 0, 4 * (size_t)kTbPods * kVarSlots * 2 * KSIM_MAX_SCORE, h->stream));
+  return KSIM_OK;
+}
 
 // A run of topology batch pods [a, b) (set_run done).  The host knows each
 // batch's pod count (the conflict-free run from its first pod, capped) and a
@@ -700,20 +718,16 @@ int capture(ksim_handle* h, bool batch, bool topo, hipGraphExec_t* out, bool fas
 // pinv) leaves pods for the next round.
 int run_tbatch(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la) {
   int rc;
-  HIPCHK(h, hipMemsetAsync(h->sc.tb_win, 0, sizeof(WinState) * kTbPods, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->sc.tb_dom, 0, sizeof(TbDom) * kTbPods * kVarDom, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->sc.tb_vhold, 0, 4 * (size_t)kTbPods * kVarSlots * 2 * KSIM_MAX_SCORE, h->stream));
-  if (!h->graph_tbatch) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = capture_launches(h, kGraphBatches, [&](int) { launch_tbatch(la, h->stream); }, &h->graph_tbatch)))
-      return rc;
-  }
+  if ((rc = tbatch_begin(h))) return rc;
+  hipGraphExec_t graph;
+  if ((rc = handle_graph(h, {GraphKind::kTbatch, {}}, kGraphBatches, [&](int) { launch_tbatch(la, h->stream); }, &graph)))
+    return rc;
   int32_t cursor = a;
   while (cursor < b) {
     int32_t nbat = 0;
     for (int32_t i = cursor; i < b; nbat++) i += std::min(std::min(kTbPods, b - i), std::max(h->tlen[i], 1));
     int32_t done = 0;
-    for (; done + kGraphBatches <= nbat; done += kGraphBatches) HIPCHK(h, hipGraphLaunch(h->graph_tbatch, h->stream));
+    for (; done + kGraphBatches <= nbat; done += kGraphBatches) HIPCHK(h, hipGraphLaunch(graph, h->stream));
     for (; done < nbat; done++) launch_tbatch(la, h->stream);
     HIPCHK(h, hipGetLastError());
     DevState st;
@@ -759,10 +773,7 @@ int sync_one_cut(ksim_handle* h) {
   const bool want = v && v[0] == '1';
   if (want == h->one_cut) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_lazy_graphs(h);
-  for (auto& kv : h->sweep_graphs)
-    if (kv.second) (void)hipGraphExecDestroy(kv.second);
-  h->sweep_graphs.clear();
+  drop_graphs_if(h, [](const GraphKey& k) { return k.kind == GraphKind::kLazy || k.kind == GraphKind::kSweep; });
   drop_group_graphs(h);                           // a replica group's (its leader's)
   h->one_cut = want;
   return KSIM_OK;
@@ -772,7 +783,7 @@ int alloc_lazy(ksim_handle* h) {
   if (int rc = sync_one_cut(h)) return rc;
   if (h->lazy_n == h->dc.n) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_lazy_graphs(h);
+  drop_graphs_if(h, is_lazy);
   free_bufs(h->lazy_bufs);
   h->lazy_n = -1;
   if (!h->prog) {   // kept for the handle's life: the graphs hold its address
@@ -839,6 +850,33 @@ bool reqtab_ok(const ksim_handle* h, int32_t a, int32_t b) {
   return true;
 }
 
+// The plan of run [a, b), one of for_each_run's (batch, topo: its path).
+RunPlan plan_run(const ksim_handle* h, int32_t a, int32_t b, bool batch, bool topo) {
+  RunPlan p;
+  if (!batch) {
+    p.topo = topo;
+    p.fuse_min = topo;
+    for (int32_t i = a; i < b && p.fuse_min; i++) p.fuse_min = h->hard_small[i] != 0;
+    p.fuse_ext = true;
+    for (int32_t i = a; i < b && p.fuse_ext; i++) p.fuse_ext = h->soft_le1[i] != 0;
+    p.ptab = h->topo[a] == 2;                      // runs are uniform in topo (for_each_run)
+  } else if (topo) {
+    p.form = RunForm::kTbatch;
+  } else {
+    // the FAST evaluation kernel when every pod of the run is trivial with
+    // cpu/memory scoring, or is in a static class (STAB)
+    pick_keys(h, a, b, p.fast, p.stab);
+    const bool adapt = adapt_mode(h);
+    if (lazy_ok(h, a, b, p.fast, p.stab)) {
+      p.form = adapt ? RunForm::kLazyAdapt : RunForm::kLazy;
+      p.rt = reqtab_ok(h, a, b);
+    } else {
+      p.form = adapt ? RunForm::kAdaptBatch : RunForm::kBatch;
+    }
+  }
+  return p;
+}
+
 // The table's two halves for the handle's cluster, then (at a 256-byte step)
 // the ring's patch entries P[kLazySlots][C][kBatchPods]; a reallocation drops
 // the graph that holds their addresses (ensure_stab's rule).  Behind them (a
@@ -854,7 +892,7 @@ int ensure_rtab(ksim_handle* h) {
   const size_t need = rtab_halves_bytes(h) + rtab_patch_bytes(h) + sizeof(PodRec) * 2 * 2 * kBatchPods;
   if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
+  drop_graphs_if(h, is_table);
   free_bufs(h->rtab_bufs);
   h->rtab_bytes = 0;
   void* p = nullptr;
@@ -948,12 +986,6 @@ int lazy_end(ksim_handle* h, int64_t f) {
   return KSIM_OK;
 }
 
-int read_state_at(ksim_handle* h, const DevState* src, DevState& st) {
-  HIPCHK(h, hipMemcpyAsync(&st, src, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return KSIM_OK;
-}
-
 // A run of pods [a, b) as deferred-commit batches (lazy_ok; set_run done).
 // Batch i commits batch i - 1; each stretch of launches ends with a flush, whose
 // state tells the host where the run stands.  A batch commits 1..kBatchPods
@@ -1019,11 +1051,6 @@ int lazy_end_run(ksim_handle* h, int64_t f) {
   return KSIM_OK;
 }
 
-// kGraphBatches (tail: kLazySlots) batches of the flavour from ring phase 0.
-int capture_lazy(ksim_handle* h, const LaunchArgs& la, bool rt, int batches, hipGraphExec_t* out) {
-  return capture_launches(h, batches, [&](int i) { lazy_launch(h, lazy_batch(h, la, i, rt), h->stream); }, out);
-}
-
 // KSIM_FEED_FLUSH=1 (read at every run): every stretch ends with a flush and
 // a synchronised state read, the loop's fallback taken unconditionally (an
 // A/B form of the same runs, and the fallback's test).
@@ -1041,8 +1068,8 @@ bool feed_flush_forced() {
 // the host waits for.  A word that does not move within the deadline (sized by
 // the launches outstanding) ends the stretch the old way: a flush, a state
 // read, a synchronisation.  zero_counters: the begin launch zeroes the call's
-// counters (run_range).
-int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la, bool zero_counters) {
+// counters (run_range).  plan: the run's (a deferred-commit form).
+int run_lazy(ksim_handle* h, int32_t a, int32_t b, const RunPlan& plan, const LaunchArgs& la, bool zero_counters) {
   int rc;
   if ((rc = alloc_lazy(h))) return rc;
   volatile unsigned long long* const word = h->prog;
@@ -1051,24 +1078,18 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const LaunchArgs& la, bool ze
   if ((rc = lazy_begin_run(h, a, b, zero_counters))) return rc;
   // the request-class table, rebuilt from the run's starting snapshot in
   // stream order: anything may have moved X since the last run
-  const bool rt = reqtab_ok(h, a, b);
+  const bool rt = plan.rt;
   if (rt) {
     h->rtab_runs++;
     if ((rc = reqtab_begin(h, la, a, b))) return rc;
   }
-  if (rt && h->graph_lazy_rt && h->rt_graph_ncls != h->rq_ncls) {   // a reloaded queue with other classes
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    drop_lazy_pair(h->graph_lazy_rt, h->graph_lazy4_rt);
-  }
-  hipGraphExec_t& graph = adapt_mode(h) ? h->graph_lazy_adapt : rt ? h->graph_lazy_rt : h->graph_lazy;
-  hipGraphExec_t& graph4 = adapt_mode(h) ? h->graph_lazy4_adapt : rt ? h->graph_lazy4_rt : h->graph_lazy4;
-  if (!graph || !graph4) {
-    if (rt) h->rt_graph_ncls = h->rq_ncls;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    drop_lazy_pair(graph, graph4);
-    if ((rc = capture_lazy(h, la, rt, kGraphBatches, &graph)) || (rc = capture_lazy(h, la, rt, kLazySlots, &graph4)))
-      return rc;
-  }
+  // the run's graph and its tail graph, both from ring phase 0, captured together
+  const int32_t adapt = plan.adapt(), ncls = rt ? h->rq_ncls : 0;
+  hipGraphExec_t graph, graph4;
+  const auto batch_i = [&](int i) { lazy_launch(h, lazy_batch(h, la, i, rt), h->stream); };
+  if ((rc = handle_graph(h, {GraphKind::kLazy, {adapt, ncls, 0}}, kGraphBatches, batch_i, &graph)) ||
+      (rc = handle_graph(h, {GraphKind::kLazy, {adapt, ncls, 1}}, kLazySlots, batch_i, &graph4)))
+    return rc;
   static_assert(kGraphBatches % kLazySlots == 0, "lazy graphs keep the ring phase");
   const bool forced = feed_flush_forced();
   int64_t i = 0;                  // the next launch's ring index (flushes take one)
@@ -1354,14 +1375,11 @@ int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lan
   // st0 / idle / htab are read by the copies above when they are enqueued
   // (pageable memory: staged before hipMemcpyAsync returns)
   HIPCHK(h, hipMemcpyAsync(tab, htab.data(), sizeof(SweepLane) * htab.size(), hipMemcpyHostToDevice, h->stream));
-  hipGraphExec_t& graph = h->sweep_graphs[{lanes, def}];
-  if (!graph && count >= kBatchPods * kGraphBatches) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = capture_launches(h, kGraphBatches, [&](int i) {
-           launch_sweep_batch(c, P, tab + (size_t)(i & 3) * kSweepMaxLanes, lanes, def, h->stream);
-         }, &graph)))
-      return rc;
-  }
+  hipGraphExec_t graph;                             // captured by a run long enough to replay it
+  if ((rc = handle_graph(h, {GraphKind::kSweep, {lanes, def}}, kGraphBatches, [&](int i) {
+         launch_sweep_batch(c, P, tab + (size_t)(i & 3) * kSweepMaxLanes, lanes, def, h->stream);
+       }, &graph, count >= kBatchPods * kGraphBatches)))
+    return rc;
   auto phase_tab = [&](int64_t i) { return tab + (size_t)(i & 3) * kSweepMaxLanes; };
   int64_t i = 0;
   while (live > 0) {
@@ -1421,43 +1439,36 @@ int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lan
 
 int reset_counters(ksim_handle* h, hipStream_t stream);
 
-// Run pods [a, b) on one path (all of them share the path).
-int run_range(ksim_handle* h, int32_t a, int32_t b, bool batch, bool topo) {
+// Run pods [a, b) on one path (all of them share the path: one of
+// for_each_run's runs), in the form of its plan (plan_run on this handle).
+int run_range(ksim_handle* h, int32_t a, int32_t b, const RunPlan& plan) {
   int rc;
   // No launch is ever issued past the end of the run (a launch there would
   // exit at once and skew per-kernel averages): whole graphs while they fit,
   // then single launches for the remainder.
   LaunchArgs la = make_args(h, h->dp, h->d_chosen);
+  apply_plan(plan, la);
   // the call's counters are zeroed before its first run: by a deferred-commit
   // run's begin launch, which sets the run header too, or on their own
   const bool zero = h->counters_pending;
   h->counters_pending = false;
-  if (batch && !topo) {
-    // the FAST evaluation kernel when every pod of the run is trivial with
-    // cpu/memory scoring, or is in a static class (STAB)
-    pick_keys(h, a, b, la);
-    if (lazy_ok(h, a, b, la.fast, la.stab)) return run_lazy(h, a, b, la, zero);
-  }
+  if (plan.lazy()) return run_lazy(h, a, b, plan, la, zero);
   if (zero && (rc = reset_counters(h, h->stream))) return rc;
   if ((rc = set_run(h, a, b))) return rc;
-  if (!batch) {
-    la.fuse_min = topo;
-    for (int32_t i = a; i < b && la.fuse_min; i++) la.fuse_min = h->hard_small[i] != 0;
-    la.fuse_ext = true;
-    for (int32_t i = a; i < b && la.fuse_ext; i++) la.fuse_ext = h->soft_le1[i] != 0;
-    la.ptab = h->topo[a] == 2;                     // runs are uniform in topo (for_each_run)
-    hipGraphExec_t& g =
-        h->graph_cycle[(topo ? 1 : 0) | (la.fuse_min ? 2 : 0) | (la.fuse_ext ? 4 : 0) | (la.ptab ? 8 : 0)];
-    if (!g && (rc = capture(h, false, topo, &g, false, la.fuse_min, la.fuse_ext, la.ptab))) return rc;
+  hipGraphExec_t graph;
+  if (plan.form == RunForm::kPerPod) {
+    const GraphKey key{GraphKind::kCycle, {plan.topo, la.fuse_min, la.fuse_ext, la.ptab}};
+    if ((rc = handle_graph(h, key, kGraphCycles, [&](int) { launch_cycle(la, h->stream, false, plan.topo); }, &graph)))
+      return rc;
     int32_t done = a;
-    for (; done + kGraphCycles <= b; done += kGraphCycles) HIPCHK(h, hipGraphLaunch(g, h->stream));
-    for (; done < b; done++) launch_cycle(la, h->stream, false, topo);
+    for (; done + kGraphCycles <= b; done += kGraphCycles) HIPCHK(h, hipGraphLaunch(graph, h->stream));
+    for (; done < b; done++) launch_cycle(la, h->stream, false, plan.topo);
     HIPCHK(h, hipGetLastError());
     return KSIM_OK;
   }
-  if (topo) return run_tbatch(h, a, b, la);
-  hipGraphExec_t& gb = la.stab ? h->graph_batch_stab : la.fast ? h->graph_batch_fast : h->graph_batch;
-  if (!gb && (rc = capture(h, true, false, &gb, la.fast, false, false, false, la.stab))) return rc;
+  if (plan.form == RunForm::kTbatch) return run_tbatch(h, a, b, la);
+  const auto one_batch = [&](int) { return plan.adapt() ? launch_batch_adapt(la, h->stream) : launch_batch(la, h->stream); };
+  if ((rc = handle_graph(h, {GraphKind::kBatch, {la.fast, la.stab}}, kGraphBatches, one_batch, &graph))) return rc;
   // every batch commits between 1 and kBatchPods pods: a graph of
   // kGraphBatches batches never overshoots while left >= kBatchPods * kGraphBatches,
   // and ceil(left / kBatchPods) single batches never overshoot either
@@ -1466,15 +1477,10 @@ int run_range(ksim_handle* h, int32_t a, int32_t b, bool batch, bool topo) {
     const int32_t left = b - cursor;
     if (left >= kBatchPods * kGraphBatches) {
       const int reps = left / (kBatchPods * kGraphBatches);
-      for (int r = 0; r < reps; r++) HIPCHK(h, hipGraphLaunch(gb, h->stream));
+      for (int r = 0; r < reps; r++) HIPCHK(h, hipGraphLaunch(graph, h->stream));
     } else {
       const int n1 = (left + kBatchPods - 1) / kBatchPods;
-      for (int r = 0; r < n1; r++) {
-        if (adapt_mode(h))
-          launch_batch_adapt(la, h->stream);
-        else
-          launch_batch(la, h->stream);
-      }
+      for (int r = 0; r < n1; r++) one_batch(r);
       HIPCHK(h, hipGetLastError());
     }
     DevState st;
@@ -1928,8 +1934,7 @@ int shard_schedule(const std::vector<ksim_handle*>& hs, int32_t first, int32_t c
     return for_each_run(g.h0, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
       if (batch && !adapt) return topo ? shard_run_tbatch(g, a, b) : shard_run(g, a, b);
       for (auto* h : hs) {
-        int rc = run_range(h, a, b, batch, topo);
-        if (rc) return rc;
+        if (int rc = run_range(h, a, b, plan_run(h, a, b, batch, topo))) return rc;
       }
       return (int)KSIM_OK;
     }, true);
@@ -1940,8 +1945,6 @@ int shard_schedule(const std::vector<ksim_handle*>& hs, int32_t first, int32_t c
     return adapt ? shard_run_adapt(g, a, b) : shard_run(g, a, b);
   }, adapt_batch);
 }
-
-
 
 int reset_counters(ksim_handle* h, hipStream_t stream) {
   HIPCHK(h, hipMemsetAsync(&h->st->truncations, 0, 4, stream));
@@ -3620,7 +3623,7 @@ int ksim_schedule_loaded(ksim_handle* h, int32_t first, int32_t count, int32_t* 
     h->counters_pending = defer_zero;
     rc = for_each_run(h, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
       if (!batch) perpod += b - a;
-      return run_range(h, a, b, batch, topo);
+      return run_range(h, a, b, plan_run(h, a, b, batch, topo));
     });
     h->counters_pending = false;
   }
@@ -3678,9 +3681,8 @@ int ksim_sweep_loaded(ksim_handle* h, int32_t first, int32_t count, const ksim_p
     bool one = true;
     (void)for_each_run(h, first, count, [&](int32_t a, int32_t b, bool batch, bool topo) {
       runs++;
-      LaunchArgs la{};
-      if (batch && !topo) pick_keys(h, a, b, la);
-      one = one && batch && !topo && la.fast && !la.stab && lazy_ok(h, a, b, la.fast, la.stab);
+      const RunPlan p = plan_run(h, a, b, batch, topo);
+      one = one && p.form == RunForm::kLazy && p.fast && !p.stab;
       return KSIM_OK;
     });
     if (runs > 1 || !one) return no("the range is not one run of the deferred-commit FAST batches");
@@ -3857,6 +3859,20 @@ int ksim_schedule_batch(ksim_handle* h, const ksim_pod_set* ps, int32_t* chosen,
   return ksim_schedule_loaded(h, 0, ps->n_pods, chosen, stats);
 }
 
+// ksim_time_kernels' slots: the kernels of the six launch forms, a family per
+// RunForm in the forms' order, each family's kernels in launch order.  A slot
+// is its family's base plus the kernel's place in it (ksim_kernel_name).
+struct KernelFamily { const char* const* names; int count; };
+constexpr KernelFamily kFamilies[] = {
+    {kKernelNames, kKernelsPerCycle},       {kBatchKernelNames, kKernelsPerBatch},
+    {kAdaptKernelNames, kKernelsPerAdapt},  {kTbatchKernelNames, kKernelsPerTbatch},
+    {kLazyKernelNames, kKernelsPerLazy},    {kLazyAdaptKernelNames, kKernelsPerLazyAdapt},
+};
+constexpr int kFamilyCount = (int)(sizeof(kFamilies) / sizeof(kFamilies[0]));
+static_assert(kFamilyCount == (int)RunForm::kLazyAdapt + 1, "a kernel family per run form");
+constexpr int family_base(int f) { return f == 0 ? 0 : family_base(f - 1) + kFamilies[f - 1].count; }
+constexpr int kKernelSlots = family_base(kFamilyCount);
+
 int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, int32_t* kernel) {
   int rc = ensure_ready(h);
   if (rc) return rc;
@@ -3872,193 +3888,166 @@ int ksim_time_eval(ksim_handle* h, int32_t first, int32_t reps, double* avg_ms, 
   // batch whatever batch 0 commits)
   const int32_t end = batch ? std::min(h->dp.n_pods, first + 2 * kBatchPods) : first + 1;
   if ((rc = set_run(h, first, end))) return rc;
+  const RunPlan plan = plan_run(h, first, end, batch, !batch && h->topo[first] != 0);
   LaunchArgs a = make_args(h, h->dp, h->d_chosen);
-  if (batch) pick_keys(h, first, end, a);
-  a.fuse_min = !batch && h->topo[first] && h->hard_small[first];
-  a.fuse_ext = !batch && h->soft_le1[first];
-  a.ptab = !batch && h->topo[first] == 2;
-  if (batch && a.fast && lazy_ok(h, first, end, true, a.stab)) {
-    // the deferred-commit evaluation launch as the run issues it: batch 0 of
-    // the run (both launches), then batch 1's k_batch_top_commit repeated
-    // (idempotent: it reads X[0], st[0] and slot 0, and writes X[1], st[1],
-    // the lists and batch 0's placements); the handle's own buffers keep
-    // their contents
-    // (with the request-class table when the run from `first` to the queue's
-    // end takes it: the launch the timing stands for)
-    if ((rc = lazy_begin(h))) return rc;
-    const bool rt = reqtab_ok(h, first, h->dp.n_pods);
-    if (rt && (rc = reqtab_begin(h, a, first, end))) return rc;
-    launch_batch_lazy(lazy_batch(h, a, 0, rt), h->stream);
-    const LazyBatch z = lazy_batch(h, a, 1, rt);
-    launch_lazy_top(z, h->stream);
+  apply_plan(plan, a);
+  // one warming launch (code object, caches), then `reps` back to back
+  auto timed = [&](auto&& launch) -> int {
+    launch();
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    for (int32_t i = 0; i < reps; i++) launch_lazy_top(z, h->stream);
+    for (int32_t i = 0; i < reps; i++) launch();
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipEventSynchronize(h->ev1));
     HIPCHK(h, hipGetLastError());
     float ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *avg_ms = ms / reps;
-    if (kernel) *kernel = kKernelsPerCycle + kKernelsPerBatch + kKernelsPerAdapt + kKernelsPerTbatch;
+    return KSIM_OK;
+  };
+  if (plan.form == RunForm::kLazy) {
+    // the deferred-commit evaluation launch as the run issues it: batch 0 of
+    // the run (both launches), then batch 1's k_batch_top_commit repeated
+    // (idempotent: it reads X[0], st[0] and slot 0, and writes X[1], st[1],
+    // the lists and batch 0's placements); the handle's own buffers keep
+    // their contents
+    // (the one departure from the plan: with the request-class table when the
+    // run from `first` to the queue's end takes it, not the two batches timed
+    // here: the launch the timing stands for)
+    if ((rc = lazy_begin(h))) return rc;
+    const bool rt = reqtab_ok(h, first, h->dp.n_pods);
+    if (rt && (rc = reqtab_begin(h, a, first, end))) return rc;
+    launch_batch_lazy(lazy_batch(h, a, 0, rt), h->stream);
+    const LazyBatch z = lazy_batch(h, a, 1, rt);
+    if ((rc = timed([&] { launch_lazy_top(z, h->stream); }))) return rc;
+    if (kernel) *kernel = family_base(plan.family());   // k_batch_top_commit
     return KSIM_OK;
   }
-  auto launch = [&] {
+  rc = timed([&] {
     if (batch) launch_batch_eval_only(a, h->stream);
     else launch_filter_only(a, h->stream);
-  };
-  launch();                                          // warm (code object, caches)
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  for (int32_t i = 0; i < reps; i++) launch();
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipEventSynchronize(h->ev1));
-  HIPCHK(h, hipGetLastError());
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *avg_ms = ms / reps;
+  });
+  if (rc) return rc;
   // the timed no-window filter passes added into the window counters
   if (!batch) HIPCHK(h, hzero(h, h->sc.win, sizeof(WinState)));
-  if (kernel) *kernel = batch ? kKernelsPerCycle : 2;   // k_batch_top / k_filter_score
+  if (kernel) *kernel = family_base(plan.family()) + (batch ? 0 : 2);   // k_batch_top / k_filter_score
   return KSIM_OK;
 }
 
 const char* ksim_kernel_name(int32_t k) {
-  if (k >= 0 && k < kKernelsPerCycle) return kKernelNames[k];
-  k -= kKernelsPerCycle;
-  if (k >= 0 && k < kKernelsPerBatch) return kBatchKernelNames[k];
-  k -= kKernelsPerBatch;
-  if (k >= 0 && k < kKernelsPerAdapt) return kAdaptKernelNames[k];
-  k -= kKernelsPerAdapt;
-  if (k >= 0 && k < kKernelsPerTbatch) return kTbatchKernelNames[k];
-  k -= kKernelsPerTbatch;
-  if (k >= 0 && k < kKernelsPerLazy) return kLazyKernelNames[k];
-  k -= kKernelsPerLazy;
-  if (k >= 0 && k < kKernelsPerLazyAdapt) return kLazyAdaptKernelNames[k];
+  for (int f = 0; f < kFamilyCount; f++)
+    if (k >= family_base(f) && k < family_base(f + 1)) return kFamilies[f].names[k - family_base(f)];
   return nullptr;
+}
+
+// One timed stretch of ksim_time_kernels: `iters` iterations of `per` kernels,
+// launch(evs) recording its per + 1 events and returning the mask of the
+// kernels it launched; then read(), the caller's state read, and did(), the
+// iterations that did work by that state, whose times go to sum / n from slot
+// 0 up.  The events are destroyed on every path.
+template <class L, class R, class D>
+int timed_stretch(ksim_handle* h, int32_t iters, int per, double* sum, int64_t* n, L&& launch, R&& read, D&& did) {
+  std::vector<hipEvent_t> evs((size_t)iters * (per + 1), nullptr);
+  const int rc = [&]() -> int {
+    for (auto& e : evs) HIPCHK(h, hipEventCreate(&e));
+    uint32_t launched = 0;
+    for (int32_t t = 0; t < iters; t++) launched = launch(&evs[(size_t)t * (per + 1)]);
+    HIPCHK(h, hipGetLastError());
+    if (int r = read()) return r;
+    const int32_t worked = did();
+    for (int32_t t = 0; t < worked; t++)
+      for (int k = 0; k < per; k++) {
+        if (!((launched >> k) & 1u)) continue;     // an empty event pair, not a kernel
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, evs[(size_t)t * (per + 1) + k], evs[(size_t)t * (per + 1) + k + 1]));
+        sum[k] += ms;
+        n[k] += 1;
+      }
+    return KSIM_OK;
+  }();
+  for (auto& e : evs)
+    if (e) (void)hipEventDestroy(e);
+  return rc;
 }
 
 int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_ms, int64_t* launches, int32_t cap) {
   int rc = ensure_ready(h);
   if (rc) return rc;
-  constexpr int kKinds = kKernelsPerCycle + kKernelsPerBatch + kKernelsPerAdapt + kKernelsPerTbatch + kKernelsPerLazy +
-                         kKernelsPerLazyAdapt;
-  if (!avg_ms || cap < kKinds) return set_err(h, KSIM_E_INVALID, "avg_ms too small");
+  if (!avg_ms || cap < kKernelSlots) return set_err(h, KSIM_E_INVALID, "avg_ms too small");
   if (!h->dp.pods || first < 0 || count <= 0 || first + count > h->dp.n_pods)
     return set_err(h, KSIM_E_INVALID, "range out of loaded pods");
   HIPCHK(h, hipSetDevice(h->device));
   if ((rc = ensure_stab(h))) return rc;
-  double sum[kKinds] = {0};
-  int64_t n[kKinds] = {0};
+  double sum[kKernelSlots] = {0};
+  int64_t n[kKernelSlots] = {0};
   LaunchArgs a = make_args(h, h->dp, h->d_chosen);
   rc = for_each_run(h, first, count, [&](int32_t lo, int32_t hi, bool batch, bool topo) -> int {
     int r;
     if ((r = set_run(h, lo, hi))) return r;
-    const bool adapt = batch && adapt_mode(h);
-    const bool tb = batch && topo;                 // topology batch runs (class 3)
-    // the same kernel variants the run itself would launch
-    a.fast = a.stab = false;
-    if (batch) pick_keys(h, lo, hi, a);
-    a.fuse_min = !batch && topo;
-    for (int32_t i = lo; i < hi && a.fuse_min; i++) a.fuse_min = h->hard_small[i] != 0;
-    a.fuse_ext = !batch;
-    for (int32_t i = lo; i < hi && a.fuse_ext; i++) a.fuse_ext = h->soft_le1[i] != 0;
-    a.ptab = !batch && h->topo[lo] == 2;
-    const int per = tb ? kKernelsPerTbatch : adapt ? kKernelsPerAdapt : batch ? kKernelsPerBatch : kKernelsPerCycle;
-    const int base = tb      ? kKernelsPerCycle + kKernelsPerBatch + kKernelsPerAdapt
-                     : adapt ? kKernelsPerCycle + kKernelsPerBatch
-                     : batch ? kKernelsPerCycle : 0;
-    if (tb) {
-      HIPCHK(h, hipMemsetAsync(h->sc.tb_win, 0, sizeof(WinState) * kTbPods, h->stream));
-      HIPCHK(h, hipMemsetAsync(h->sc.tb_dom, 0, sizeof(TbDom) * kTbPods * kVarDom, h->stream));
-      HIPCHK(h, hipMemsetAsync(h->sc.tb_vhold, 0, 4 * (size_t)kTbPods * kVarSlots * 2 * KSIM_MAX_SCORE, h->stream));
-    }
-    if (batch && !tb && a.fast && lazy_ok(h, lo, hi, true, a.stab)) {
+    // the kernel variants the run itself launches: its plan
+    const RunPlan plan = plan_run(h, lo, hi, batch, topo);
+    apply_plan(plan, a);
+    const int per = kFamilies[plan.family()].count, base = family_base(plan.family());
+    int32_t cursor = lo;
+    DevState st;
+    if (plan.lazy()) {
       // deferred-commit batches: two (P100) or three to four (ADAPT) launches
       // each, a flush (untimed) before every state read
-      const int lper = adapt ? kKernelsPerLazyAdapt : kKernelsPerLazy;
-      const int lbase = kKernelsPerCycle + kKernelsPerBatch + kKernelsPerAdapt + kKernelsPerTbatch +
-                        (adapt ? kKernelsPerLazy : 0);
       HIPCHK(h, hipMemsetAsync(&h->st->batches, 0, 4, h->stream));
       if ((r = lazy_begin(h))) return r;
-      const bool rt = reqtab_ok(h, lo, hi);
-      if (rt && (r = reqtab_begin(h, a, lo, hi))) return r;
+      if (plan.rt && (r = reqtab_begin(h, a, lo, hi))) return r;
       int64_t i = 0;
-      int32_t cursor = lo, done_batches = 0;
+      int32_t done_batches = 0;
       while (cursor < hi) {
         const int32_t iters = std::min(64, (hi - cursor + kBatchPods - 1) / kBatchPods);
-        std::vector<hipEvent_t> evs((size_t)iters * (lper + 1));
-        for (auto& e : evs) HIPCHK(h, hipEventCreate(&e));
-        uint32_t launched = 0;
-        for (int32_t t = 0; t < iters; t++, i++)
-          launched = lazy_launch(h, lazy_batch(h, a, i, rt), h->stream, &evs[(size_t)t * (lper + 1)]);
-        lazy_flush(h, lazy_batch(h, a, i, rt), h->stream);
-        HIPCHK(h, hipGetLastError());
-        DevState st;
-        if ((r = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return r;
-        const int32_t did = std::min<int32_t>(iters, st.batches - done_batches);
+        r = timed_stretch(
+            h, iters, per, sum + base, n + base,
+            [&](hipEvent_t* evs) { return lazy_launch(h, lazy_batch(h, a, i++, plan.rt), h->stream, evs); },
+            [&]() -> int {
+              lazy_flush(h, lazy_batch(h, a, i, plan.rt), h->stream);
+              HIPCHK(h, hipGetLastError());
+              return read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st);
+            },
+            [&] { return std::min<int32_t>(iters, st.batches - done_batches); });
+        if (r) return r;
         done_batches = st.batches;
-        for (int32_t t = 0; t < did; t++)
-          for (int k = 0; k < lper; k++) {
-            if (!((launched >> k) & 1u)) continue;   // an empty event pair (the window fused into the top)
-            float ms = 0;
-            const size_t e0 = (size_t)t * (lper + 1);
-            HIPCHK(h, hipEventElapsedTime(&ms, evs[e0 + k], evs[e0 + k + 1]));
-            sum[lbase + k] += ms;
-            n[lbase + k] += 1;
-          }
-        for (auto& e : evs) (void)hipEventDestroy(e);
         if (st.cursor <= cursor) return set_err(h, KSIM_E_DEVICE, "no progress while timing");
         cursor = st.cursor;
         i++;
       }
       return lazy_end(h, i - 1);
     }
-    int32_t cursor = lo;
-    uint32_t launched = (1u << per) - 1;         // batch paths launch every kernel of a batch
+    const bool tb = plan.form == RunForm::kTbatch;
+    if (tb && (r = tbatch_begin(h))) return r;
     while (cursor < hi) {
       int32_t iters = batch ? std::min(64, (hi - cursor + kBatchPods - 1) / kBatchPods) : std::min(512, hi - cursor);
       if (tb) {                                  // the batches the host's run lengths predict (run_tbatch)
         iters = 0;
         for (int32_t i = cursor; i < hi && iters < 64; iters++) i += std::min(std::min(kTbPods, hi - i), std::max(h->tlen[i], 1));
       }
-      std::vector<hipEvent_t> evs((size_t)iters * (per + 1));
-      for (auto& e : evs) HIPCHK(h, hipEventCreate(&e));
       if (batch) HIPCHK(h, hipMemsetAsync(&h->st->batches, 0, 4, h->stream));
-      for (int32_t i = 0; i < iters; i++) {
-        if (tb)
-          launched = launch_tbatch(a, h->stream, &evs[(size_t)i * (per + 1)]);
-        else if (adapt)
-          launched = launch_batch_adapt(a, h->stream, &evs[(size_t)i * (per + 1)]);
-        else if (batch)
-          launched = launch_batch(a, h->stream, &evs[(size_t)i * (per + 1)]);
-        else
-          launched = launch_cycle(a, h->stream, false, topo, &evs[(size_t)i * (per + 1)]);
-      }
-      HIPCHK(h, hipGetLastError());
-      DevState st;
-      if ((r = read_state(h, st))) return r;
-      // iterations past the end exit at once; count only those that did work
-      const int32_t did = batch ? std::min<int32_t>(iters, st.batches) : std::min(iters, st.cursor - cursor);
-      for (int32_t i = 0; i < did; i++)
-        for (int k = 0; k < per; k++) {
-          if (!((launched >> k) & 1u)) continue;   // an empty event pair, not a kernel
-          float ms = 0;
-          const size_t b = (size_t)i * (per + 1);
-          HIPCHK(h, hipEventElapsedTime(&ms, evs[b + k], evs[b + k + 1]));
-          sum[base + k] += ms;
-          n[base + k] += 1;
-        }
-      for (auto& e : evs) (void)hipEventDestroy(e);
+      r = timed_stretch(
+          h, iters, per, sum + base, n + base,
+          [&](hipEvent_t* evs) {
+            return tb             ? launch_tbatch(a, h->stream, evs)
+                   : plan.adapt() ? launch_batch_adapt(a, h->stream, evs)
+                   : batch        ? launch_batch(a, h->stream, evs)
+                                  : launch_cycle(a, h->stream, false, topo, evs);
+          },
+          [&] { return read_state(h, st); },
+          // iterations past the end exit at once; count only those that did work
+          [&] { return batch ? std::min<int32_t>(iters, st.batches) : std::min(iters, st.cursor - cursor); });
+      if (r) return r;
       if (st.cursor <= cursor) return set_err(h, KSIM_E_DEVICE, "no progress while timing");
       cursor = st.cursor;
     }
     return KSIM_OK;
   });
   if (rc) return rc;
-  for (int k = 0; k < kKinds; k++) {
+  for (int k = 0; k < kKernelSlots; k++) {
     avg_ms[k] = n[k] ? sum[k] / n[k] : 0.0;
     if (launches) launches[k] = n[k];
   }
-  return kKinds;
+  return kKernelSlots;
 }
 
 extern "C" int ksim_get_diag(ksim_handle* h, int64_t* out, int32_t n) {

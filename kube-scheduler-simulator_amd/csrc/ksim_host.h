@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <array>
 #include <map>
 #include <string>
 #include <tuple>
@@ -60,6 +61,23 @@ struct GroupGraphKey {
   bool operator<(const GroupGraphKey& o) const {
     return std::tie(kind, topo, fast, xdom, xreg) < std::tie(o.kind, o.topo, o.fast, o.xdom, o.xreg);
   }
+};
+
+// What a single handle's graph holds (ksim_engine.cpp handle_graph): its kind
+// and, in arg, exactly the launch arguments that kind bakes into the graph.
+enum class GraphKind : int32_t {
+  kCycle,    // kGraphCycles per-pod cycles: {topo, fuse_min, fuse_ext, ptab}
+  kBatch,    // kGraphBatches three-launch batches (P100 or ADAPT, by the profile): {fast, stab}
+  kTbatch,   // kGraphBatches topology batches: {}
+  kLazy,     // deferred-commit batches: {ADAPT, the request-class count (0: no table), tail}; the tail
+             // graph is kLazySlots batches (run_lazy's top-ups), the whole one kGraphBatches
+  kSweep,    // kGraphBatches packed sweep batches: {lanes, def}
+};
+
+struct GraphKey {
+  GraphKind kind;
+  std::array<int32_t, 4> arg;
+  bool operator<(const GraphKey& o) const { return std::tie(kind, arg) < std::tie(o.kind, o.arg); }
 };
 
 struct ksim_handle {
@@ -280,16 +298,13 @@ struct ksim_handle {
   int32_t rank = 0, world = 1;
   ncclComm_t comm = nullptr;
 
-  // per-pod cycles, by variant: topology kernels (1) | critical paths in the
-  // filter pass (2) | NormalizeScore extrema in the filter pass (4)
-  hipGraphExec_t graph_cycle[16] = {};   // | persistent tables (8)
-  hipGraphExec_t graph_batch = nullptr;
-  hipGraphExec_t graph_batch_fast = nullptr;   // k_batch_top<true> runs
-  hipGraphExec_t graph_batch_stab = nullptr;   // static-class runs (LaunchArgs::stab)
-  hipGraphExec_t graph_tbatch = nullptr;       // topology batches (ksim_tbatch.hip)
+  // every graph of this handle's own runs, by what it holds (ksim_engine.cpp
+  // handle_graph captures them, drop_graphs_if destroys them)
+  std::map<GraphKey, hipGraphExec_t> graphs;
   // deferred-commit FAST batches (ksim_internal.h): the second snapshot buffer
-  // X[1] and state st[1], the ring of chain + pairs outputs, kGraphBatches
+  // X[1] and state st[1], the ring of chain + pairs outputs; kGraphBatches
   // batches as one graph (starting at a batch index divisible by kLazySlots)
+  // and, captured with it, the tail graph of kLazySlots batches
   std::vector<DevBuf> lazy_bufs;
   int32_t lazy_n = -1;
   DynCols lazy_x1{};
@@ -297,12 +312,6 @@ struct ksim_handle {
   uint64_t *lazy_g = nullptr, *lazy_m = nullptr;   // [kLazySlots][kBatchPods]
   int32_t* lazy_e = nullptr;                        // [kLazySlots] prefix length, -1 = empty slot
   int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
-  hipGraphExec_t graph_lazy = nullptr;
-  hipGraphExec_t graph_lazy_adapt = nullptr;
-  // the tail graphs: kLazySlots batches of the same flavour, captured with and
-  // dropped with the kGraphBatches graph beside them (run_lazy's top-ups of
-  // fewer than kGraphBatches batches)
-  hipGraphExec_t graph_lazy4 = nullptr, graph_lazy4_adapt = nullptr, graph_lazy4_rt = nullptr;
   // run_lazy's progress words (host-mapped pinned, alloc_lazy): [0] the last
   // state writer's lazy_progress, [1] the batch counter the run started from
   unsigned long long* prog = nullptr;
@@ -322,16 +331,14 @@ struct ksim_handle {
   // pod its class (0xffff: none), the classes' requests, and the table's two
   // halves [2][rq_ncls][dc.n] with the ring's patch entries
   // [kLazySlots][rq_ncls][kBatchPods] behind them (ensure_rtab; a reallocation
-  // drops graph_lazy_rt, the deferred-commit graph of the runs that take the table)
+  // drops the deferred-commit graphs of the runs that take the table)
   std::vector<uint16_t> rq_cls;
   uint16_t* d_rcls = nullptr;
   PodReq* d_rreq = nullptr;
   int32_t rq_ncls = 0;                             // > kReqMaxClasses: too many, no table
   std::vector<DevBuf> rtab_bufs;
   size_t rtab_bytes = 0;
-  hipGraphExec_t graph_lazy_rt = nullptr;
   int64_t rtab_runs = 0;                           // runs that took the table (ksim_get_diag out[27])
-  int32_t rt_graph_ncls = 0;                       // the class count graph_lazy_rt was captured with
   // node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and
   // the global bitmap (allocated at the first such run)
   std::vector<DevBuf> ash_bufs;
@@ -340,7 +347,7 @@ struct ksim_handle {
   // packed policy sweep (ksim_sweep_loaded, run_sweep): the lanes' buffers as
   // one slab sized by (dc.n, lanes), the lane table [kLazySlots][kSweepMaxLanes]
   // (its address is all a sweep graph holds of them), the vectors' profile
-  // copies, the lanes' placement rows, one graph per (lanes, fast_def)
+  // copies, the lanes' placement rows
   struct SweepLaneBufs {
     DynCols x[2];
     uint64_t *g, *m;                             // [kLazySlots][kBatchPods]
@@ -355,7 +362,6 @@ struct ksim_handle {
   DevState* sweep_st = nullptr;                  // [sweep_lanes][2]
   SweepLane* sweep_tab = nullptr;
   DevArena sweep_profs, sweep_rows;
-  std::map<std::pair<int32_t, bool>, hipGraphExec_t> sweep_graphs;
   // deferred-commit batches end at their first pair cut (KSIM_ONE_CUT=1 at the
   // last run's start): the setting the handle's deferred-commit graphs hold
   bool one_cut = false;

@@ -14,8 +14,8 @@ import numpy as np
 from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# KSIM_LIB_VARIANT=<tag> loads an A/B build of the batch geometry
-# (csrc/Makefile "variant": libksim_engine_<tag>.so); the default is the product build.
+# KSIM_LIB_VARIANT=<tag> loads an instrumented or A/B build of the same ABI
+# (csrc/Makefile "flavor", "ab": libksim_engine_<tag>.so); the default is the product build.
 _VARIANT = os.environ.get("KSIM_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, f"libksim_engine_{_VARIANT}.so" if _VARIANT else "libksim_engine.so")
 _LIB = None
