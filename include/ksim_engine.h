@@ -1183,6 +1183,48 @@ int ksim_preempt_many_dom(ksim_handle* h, const ksim_pod_set* pods, int32_t n,
  * call that needs them and freed with the bound table. */
 int32_t ksim_preempt_many_dom_rows(int32_t n_nodes, int32_t n_bound, int32_t n_values);
 
+/* Commit a preemption (the framework's prepareCandidate, or any list of
+ * deleted bound pods): n rows of the bound-pod table leave the device's state
+ * in one call, with no re-upload of the table.  rows[i] is a row in the
+ * caller's order of the last ksim_set_bound_pods (the numbers
+ * ksim_preempt_out.victims reports); pods[pod_index[i]] is that bound pod's
+ * record, as ksim_forget takes it (the table carries neither the non-zero
+ * requests, the bandwidth add nor the pod's own uses and adds).  The rows may
+ * sit on any nodes.
+ *   snapshot    afterwards it equals what ksim_forget(h, pods, pod_index[i],
+ *               node of rows[i]) for every i, in any order, leaves: the node
+ *               columns, num_pods, every class count, the attached volumes
+ *               (ksim_forget's last-holder rule: two victims that are the only
+ *               holders of a volume lower attached by one), nb_alloc and the
+ *               loaded queue's persistent domain tables.  nextStartNodeIndex
+ *               and the pod sequence do not move.
+ *   table       the rows are gone from the per-node importance order and from
+ *               the lists set on the rows (ksim_set_bound_pod_adds, _pdbs,
+ *               _volumes); the survivors keep their relative order.  Every
+ *               later dry run, through any entry point, answers as on a table
+ *               freshly set from the survivors with their lists.
+ *   row numbers keep their meaning: survivors keep the caller's numbers,
+ *               victims[] of later dry runs reports those, and an evicted row
+ *               is never a victim again.  The budgets' allowed counts are not
+ *               touched (the caller re-sets them: ksim_set_bound_pod_pdbs).
+ *   setters     the three ksim_set_bound_pod_* calls still take a CSR over all
+ *               the caller's rows; entries of evicted rows are validated as
+ *               before and then ignored.
+ *   cost        the host does O(n) work and uploads the n pod records; the
+ *               device compacts the table in a fixed number of launches (passes
+ *               over its rows) into a second buffer set, allocated at the first
+ *               commit and freed with the table; one synchronization.
+ * Everything is checked before anything runs; on an error nothing is changed.
+ * KSIM_E_INVALID, the message naming the entry i: n < 0, a null array with
+ * n > 0, no bound table, a row outside the table, a row already evicted, a row
+ * named twice, a pod index outside the set, a pod the per-pod calls refuse, or
+ * a pod record whose cpu, memory, ephemeral-storage or scalar requests differ
+ * from the row's req.  KSIM_E_UNSUPPORTED: shard and replica handles.  n == 0
+ * is KSIM_OK. */
+int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* pods, int32_t n,
+                        const int32_t* rows      /* [n] bound-table rows, caller's row order */,
+                        const int32_t* pod_index /* [n] the rows' pod records in `pods` */);
+
 /* ---- selector / affinity-term matching -------------------- */
 /* The pod-matching half of PodTopologySpread's and InterPodAffinity's
  * PreFilter / PreScore: upstream countPodsMatchSelector,

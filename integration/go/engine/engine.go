@@ -267,6 +267,24 @@ func (e *Engine) PreemptManyDom(ps *C.ksim_pod_set, idx, priority []int32, outs 
 	})
 }
 
+// PreemptCommit: prepareCandidate's evictions in one call.  rows are the
+// victims' rows of the bound-pod table (the numbers a dry run's victims list
+// reports), idx[i] the record of rows[i]'s pod in ps (as Forget takes it).  The
+// snapshot loses the pods and the table their rows, on the device: no table
+// or list is sent again, survivors keep their row numbers.
+func (e *Engine) PreemptCommit(ps *C.ksim_pod_set, rows, idx []int32) error {
+	if len(rows) != len(idx) {
+		return fmt.Errorf("PreemptCommit: %d rows, %d pods", len(rows), len(idx))
+	}
+	if len(rows) == 0 {
+		return nil
+	}
+	return e.locked(func() C.int {
+		return C.ksim_preempt_commit(e.h, ps, C.int32_t(len(rows)), (*C.int32_t)(unsafe.Pointer(&rows[0])),
+			(*C.int32_t)(unsafe.Pointer(&idx[0])))
+	})
+}
+
 // FwFilterNominated: RunFilterPluginsWithNominatedPods' first pass of the
 // cycle in flight on the grouped nodes (plugins.go calls it per node).
 func (e *Engine) FwFilterNominated(nominated *C.ksim_pod_set, nodes, first, count []int32, fail []uint8,

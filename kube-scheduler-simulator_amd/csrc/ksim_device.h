@@ -2189,9 +2189,11 @@ __device__ __forceinline__ void atomic_add_i64(int64_t* x, int64_t v) {
 // commit's one-thread-per-pod binds keep plain read-modify-writes: atomics
 // there cost 9.23 -> 9.86 ms per config-2 step).  A pod's class adds name
 // distinct classes.  ``add0``: this lane's first class add (lane < add_count),
-// loaded by the caller ahead of the node choice.
+// loaded by the caller ahead of the node choice.  ``volumes`` off: the caller
+// moves the attached volumes itself (k_commit_evict: concurrent waves on one node).
 __device__ __forceinline__ void assume_pod_wave(const DevCluster& c, const DevPods& P, const ksim_pod& p, int32_t node,
-                                                int sign, bool tables = true, const ksim_class_add* add0 = nullptr) {
+                                                int sign, bool tables = true, const ksim_class_add* add0 = nullptr,
+                                                bool volumes = true) {
   const int lane = threadIdx.x & 63;
   if (lane == 0) atomic_add_i64(&c.req_cpu[node], sign * p.req_cpu);
   if (lane == 1) atomic_add_i64(&c.req_mem[node], sign * p.req_mem);
@@ -2200,7 +2202,7 @@ __device__ __forceinline__ void assume_pod_wave(const DevCluster& c, const DevPo
   if (lane == 4) atomic_add_i64(&c.nz_mem[node], sign * p.nz_mem);
   if (lane == 5) atomicAdd(&c.num_pods[node], sign);
   if (lane == 6 && p.nb_add) atomic_add_i64(&c.nb_alloc[node], sign * p.nb_add);
-  if (lane == 7) volume_bind(c, P, p, node, sign);
+  if (lane == 7 && volumes) volume_bind(c, P, p, node, sign);
   if (lane >= 8 && lane < 8 + c.n_scalar) {
     const int k = lane - 8;
     int64_t q = 0;

@@ -180,6 +180,13 @@ void drop_bound_pods(ksim_handle* h) {
   h->pre_dindex = nullptr;
   h->pre_maxrow = 0;
   h->pre_n = 0;
+  h->pre_row_node.clear();              // what ksim_preempt_commit keeps of the table
+  h->pre_row_req.clear();
+  h->pre_dead.clear();
+  h->pre_live = 0;
+  h->pre_index_stale = false;
+  h->pre_alt = DevCommit{};
+  h->pre_add_ents = h->pre_pdb_ents = h->pre_vol_ents = 0;
 }
 
 // ksim_preempt_many's per-row slabs: sized by the bound table, so they go with it.

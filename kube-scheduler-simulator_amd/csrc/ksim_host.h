@@ -227,7 +227,24 @@ struct ksim_handle {
   const VolHold* pre_vols = nullptr;
   DevPreempt pre{};
   std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
-  int32_t pre_n = 0;
+  int32_t pre_n = 0;                    // the caller's rows (ksim_set_bound_pods), evicted ones included
+  // ksim_preempt_commit.  Per caller's row: its node and requests as
+  // ksim_set_bound_pods took them, and whether a commit evicted it since
+  // (pre_dead; 2 inside a call: named by it).  pre_live rows are left, at the
+  // table's positions [0, pre_live).  A commit compacts the device's arrays and
+  // leaves pre_index as it was (pre_index_stale): the setters compact it, and
+  // until then a single dry run reads its victims' rows from pre_dindex.
+  // pre_alt holds the table's second buffer set and the scan's scratch (its
+  // *2 fields and pos / dead / before / tile; null: not allocated), owned by
+  // pre_bufs and, each list's, by the list's owner; every commit swaps the two
+  // sets.  pre_*_ents: the entries of each list as its setter uploaded it.
+  std::vector<int32_t> pre_row_node;
+  std::vector<int64_t> pre_row_req;
+  std::vector<uint8_t> pre_dead;
+  int32_t pre_live = 0;
+  bool pre_index_stale = false;
+  DevCommit pre_alt{};
+  size_t pre_add_ents = 0, pre_pdb_ents = 0, pre_vol_ents = 0;
   // ksim_preempt_many.  With the bound table (dropped where pre_bufs is): the
   // device copy of pre_index (in pre_bufs), the most bound pods one node holds,
   // and, allocated at the first call that needs them, the per-row slabs of one

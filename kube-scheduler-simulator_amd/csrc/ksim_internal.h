@@ -454,6 +454,49 @@ struct PreemptManyDom {
 void launch_preempt_many_dom(const LaunchArgs& a, const DevPreempt& pre, const PreemptPlan& common,
                              const PreemptMany& g, const PreemptManyDom& d, hipStream_t stream);
 
+// ksim_preempt_commit (ksim_preempt.hip "committed preemption"): the victims
+// leave the snapshot and the bound table's rows are compacted in place, into
+// the table's second buffer set.  A scan tile is kCommitTile rows: one block of
+// kCommitThreads threads, kCommitTile / kCommitThreads consecutive rows each.
+constexpr int kCommitThreads = 256;
+constexpr int kCommitTile = 1024;                            // KSIM_COMMIT_TILE (ksim/preemption.py)
+struct CommitRec {                     // one victim
+  DevPods P;                           // its pod record as pod 0 of a set of its own
+  int32_t row, node;                   // the caller's row number, the row's node
+};
+struct CommitSum {                     // what the scan carries per row: dead rows, surviving list entries
+  int32_t dead, adds, pids, vols;
+};
+struct DevCommit {
+  int32_t n, n_nodes;                  // rows before the commit, nodes
+  // the table as it is (a list's offsets null: not set) ...
+  const int32_t *off, *prio, *index;
+  const int64_t *start, *req;
+  const int32_t* aoff;
+  const ksim_class_add* adds;
+  const int32_t *poff, *pids;
+  const int32_t* voff;
+  const VolHold* vols;
+  // ... and the second buffer set the survivors go to
+  int32_t *off2, *prio2, *index2;
+  int64_t *start2, *req2;
+  int32_t* aoff2;
+  ksim_class_add* adds2;
+  int32_t *poff2, *pids2;
+  int32_t* voff2;
+  VolHold* vols2;
+  // scratch, kept with the table
+  int32_t* pos;                        // [rows of ksim_set_bound_pods] caller's row -> position
+  uint8_t* dead;                       // [n + 1] the position leaves (position n: the end, never dead)
+  int32_t* before;                     // [n + 1] dead rows before the position
+  CommitSum* tile;                     // [tiles] each tile's sums, then (k_commit_carry) the sums before it
+};
+// Positions 0 .. n are scanned (position n carries the lists' end offsets).
+constexpr int32_t commit_tiles(int32_t n) { return n / kCommitTile + 1; }
+// The launches of one commit: victims recs[0 .. n_victims) evicted, the table compacted.
+void launch_preempt_commit(const DevCluster& c, const DevCommit& m, const CommitRec* recs, int32_t n_victims,
+                           hipStream_t stream);
+
 // The evaluation kernels alone (ksim_time_eval).
 void launch_batch_eval_only(const LaunchArgs& a, hipStream_t stream);
 // topo: the pod carries uses; the PreFilter pass of its cycle runs first (the

@@ -56,6 +56,9 @@
 // topology flags; k_preempt_many_mins: its critical-path minima), and
 // k_preempt_many_dom_nodes runs SpreadForm or FullForm through a row's view
 // that also swaps those in.
+//
+// ksim_preempt_commit makes a dry run's evictions real on the device: the
+// k_commit_* kernels below ("committed preemption").
 #include "ksim_device.h"
 #include "ksim_internal.h"
 #include "ksim_wave.h"
@@ -1258,6 +1261,206 @@ __global__ __launch_bounds__(kPickThreads) void k_preempt_pick(DevCluster c, Dev
     pre.pick[3] = want > 0 ? kept : 0;
     pre.pick[4] = s_node[0] >= 0 ? s_best[0].nviol() : 0;
   }
+}
+
+// ---- committed preemption (ksim_preempt_commit) -----------------------------------
+// The victims of a dry run (or any list of deleted bound pods) leave the
+// device's state: the snapshot as ksim_forget would leave it, and the bound
+// table without their rows, the survivors in their order.  Six launches:
+//   k_commit_begin    pos[caller's row] = position, dead[] = 0
+//   k_commit_evict    one wave per victim: assume_pod_wave with sign -1, the
+//                     attached volumes, dead[its position] = 1
+//   k_commit_sums     per tile of kCommitTile positions: dead rows, and the
+//                     surviving entries of each list set on the rows
+//   k_commit_carry    one block: the exclusive scan of the tiles' sums
+//   k_commit_scatter  per tile again: the scan inside the tile (per thread its
+//                     kCommitTile / kCommitThreads consecutive rows, a wave64
+//                     scan of the threads' sums by __shfl_up, the four waves'
+//                     totals through LDS, the tile's carry), then every
+//                     survivor's row and list entries into the second buffer
+//                     set at position k - dead-before(k)
+//   k_commit_off      off2[v] = off[v] - dead-before(off[v])
+// The scatter goes to a second buffer set (shifting in place would overwrite
+// rows a later thread still reads); the host swaps the handle's pointers.
+// The carry between tiles is the three-launch reduce-then-scan, not a
+// single-pass look-back: no block waits for another, so nothing depends on the
+// dispatch order or on co-residency, and the tiles' sums of a million rows
+// (977) are four passes of one block.  What the tiles read twice for it (a flag
+// byte and the lists' offsets of every row) is small beside the 104 bytes a
+// surviving row moves.
+//
+// Victims on one node: every column moves by a returnless atomic add, so the
+// order of the waves does not matter.  The last-holder rule of volume_bind
+// reads a class count before it moves it; here the move is a returning atomic
+// add of -1 on the class count, and the one wave that gets 1 back took the
+// last holding: it alone moves the family's distinct count.  The hardware
+// serializes the adds on the word, whichever nodes and waves they come from.
+__device__ __forceinline__ void volume_unbind_atomic(const DevCluster& c, const DevPods& P, const ksim_pod& p,
+                                                     int32_t node) {
+  if (!c.vol_nf) return;
+  for (int i = 0; i < p.use_count; i++) {
+    const ksim_topo_use u = P.uses[p.use_first + i];
+    if (u.kind != KSIM_USE_VOLUME || (uint32_t)u._pad >= (uint32_t)c.vol_nf) continue;   // as volume_bind
+    int32_t* att = c.vol_attached + (size_t)u._pad * c.n + node;
+    if (u.cls < 0) {
+      atomicAdd(att, -u.arg);
+      continue;
+    }
+    if (atomicAdd(c.cnt + (size_t)u.cls * c.n + node, -1) == 1) atomicAdd(att, -1);
+  }
+}
+
+__device__ __forceinline__ CommitSum operator+(const CommitSum& a, const CommitSum& b) {
+  return CommitSum{a.dead + b.dead, a.adds + b.adds, a.pids + b.pids, a.vols + b.vols};
+}
+__device__ __forceinline__ CommitSum operator-(const CommitSum& a, const CommitSum& b) {
+  return CommitSum{a.dead - b.dead, a.adds - b.adds, a.pids - b.pids, a.vols - b.vols};
+}
+
+// What position k adds to the scan: a dead row counts one, a survivor its
+// lists' lengths, the end position (k == n) and everything past it nothing.
+__device__ __forceinline__ CommitSum commit_row(const DevCommit& m, int32_t k) {
+  CommitSum s{0, 0, 0, 0};
+  if (k >= m.n) return s;
+  if (m.dead[k]) {
+    s.dead = 1;
+    return s;
+  }
+  if (m.aoff) s.adds = m.aoff[k + 1] - m.aoff[k];
+  if (m.poff) s.pids = m.poff[k + 1] - m.poff[k];
+  if (m.voff) s.vols = m.voff[k + 1] - m.voff[k];
+  return s;
+}
+
+// Exclusive scan of v over the block's kCommitThreads threads (every thread
+// calls it); total: the block's sum.  s_wave: kCommitThreads / 64 LDS words.
+__device__ __forceinline__ CommitSum commit_block_scan(const CommitSum& v, CommitSum* s_wave, CommitSum& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  CommitSum inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const CommitSum o{__shfl_up(inc.dead, d), __shfl_up(inc.adds, d), __shfl_up(inc.pids, d), __shfl_up(inc.vols, d)};
+    if (lane >= d) inc = inc + o;
+  }
+  if (lane == 63) s_wave[w] = inc;
+  __syncthreads();
+  CommitSum base{0, 0, 0, 0};
+  total = base;
+#pragma unroll
+  for (int x = 0; x < kCommitThreads / 64; x++) {
+    const CommitSum t = s_wave[x];
+    if (x < w) base = base + t;
+    total = total + t;
+  }
+  __syncthreads();                                       // s_wave is free again
+  return base + inc - v;
+}
+
+__global__ __launch_bounds__(256) void k_commit_begin(DevCommit m) {
+  const int32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k > m.n) return;
+  m.dead[k] = 0;
+  if (k < m.n) m.pos[m.index[k]] = k;
+}
+
+__global__ __launch_bounds__(64) void k_commit_evict(DevCluster c, DevCommit m, const CommitRec* __restrict__ recs) {
+  const CommitRec& r = recs[blockIdx.x];
+  const ksim_pod& p = r.P.pods[0];
+  assume_pod_wave(c, r.P, p, r.node, -1, true, nullptr, false);   // NodeInfo.RemovePod, the tables with it
+  if (threadIdx.x == 7) volume_unbind_atomic(c, r.P, p, r.node);
+  if (threadIdx.x == 63) m.dead[m.pos[r.row]] = 1;
+}
+
+// The sums of the thread's consecutive positions, and each one's own.
+__device__ __forceinline__ CommitSum commit_thread_rows(const DevCommit& m, int32_t k0,
+                                                        CommitSum (&r)[kCommitTile / kCommitThreads]) {
+  CommitSum mine{0, 0, 0, 0};
+#pragma unroll
+  for (int q = 0; q < kCommitTile / kCommitThreads; q++) {
+    r[q] = commit_row(m, k0 + q);
+    mine = mine + r[q];
+  }
+  return mine;
+}
+
+__global__ __launch_bounds__(kCommitThreads) void k_commit_sums(DevCommit m) {
+  __shared__ CommitSum s_wave[kCommitThreads / 64];
+  CommitSum r[kCommitTile / kCommitThreads], total;
+  const CommitSum mine =
+      commit_thread_rows(m, blockIdx.x * kCommitTile + (int32_t)threadIdx.x * (kCommitTile / kCommitThreads), r);
+  commit_block_scan(mine, s_wave, total);
+  if (threadIdx.x == 0) m.tile[blockIdx.x] = total;
+}
+
+// tile[t] becomes the sums of the tiles before t: one block, kCommitThreads
+// tiles a pass, the passes chained by a running carry.
+__global__ __launch_bounds__(kCommitThreads) void k_commit_carry(DevCommit m, int32_t tiles) {
+  __shared__ CommitSum s_wave[kCommitThreads / 64];
+  CommitSum carry{0, 0, 0, 0};
+  for (int32_t t0 = 0; t0 < tiles; t0 += kCommitThreads) {
+    const int32_t t = t0 + (int32_t)threadIdx.x;
+    const CommitSum v = t < tiles ? m.tile[t] : CommitSum{0, 0, 0, 0};
+    CommitSum total;
+    const CommitSum at = carry + commit_block_scan(v, s_wave, total);
+    if (t < tiles) m.tile[t] = at;
+    carry = carry + total;
+  }
+}
+
+template <class E>
+__device__ __forceinline__ void commit_list(const int32_t* off, const E* ent, int32_t* off2, E* ent2, int32_t k,
+                                            int32_t k2, int32_t at, int32_t len) {
+  if (!off) return;
+  off2[k2] = at;                                         // (the end position: len = 0, the list's new length)
+  const int32_t from = off[k];
+  for (int32_t j = 0; j < len; j++) ent2[at + j] = ent[from + j];
+}
+
+__global__ __launch_bounds__(kCommitThreads) void k_commit_scatter(DevCommit m) {
+  __shared__ CommitSum s_wave[kCommitThreads / 64];
+  CommitSum r[kCommitTile / kCommitThreads], total;
+  const int32_t k0 = blockIdx.x * kCommitTile + (int32_t)threadIdx.x * (kCommitTile / kCommitThreads);
+  const CommitSum mine = commit_thread_rows(m, k0, r);
+  CommitSum at = m.tile[blockIdx.x] + commit_block_scan(mine, s_wave, total);
+#pragma unroll
+  for (int q = 0; q < kCommitTile / kCommitThreads; q++) {
+    const int32_t k = k0 + q;
+    if (k > m.n) break;
+    m.before[k] = at.dead;
+    if (!r[q].dead) {                                    // a survivor, or the end position
+      const int32_t k2 = k - at.dead;
+      commit_list(m.aoff, m.adds, m.aoff2, m.adds2, k, k2, at.adds, r[q].adds);
+      commit_list(m.poff, m.pids, m.poff2, m.pids2, k, k2, at.pids, r[q].pids);
+      commit_list(m.voff, m.vols, m.voff2, m.vols2, k, k2, at.vols, r[q].vols);
+      if (k < m.n) {
+        m.prio2[k2] = m.prio[k];
+        m.start2[k2] = m.start[k];
+        m.index2[k2] = m.index[k];
+#pragma unroll
+        for (int x = 0; x < KSIM_PREEMPT_REQ; x++)
+          m.req2[(size_t)k2 * KSIM_PREEMPT_REQ + x] = m.req[(size_t)k * KSIM_PREEMPT_REQ + x];
+      }
+    }
+    at = at + r[q];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_commit_off(DevCommit m) {
+  const int32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v > m.n_nodes) return;
+  const int32_t o = m.off[v];
+  m.off2[v] = o - m.before[o];
+}
+
+void launch_preempt_commit(const DevCluster& c, const DevCommit& m, const CommitRec* recs, int32_t n_victims,
+                           hipStream_t stream) {
+  const int32_t tiles = commit_tiles(m.n);
+  k_commit_begin<<<m.n / 256 + 1, 256, 0, stream>>>(m);
+  k_commit_evict<<<n_victims, 64, 0, stream>>>(c, m, recs);
+  k_commit_sums<<<tiles, kCommitThreads, 0, stream>>>(m);
+  k_commit_carry<<<1, kCommitThreads, 0, stream>>>(m, tiles);
+  k_commit_scatter<<<tiles, kCommitThreads, 0, stream>>>(m);
+  k_commit_off<<<m.n_nodes / 256 + 1, 256, 0, stream>>>(m);
 }
 
 template <class FORM>

@@ -77,6 +77,14 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   h->pre = d;
   h->pre_index = ix;
   h->pre_n = n;
+  // what ksim_preempt_commit checks its rows against; its buffers went with pre_bufs and the lists
+  h->pre_row_node.assign(b->node, b->node + n);
+  h->pre_row_req.assign(b->req, b->req + (size_t)n * KSIM_PREEMPT_REQ);
+  h->pre_dead.assign((size_t)n, 0);
+  h->pre_live = n;
+  h->pre_index_stale = false;
+  h->pre_alt = DevCommit{};
+  h->pre_add_ents = h->pre_pdb_ents = h->pre_vol_ents = 0;
   h->pre_maxrow = 0;
   for (int32_t v = 0; v < N; v++) h->pre_maxrow = std::max(h->pre_maxrow, off[v + 1] - off[v]);
   return KSIM_OK;
@@ -103,16 +111,26 @@ static int bound_csr_check(ksim_handle* h, const std::string& fn, const int32_t*
 // run ends synchronized: nothing reads it) and the new one uploaded, and
 // published once the copies have read this call's vectors.  off == null only
 // clears the list.  extra: one more int32 array that goes with the list (the
-// budgets' allowed counts).
+// budgets' allowed counts).  After a ksim_preempt_commit the caller's CSR still
+// spans all its rows; the table's positions are the rows left, so an evicted
+// row's entries are passed over (the host's pre_index is compacted here, where
+// the work is O(rows) anyway).  ents: the entries uploaded; alt_off / alt_ent:
+// the commit's second buffers of this list, which go with the old ones.
 template <class E, class In, class Conv>
 static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_t* off, const In* in, Conv conv,
-                         const int32_t*& d_off, const E*& d_ent, const int32_t* extra = nullptr, size_t n_extra = 0,
-                         const int32_t** d_extra = nullptr) {
-  const int32_t n = h->pre_n;
+                         const int32_t*& d_off, const E*& d_ent, size_t& ents, int32_t*& alt_off, E*& alt_ent,
+                         const int32_t* extra = nullptr, size_t n_extra = 0, const int32_t** d_extra = nullptr) {
+  if (h->pre_index_stale) {
+    h->pre_index.erase(std::remove_if(h->pre_index.begin(), h->pre_index.end(),
+                                      [&](int32_t i) { return h->pre_dead[i] != 0; }),
+                       h->pre_index.end());
+    h->pre_index_stale = false;
+  }
+  const int32_t n = h->pre_live;
   std::vector<int32_t> poff((size_t)n + 1, 0);
   std::vector<E> perm;
   if (off) {
-    perm.reserve((size_t)(off[n] - off[0]));
+    perm.reserve((size_t)(off[h->pre_n] - off[0]));
     for (int32_t k = 0; k < n; k++) {
       const int32_t i = h->pre_index[k];
       for (int32_t e = off[i]; e < off[i + 1]; e++) perm.push_back(conv(in[e]));
@@ -123,6 +141,9 @@ static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_
   free_bufs(bufs);
   d_off = nullptr;
   d_ent = nullptr;
+  ents = 0;
+  alt_off = nullptr;
+  alt_ent = nullptr;
   if (d_extra) *d_extra = nullptr;
   if (!off) return KSIM_OK;
   const int32_t *po = nullptr, *px = nullptr;
@@ -135,6 +156,7 @@ static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
   d_off = po;
   d_ent = pe;
+  ents = perm.size();
   if (d_extra) *d_extra = px;
   return KSIM_OK;
 }
@@ -147,7 +169,7 @@ extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const
     if (adds[e].cls < 0 || adds[e].cls >= h->dc.n_classes)
       return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: class out of range");
   return bound_csr_set(h, h->pre_add_bufs, off, adds, [](const ksim_class_add& a) { return a; }, h->pre.aoff,
-                       h->pre.adds);
+                       h->pre.adds, h->pre_add_ents, h->pre_alt.aoff2, h->pre_alt.adds2);
 }
 
 extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
@@ -170,7 +192,8 @@ extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int
   }
   // n_pdbs == 0 clears: the dry run takes the forms without budgets
   return bound_csr_set(h, h->pre_pdb_bufs, n_pdbs > 0 ? off : nullptr, ids, [](int32_t id) { return id; }, h->pre.poff,
-                       h->pre.pids, allowed, (size_t)n_pdbs, &h->pre.pallowed);
+                       h->pre.pids, h->pre_pdb_ents, h->pre_alt.poff2, h->pre_alt.pids2, allowed, (size_t)n_pdbs,
+                       &h->pre.pallowed);
 }
 
 extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses) {
@@ -191,7 +214,7 @@ extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, co
   }
   return bound_csr_set(h, h->pre_vol_bufs, off, uses,
                        [](const ksim_topo_use& u) { return VolHold{u.cls, (int32_t)u.col, u.arg}; }, h->pre_voff,
-                       h->pre_vols);
+                       h->pre_vols, h->pre_vol_ents, h->pre_alt.voff2, h->pre_alt.vols2);
 }
 
 extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
@@ -424,10 +447,19 @@ static int preempt_read_back(ksim_handle* h, ksim_preempt_out* out) {
     std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
     if (off[1] > off[0])
       HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
+    // the positions' caller rows: the host's copy, or after a ksim_preempt_commit (which leaves
+    // that one uncompacted) the node's range of the device's
+    std::vector<int32_t> moved;
+    const int32_t* index = h->pre_index.data() + off[0];
+    if (h->pre_index_stale && off[1] > off[0]) {
+      moved.resize((size_t)(off[1] - off[0]));
+      HIPCHK(h, hcopy(h, moved.data(), h->pre_dindex + off[0], 4 * moved.size(), hipMemcpyDeviceToHost));
+      index = moved.data();
+    }
     int32_t k = 0;
     for (const uint8_t want : {(uint8_t)(1 | kPreemptViolating), (uint8_t)1})
       for (int32_t j = off[0]; j < off[1] && k < out->victims_cap; j++)
-        if (flag[j - off[0]] == want) out->victims[k++] = h->pre_index[j];
+        if (flag[j - off[0]] == want) out->victims[k++] = index[j - off[0]];
   }
   return KSIM_OK;
 }
@@ -669,6 +701,127 @@ extern "C" int ksim_preempt_many(ksim_handle* h, const ksim_pod_set* ps, int32_t
 extern "C" int ksim_preempt_many_dom(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* pod_index,
                                      const int32_t* priority, ksim_preempt_out* outs) {
   return preempt_many_run(h, ps, n, pod_index, priority, outs, true, "ksim_preempt_many_dom");
+}
+
+// ---- committed preemption ---------------------------------------------------------
+// The table's second buffer set and the scan's scratch, allocated at the first
+// commit after ksim_set_bound_pods (a list's second buffers: after its setter)
+// and kept until the table or the list goes.
+static int commit_buffers(ksim_handle* h) {
+  int rc;
+  DevCommit& a = h->pre_alt;
+  const size_t n = (size_t)std::max(h->pre_n, 1), N = (size_t)h->dc.n;
+  if (!a.pos &&
+      ((rc = dev_alloc(h, h->pre_bufs, a.off2, 4 * (N + 1))) || (rc = dev_alloc(h, h->pre_bufs, a.prio2, 4 * n)) ||
+       (rc = dev_alloc(h, h->pre_bufs, a.index2, 4 * n)) || (rc = dev_alloc(h, h->pre_bufs, a.start2, 8 * n)) ||
+       (rc = dev_alloc(h, h->pre_bufs, a.req2, 8 * n * KSIM_PREEMPT_REQ)) ||
+       (rc = dev_alloc(h, h->pre_bufs, a.dead, n + 1)) || (rc = dev_alloc(h, h->pre_bufs, a.before, 4 * (n + 1))) ||
+       (rc = dev_alloc(h, h->pre_bufs, a.tile, sizeof(CommitSum) * (size_t)commit_tiles(h->pre_n))) ||
+       (rc = dev_alloc(h, h->pre_bufs, a.pos, 4 * n))))   // pos last: set once the rest is there
+    return rc;
+  const size_t offs = 4 * ((size_t)h->pre_live + 1);
+  if (h->pre.aoff && !a.aoff2 &&
+      ((rc = dev_alloc(h, h->pre_add_bufs, a.adds2, sizeof(ksim_class_add) * h->pre_add_ents)) ||
+       (rc = dev_alloc(h, h->pre_add_bufs, a.aoff2, offs))))
+    return rc;
+  if (h->pre.poff && !a.poff2 && ((rc = dev_alloc(h, h->pre_pdb_bufs, a.pids2, 4 * h->pre_pdb_ents)) ||
+                                  (rc = dev_alloc(h, h->pre_pdb_bufs, a.poff2, offs))))
+    return rc;
+  if (h->pre_voff && !a.voff2 && ((rc = dev_alloc(h, h->pre_vol_bufs, a.vols2, sizeof(VolHold) * h->pre_vol_ents)) ||
+                                  (rc = dev_alloc(h, h->pre_vol_bufs, a.voff2, offs))))
+    return rc;
+  return KSIM_OK;
+}
+
+// Bound-table rows rows[0 .. n) are evicted on the device: the snapshot as
+// ksim_forget of pods[pod_index[i]] on each row's node leaves it, and the
+// table, with the lists set on its rows, compacted to the rows left (their
+// order and their numbers kept).  Everything is validated first; the host does
+// O(n) work, the device passes are over the table (launch_preempt_commit), and
+// the call ends with its one synchronization.
+extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32_t n, const int32_t* rows,
+                                   const int32_t* pod_index) {
+  if (!h) return KSIM_E_INVALID;
+  if (n < 0) return set_err(h, KSIM_E_INVALID, "ksim_preempt_commit: negative row count");
+  if (n == 0) return KSIM_OK;
+  if (!ps || !ps->pods || !rows || !pod_index) return set_err(h, KSIM_E_INVALID, "ksim_preempt_commit: null argument");
+  int rc = ensure_ready(h);
+  if (rc) return rc;
+  if (is_sharded(h) || h->replicated)
+    return set_err(h, KSIM_E_UNSUPPORTED, "ksim_preempt_commit: preemption runs on unsharded handles");
+  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_preempt_commit: ksim_set_bound_pods first");
+  // pre_dead[row] = 2 while this call names the row; the guard takes the marks back unless the call ran
+  int32_t marked = 0;
+  bool ran = false;
+  struct Marks {
+    ksim_handle* h;
+    const int32_t* rows;
+    const int32_t& marked;
+    const bool& ran;
+    ~Marks() {
+      for (int32_t i = 0; i < marked; i++) h->pre_dead[rows[i]] = ran ? 1 : 0;
+    }
+  } marks{h, rows, marked, ran};
+  for (int32_t i = 0; i < n; i++) {
+    const std::string at = "ksim_preempt_commit entry " + std::to_string(i) + ": ";
+    const int32_t r = rows[i], j = pod_index[i];
+    if (r < 0 || r >= h->pre_n) return set_err(h, KSIM_E_INVALID, at + "row outside the bound-pod table");
+    if (h->pre_dead[r] == 1) return set_err(h, KSIM_E_INVALID, at + "row already evicted");
+    if (h->pre_dead[r] == 2) return set_err(h, KSIM_E_INVALID, at + "row named twice");
+    if (j < 0 || j >= ps->n_pods) return set_err(h, KSIM_E_INVALID, at + "pod index outside the pod set");
+    if ((rc = validate_pod(h, ps, j))) {
+      h->err = at + h->err;
+      return rc;
+    }
+    const ksim_pod& p = ps->pods[j];
+    const int64_t* q = h->pre_row_req.data() + (size_t)r * KSIM_PREEMPT_REQ;
+    bool same = p.req_cpu == q[0] && p.req_mem == q[1] && p.req_eph == q[2];
+    for (int c = 0; c < KSIM_MAX_SCALAR; c++) same = same && p.scalar_req[c] == q[3 + c];
+    if (!same) return set_err(h, KSIM_E_INVALID, at + "the pod's requests differ from the row's");
+    h->pre_dead[r] = 2;
+    marked = i + 1;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if ((rc = commit_buffers(h))) return rc;
+  std::vector<DevPods> Ps;
+  char *thost = nullptr, *tdev = nullptr;
+  if ((rc = upload_many(h, ps, pod_index, n, sizeof(CommitRec) * (size_t)n, Ps, &thost, &tdev))) return rc;
+  CommitRec* recs = (CommitRec*)thost;
+  for (int32_t i = 0; i < n; i++) recs[i] = CommitRec{Ps[i], rows[i], h->pre_row_node[rows[i]]};
+  if ((rc = upload_many_commit(h))) return rc;
+  DevPreempt& t = h->pre;
+  DevCommit& a = h->pre_alt;
+  DevCommit m = a;                               // the second set and the scratch; then the table as it is
+  m.n = h->pre_live;
+  m.n_nodes = h->dc.n;
+  m.off = t.off, m.prio = t.prio, m.index = h->pre_dindex, m.start = t.start, m.req = t.req;
+  m.aoff = t.aoff, m.adds = t.adds;
+  m.poff = t.poff, m.pids = t.pids;
+  m.voff = h->pre_voff, m.vols = h->pre_vols;
+  launch_preempt_commit(h->dc, m, (const CommitRec*)tdev, n, h->stream);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));    // the staging is the next call's to write
+  // the sets swap: the survivors' is the table now, the old one the next commit's target
+  a.off2 = const_cast<int32_t*>(m.off), a.prio2 = const_cast<int32_t*>(m.prio);
+  a.index2 = const_cast<int32_t*>(m.index), a.start2 = const_cast<int64_t*>(m.start);
+  a.req2 = const_cast<int64_t*>(m.req);
+  t.off = m.off2, t.prio = m.prio2, h->pre_dindex = m.index2, t.start = m.start2, t.req = m.req2;
+  if (m.aoff) {
+    a.aoff2 = const_cast<int32_t*>(m.aoff), a.adds2 = const_cast<ksim_class_add*>(m.adds);
+    t.aoff = m.aoff2, t.adds = m.adds2;
+  }
+  if (m.poff) {
+    a.poff2 = const_cast<int32_t*>(m.poff), a.pids2 = const_cast<int32_t*>(m.pids);
+    t.poff = m.poff2, t.pids = m.pids2;
+  }
+  if (m.voff) {
+    a.voff2 = const_cast<int32_t*>(m.voff), a.vols2 = const_cast<VolHold*>(m.vols);
+    h->pre_voff = m.voff2, h->pre_vols = m.vols2;
+  }
+  h->pre_live -= n;
+  h->pre_index_stale = true;
+  ran = true;
+  return KSIM_OK;
 }
 
 // ---- selector / affinity-term matching (ksim_match.hip) ------

@@ -618,6 +618,8 @@ int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* fa
   free_bufs(h->pre_vol_bufs);           // the bound pods' holdings named the old table's families
   h->pre_voff = nullptr;
   h->pre_vols = nullptr;
+  h->pre_alt.voff2 = nullptr;           // (ksim_preempt_commit's second set of them went with the buffers)
+  h->pre_alt.vols2 = nullptr;
   h->vol_init = nullptr;
   h->dc.vol_nf = 0;
   h->dc.vol_plug = 0;

@@ -34,6 +34,7 @@ EXPORTS = [
     "ksim_fw_filter_nominated", "ksim_preempt_nominated", "ksim_preempt_spread",
     "ksim_set_bound_pod_volumes", "ksim_preempt_volumes", "ksim_preempt_full",
     "ksim_preempt_many", "ksim_preempt_many_rows", "ksim_preempt_many_dom", "ksim_preempt_many_dom_rows",
+    "ksim_preempt_commit",
     "ksim_encoder_create", "ksim_encoder_destroy", "ksim_encoder_last_error", "ksim_encode_nodes",
     "ksim_encode_pods", "ksim_encoder_cluster", "ksim_encoder_pods", "ksim_encoder_get_info",
     "ksim_encoder_node_order", "ksim_encoder_string", "ksim_encoder_update_nodes", "ksim_encoder_old_pos",
@@ -135,6 +136,8 @@ def _load(path):
         L.ksim_preempt_many_dom.argtypes = [vp, vp, i32, vp, vp, vp]
         L.ksim_preempt_many_dom_rows.argtypes = [i32, i32, i32]
         L.ksim_preempt_many_dom_rows.restype = i32
+    if hasattr(L, "ksim_preempt_commit"):       # likewise
+        L.ksim_preempt_commit.argtypes = [vp, vp, i32, vp, vp]
     L.ksim_eval_pod_finish.argtypes = [vp, vp, vp, vp]
     L.ksim_match_terms.argtypes = [vp, vp, vp, vp]
     L.ksim_set_eval_range.argtypes = [vp, i32, i32]
@@ -578,6 +581,28 @@ class Engine:
             for i, o in enumerate(outs):
                 ctypes.memmove(ctypes.byref(o.c), ctypes.byref(arr[i]), ctypes.sizeof(abi._PreemptOutC))
         return [o.result_with_pdb() if with_pdb else o.result() for o in outs]
+
+    def preempt_commit(self, pods, rows, indices):
+        """ksim_preempt_commit: the bound-table rows ``rows`` (the caller's row
+        numbers of the last set_bound_pods, as ``preempt`` reports its victims)
+        are evicted on the device.  ``pods[indices[i]]`` is the record of the
+        pod bound at ``rows[i]``, as ``forget`` takes it.  Afterwards the
+        snapshot is what ``forget`` of each of them on its row's node leaves,
+        and the table holds the surviving rows, in their order and under their
+        numbers, with the lists set on them; nothing is uploaded again.  The
+        setters keep taking arrays over all the rows set_bound_pods was given.
+        ``ksim.preemption.commit_args`` builds the two arrays from a dry
+        run's answer."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        indices = np.ascontiguousarray(indices, np.int32)
+        if rows.shape != indices.shape or rows.ndim != 1:
+            raise ValueError("one pod index per row")
+        self._sync()
+        self._ran = True
+        ps = pods.pod_set()
+        self._chk(self.L.ksim_preempt_commit(self.h, ctypes.byref(ps), int(rows.size),
+                                             rows.ctypes.data_as(ctypes.c_void_p),
+                                             indices.ctypes.data_as(ctypes.c_void_p)))
 
     def match_terms(self, mp: abi.MatchProblem, n_words: int, counts: Optional[np.ndarray]) -> np.ndarray:
         """ksim_match_terms: [n_sigs][n_words] matcher bits; ``counts``

@@ -31,6 +31,20 @@ def pdb_matches(rows: Sequence[Pod], pdbs: Sequence[PodDisruptionBudget]) -> Lis
     return out
 
 
+COMMIT_TILE = 1024   # rows per scan tile of ksim_preempt_commit's compaction (csrc kCommitTile)
+
+
+def commit_args(answer, row_pod):
+    """A dry run's answer (``Engine.preempt`` / ``preempt_many``: nominated node,
+    victims, ...) as ``Engine.preempt_commit``'s arrays: the victims' rows of the
+    bound table, and per row the index of that bound pod's record in the pod
+    set handed to the commit.  ``row_pod``: that index per row of
+    ``bound_table`` (a sequence or a mapping; the table's rows are the bound
+    pods on the cluster's nodes, in list order).  No nominated node: empty arrays."""
+    victims = [int(r) for r in answer[1]] if answer[0] >= 0 else []
+    return np.array(victims, np.int32), np.array([row_pod[r] for r in victims], np.int32)
+
+
 def bound_table(cluster, bound: Sequence[Pod], start_time: Dict[str, int], topo=None,
                 full_adds: bool = False, pdbs: Optional[Sequence[PodDisruptionBudget]] = None,
                 vol_limits=None) -> abi.BoundPods:
