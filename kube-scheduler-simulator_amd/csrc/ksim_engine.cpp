@@ -94,19 +94,16 @@ static hipError_t hzero(ksim_handle* h, void* dst, size_t bytes) {
   return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
 }
 
-void free_bufs(std::vector<DevBuf>& v) {
-  for (auto& b : v)
-    if (b.p) (void)hipFree(b.p);
-  v.clear();
-}
+}  // namespace ksim_host
 
+// ---- ksim_mem.h: the calls that allocate ---------------------------------------
 // Allocate + copy (src may be null: zero-filled).
-int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t bytes, void** out) {
+int DevPool::upload(ksim_handle* h, const void* src, size_t bytes, void** out) {
   void* p = nullptr;
   size_t alloc = bytes ? bytes : 16;
   hipError_t e = hipMalloc(&p, alloc);
   if (e != hipSuccess) return hip_fail(h, e, "hipMalloc");
-  owner.push_back({p, alloc});
+  v_.push_back({p, alloc});
   if (src && bytes) {
     e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream);
   } else {
@@ -117,7 +114,40 @@ int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t b
   return KSIM_OK;
 }
 
-}  // namespace ksim_host
+// The reserve rule is ksim_mem.h's (Idle); a failed allocation leaves the buffer empty.
+int DevGrow::reserve(ksim_handle* h, size_t bytes, Idle idle) {
+  if (bytes <= cap) return KSIM_OK;
+  if (idle == Idle::kSync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const size_t want = floor_ ? std::max(bytes * 2, floor_) : std::max<size_t>(bytes, 16);
+  const hipError_t e = hipMalloc(&p, want);
+  if (e != hipSuccess) {
+    p = nullptr;
+    return hip_fail(h, e, what_);
+  }
+  cap = want;
+  return KSIM_OK;
+}
+
+int PinGrow::reserve(ksim_handle* h, size_t bytes, Idle idle) {
+  if (bytes <= cap) return KSIM_OK;
+  if (idle == Idle::kSync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (p) (void)hipHostFree(p);
+  p = d = nullptr;
+  cap = 0;
+  const size_t want = floor_ ? std::max(bytes * 2, floor_) : std::max<size_t>(bytes, 16);
+  hipError_t e = hipHostMalloc(&p, want, flags_);
+  if (e != hipSuccess) {
+    p = nullptr;
+    return hip_fail(h, e, what_);
+  }
+  if ((flags_ & hipHostMallocMapped) && (e = hipHostGetDevicePointer(&d, p, 0)) != hipSuccess)
+    return hip_fail(h, e, "hipHostGetDevicePointer");   // cap stays 0: the next reserve starts over
+  cap = want;
+  return KSIM_OK;
+}
 
 namespace {
 
@@ -158,47 +188,12 @@ void drop_graphs(ksim_handle* h) {
 // The loaded queue, with everything compiled against the rows it was loaded
 // on (its buffers are not kept for reuse: ksim_set_profile's narrower form is).
 void drop_loaded_pods(ksim_handle* h) {
-  free_bufs(h->pod_bufs);
+  h->pod_bufs.clear();
   h->pod_buf_bytes.clear();
+  h->d_chosen = nullptr;
   h->dp = DevPods{};
   h->batchable.clear();
   h->topo.clear();
-}
-
-// The bound-pod table (ksim_set_bound_pods) and every list set on its rows.
-void drop_bound_pods(ksim_handle* h) {
-  free_bufs(h->pre_bufs);
-  free_bufs(h->pre_nom_bufs);
-  free_bufs(h->pre_add_bufs);
-  free_bufs(h->pre_pdb_bufs);
-  free_bufs(h->pre_vol_bufs);
-  drop_many_slabs(h);
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  h->pre = DevPreempt{};
-  h->pre_index.clear();
-  h->pre_dindex = nullptr;
-  h->pre_maxrow = 0;
-  h->pre_n = 0;
-  h->pre_row_node.clear();              // what ksim_preempt_commit keeps of the table
-  h->pre_row_req.clear();
-  h->pre_dead.clear();
-  h->pre_live = 0;
-  h->pre_index_stale = false;
-  h->pre_alt = DevCommit{};
-  h->pre_add_ents = h->pre_pdb_ents = h->pre_vol_ents = 0;
-}
-
-// ksim_preempt_many's per-row slabs: sized by the bound table, so they go with it.
-void drop_many_slabs(ksim_handle* h) {
-  free_bufs(h->many_bufs);
-  h->many_res = nullptr;
-  h->many_vflag = nullptr;
-  h->many_slab_rows = 0;
-  free_bufs(h->many_dom_bufs);                 // ksim_preempt_many_dom's tables: sized by the cluster's vmax
-  h->many_dom = nullptr;
-  h->many_heads = nullptr;
-  h->many_dom_rows = 0;
 }
 
 bool is_sharded(const ksim_handle* h) { return h->comm != nullptr || h->shard_total != 0; }
@@ -406,10 +401,10 @@ int ensure_stab(ksim_handle* h) {
   if (h->stab_bytes < 8 * entries) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     drop_graphs(h);
-    free_bufs(h->stab_bufs);
+    h->stab_bufs.clear();
     h->stab_bytes = 0;
     void* p = nullptr;
-    if (const int rc = dev_alloc(h, h->stab_bufs, p, 8 * entries)) return rc;
+    if (const int rc = h->stab_bufs.alloc(h, p, 8 * entries)) return rc;
     h->stab_bytes = 8 * entries;
   } else if (!was_ready) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -788,36 +783,29 @@ int sync_one_cut(ksim_handle* h) {
 
 int alloc_lazy(ksim_handle* h) {
   if (int rc = sync_one_cut(h)) return rc;
-  if (h->lazy_n == h->dc.n) return KSIM_OK;
+  if (h->lazy.n == h->dc.n) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_graphs_if(h, is_lazy);
-  free_bufs(h->lazy_bufs);
-  h->lazy_n = -1;
-  if (!h->prog) {   // kept for the handle's life: the graphs hold its address
-    hipError_t e = hipHostMalloc((void**)&h->prog, 2 * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped);
-    if (e != hipSuccess) {
-      h->prog = nullptr;
-      return hip_fail(h, e, "hipHostMalloc (progress word)");
-    }
-    h->prog[0] = h->prog[1] = 0;
-    if ((e = hipHostGetDevicePointer((void**)&h->prog_d, h->prog, 0)) != hipSuccess)
-      return hip_fail(h, e, "hipHostGetDevicePointer");
+  h->lazy = LazyBufs{};
+  if (!h->prog.p) {   // reserved once, at one size: the graphs hold its address (the stream is idle, above)
+    if (const int rc = h->prog.reserve(h, 2 * sizeof(unsigned long long), Idle::kCaller)) return rc;
+    std::memset(h->prog.p, 0, 2 * sizeof(unsigned long long));
   }
   const size_t n = (size_t)h->dc.n;
   int rc;
-  int64_t** cols[5] = {&h->lazy_x1.req_cpu, &h->lazy_x1.req_mem, &h->lazy_x1.req_eph, &h->lazy_x1.nz_cpu,
-                       &h->lazy_x1.nz_mem};
+  int64_t** cols[5] = {&h->lazy.x1.req_cpu, &h->lazy.x1.req_mem, &h->lazy.x1.req_eph, &h->lazy.x1.nz_cpu,
+                       &h->lazy.x1.nz_mem};
   for (auto* c : cols)
-    if ((rc = dev_alloc(h, h->lazy_bufs, *c, 8 * n))) return rc;
-  if ((rc = dev_alloc(h, h->lazy_bufs, h->lazy_x1.num_pods, 4 * n)) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_st1, sizeof(DevState))) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_g, 8 * (size_t)kLazySlots * kBatchPods)) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_m, 8 * (size_t)kLazySlots * kBatchPods)) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_e, 4 * (size_t)kLazySlots)) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_ab, 4 * (size_t)kLazySlots * kBatchPods)) ||
-      (rc = dev_alloc(h, h->lazy_bufs, h->lazy_aw, 8 * (size_t)kLazySlots * kBatchPods)))
+    if ((rc = h->lazy.bufs.alloc(h, *c, 8 * n))) return rc;
+  if ((rc = h->lazy.bufs.alloc(h, h->lazy.x1.num_pods, 4 * n)) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.st1, sizeof(DevState))) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.g, 8 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.m, 8 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.e, 4 * (size_t)kLazySlots)) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.ab, 4 * (size_t)kLazySlots * kBatchPods)) ||
+      (rc = h->lazy.bufs.alloc(h, h->lazy.aw, 8 * (size_t)kLazySlots * kBatchPods)))
     return rc;
-  h->lazy_n = h->dc.n;
+  h->lazy.n = h->dc.n;
   return KSIM_OK;
 }
 
@@ -900,10 +888,10 @@ int ensure_rtab(ksim_handle* h) {
   if (h->rtab_bytes >= need && !h->rtab_bufs.empty()) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_graphs_if(h, is_table);
-  free_bufs(h->rtab_bufs);
+  h->rtab_bufs.clear();
   h->rtab_bytes = 0;
   void* p = nullptr;
-  if (const int rc = dev_alloc(h, h->rtab_bufs, p, need)) return rc;
+  if (const int rc = h->rtab_bufs.alloc(h, p, need)) return rc;
   h->rtab_bytes = need;
   return KSIM_OK;
 }
@@ -912,8 +900,8 @@ int ensure_rtab(ksim_handle* h) {
 // request-class table, ensure_rtab done).
 LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool rt = false) {
   const int p = (int)(i & 1), q = (int)(i & 3), q1 = (int)((i + 3) & 3), q2 = (int)((i + 2) & 3);
-  const DynCols x[2] = {dyn_cols(h->dc), h->lazy_x1};
-  DevState* st[2] = {h->st, h->lazy_st1};
+  const DynCols x[2] = {dyn_cols(h->dc), h->lazy.x1};
+  DevState* st[2] = {h->st, h->lazy.st1};
   LazyBatch z;
   z.a = la;
   z.a.c = with_cols(la.c, x[p ^ 1]);
@@ -921,22 +909,22 @@ LazyBatch lazy_batch(const ksim_handle* h, const LaunchArgs& la, int64_t i, bool
   z.step.w = x[p];
   z.step.st_in = st[p ^ 1];
   z.step.st_out = st[p];
-  z.step.g1 = h->lazy_g + (size_t)q1 * kBatchPods;
-  z.step.m1 = h->lazy_m + (size_t)q1 * kBatchPods;
-  z.step.e1 = h->lazy_e + q1;
-  z.step.g2 = h->lazy_g + (size_t)q2 * kBatchPods;
-  z.step.e2 = h->lazy_e + q2;
-  z.step.e_self = h->lazy_e + q;
-  z.step.prog = h->prog_d;
+  z.step.g1 = h->lazy.g + (size_t)q1 * kBatchPods;
+  z.step.m1 = h->lazy.m + (size_t)q1 * kBatchPods;
+  z.step.e1 = h->lazy.e + q1;
+  z.step.g2 = h->lazy.g + (size_t)q2 * kBatchPods;
+  z.step.e2 = h->lazy.e + q2;
+  z.step.e_self = h->lazy.e + q;
+  z.step.prog = (unsigned long long*)h->prog.d;
   z.step.one_cut = h->one_cut ? 1 : 0;
   z.st = st[p];
-  z.gkey = h->lazy_g + (size_t)q * kBatchPods;
-  z.pmax = h->lazy_m + (size_t)q * kBatchPods;
-  z.cend = h->lazy_e + q;
-  z.b1 = h->lazy_ab + (size_t)q1 * kBatchPods;
-  z.w1 = h->lazy_aw + (size_t)q1 * 2 * kBatchPods;
-  z.abroken = h->lazy_ab + (size_t)q * kBatchPods;
-  z.awin = h->lazy_aw + (size_t)q * 2 * kBatchPods;
+  z.gkey = h->lazy.g + (size_t)q * kBatchPods;
+  z.pmax = h->lazy.m + (size_t)q * kBatchPods;
+  z.cend = h->lazy.e + q;
+  z.b1 = h->lazy.ab + (size_t)q1 * kBatchPods;
+  z.w1 = h->lazy.aw + (size_t)q1 * 2 * kBatchPods;
+  z.abroken = h->lazy.ab + (size_t)q * kBatchPods;
+  z.awin = h->lazy.aw + (size_t)q * 2 * kBatchPods;
   if (rt) {
     uint16_t* const t = (uint16_t*)h->rtab_bufs[0].p;
     const size_t half = (size_t)h->rq_ncls * (size_t)h->dc.n;
@@ -965,15 +953,15 @@ int lazy_begin(ksim_handle* h) {
   int rc;
   if ((rc = alloc_lazy(h))) return rc;
   const size_t n = (size_t)h->dc.n;
-  const DynCols x0 = dyn_cols(h->dc), x1 = h->lazy_x1;
+  const DynCols x0 = dyn_cols(h->dc), x1 = h->lazy.x1;
   HIPCHK(h, hipMemcpyAsync(x1.req_cpu, x0.req_cpu, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x1.req_mem, x0.req_mem, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x1.req_eph, x0.req_eph, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x1.nz_cpu, x0.nz_cpu, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x1.nz_mem, x0.nz_mem, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x1.num_pods, x0.num_pods, 4 * n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->lazy_st1, h->st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->lazy_e, 0xff, 4 * kLazySlots, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->lazy.st1, h->st, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->lazy.e, 0xff, 4 * kLazySlots, h->stream));
   return KSIM_OK;
 }
 
@@ -982,14 +970,14 @@ int lazy_begin(ksim_handle* h) {
 int lazy_end(ksim_handle* h, int64_t f) {
   if ((f & 1) == 0) return KSIM_OK;
   const size_t n = (size_t)h->dc.n;
-  const DynCols x0 = dyn_cols(h->dc), x1 = h->lazy_x1;
+  const DynCols x0 = dyn_cols(h->dc), x1 = h->lazy.x1;
   HIPCHK(h, hipMemcpyAsync(x0.req_cpu, x1.req_cpu, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x0.req_mem, x1.req_mem, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x0.req_eph, x1.req_eph, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x0.nz_cpu, x1.nz_cpu, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x0.nz_mem, x1.nz_mem, 8 * n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(x0.num_pods, x1.num_pods, 4 * n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->st, h->lazy_st1, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->st, h->lazy.st1, sizeof(DevState), hipMemcpyDeviceToDevice, h->stream));
   return KSIM_OK;
 }
 
@@ -1027,7 +1015,7 @@ int lazy_begin_run(ksim_handle* h, int32_t first, int32_t end, bool zero_counter
   h->run_hdr[1] = end;
   LazyMove m{};
   m.src = dyn_cols(h->dc);
-  m.dst = h->lazy_x1;
+  m.dst = h->lazy.x1;
   m.n = h->dc.n;
   m.begin = 1;
   m.zero_counters = zero_counters ? 1 : 0;
@@ -1035,10 +1023,10 @@ int lazy_begin_run(ksim_handle* h, int32_t first, int32_t end, bool zero_counter
   m.end = end;
   m.st_src = h->st;
   m.st_dst = h->st;
-  m.st_dst2 = h->lazy_st1;
+  m.st_dst2 = h->lazy.st1;
   m.win = h->sc.win;
-  m.ring_e = h->lazy_e;
-  m.batches0 = h->prog_d + 1;
+  m.ring_e = h->lazy.e;
+  m.batches0 = (unsigned long long*)h->prog.d + 1;
   launch_lazy_move(m, h->stream);
   HIPCHK(h, hipGetLastError());
   return KSIM_OK;
@@ -1048,10 +1036,10 @@ int lazy_begin_run(ksim_handle* h, int32_t first, int32_t end, bool zero_counter
 int lazy_end_run(ksim_handle* h, int64_t f) {
   if ((f & 1) == 0) return KSIM_OK;
   LazyMove m{};
-  m.src = h->lazy_x1;
+  m.src = h->lazy.x1;
   m.dst = dyn_cols(h->dc);
   m.n = h->dc.n;
-  m.st_src = h->lazy_st1;
+  m.st_src = h->lazy.st1;
   m.st_dst = h->st;
   launch_lazy_move(m, h->stream);
   HIPCHK(h, hipGetLastError());
@@ -1079,7 +1067,7 @@ bool feed_flush_forced() {
 int run_lazy(ksim_handle* h, int32_t a, int32_t b, const RunPlan& plan, const LaunchArgs& la, bool zero_counters) {
   int rc;
   if ((rc = alloc_lazy(h))) return rc;
-  volatile unsigned long long* const word = h->prog;
+  volatile unsigned long long* const word = (unsigned long long*)h->prog.p;
   constexpr unsigned long long kNoWord = ~0ull;     // no cursor is -1
   word[0] = kNoWord;                                // nothing in flight writes it: every run ends waited for
   if ((rc = lazy_begin_run(h, a, b, zero_counters))) return rc;
@@ -1183,7 +1171,7 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const RunPlan& plan, const La
       lazy_flush(h, lazy_batch(h, la, i, rt), h->stream);
       HIPCHK(h, hipGetLastError());
       DevState st;
-      if ((rc = read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st))) return rc;
+      if ((rc = read_state_at(h, (i & 1) ? h->lazy.st1 : h->st, st))) return rc;
       h->feed_syncs++;
       h->feed_fallbacks++;
       i++;
@@ -1206,16 +1194,11 @@ int run_lazy(ksim_handle* h, int32_t a, int32_t b, const RunPlan& plan, const La
 // 16-byte words), zero-filled; sized by (dc.n, lanes) and kept with the handle.
 int alloc_sweep(ksim_handle* h, int32_t lanes) {
   if (int rc = sync_one_cut(h)) return rc;
-  if (!h->sweep_tab) {                              // its address is what the sweep graphs hold: allocated once
-    void* t = nullptr;
-    hipError_t e = hipMalloc(&t, sizeof(SweepLane) * kLazySlots * kSweepMaxLanes);
-    if (e != hipSuccess) return hip_fail(h, e, "hipMalloc");
-    h->sweep_tab = (SweepLane*)t;
-  }
+  if (!h->sweep_tab)                                // its address is what the sweep graphs hold: allocated once
+    if (const int rc = h->life_bufs.alloc(h, h->sweep_tab, sizeof(SweepLane) * kLazySlots * kSweepMaxLanes)) return rc;
   if (h->sweep_n == h->dc.n && lanes <= h->sweep_lanes) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->sweep_slab) (void)hipFree(h->sweep_slab);
-  h->sweep_slab = nullptr;
+  h->sweep_slab.clear();
   h->sweep_n = -1;
   h->sweep_lanes = 0;
   h->sweep_lane.clear();
@@ -1243,15 +1226,8 @@ int alloc_sweep(ksim_handle* h, int32_t lanes) {
     o.pnorm = take(8 * (size_t)kBatchPods * 4);
     o.pinv = take(4 * (size_t)kBatchPods);
   }
-  void* slab = nullptr;
-  hipError_t e = hipMalloc(&slab, off);
-  if (e != hipSuccess) return hip_fail(h, e, "hipMalloc");
-  if ((e = hipMemsetAsync(slab, 0, off, h->stream)) != hipSuccess) {
-    (void)hipFree(slab);
-    return hip_fail(h, e, "hipMemsetAsync");
-  }
-  char* base = (char*)slab;
-  h->sweep_slab = slab;
+  char* base = nullptr;
+  if (const int rc = h->sweep_slab.alloc(h, base, off)) return rc;
   h->sweep_st = (DevState*)(base + st_off);
   for (const auto& o : offs) {
     ksim_handle::SweepLaneBufs b{};
@@ -1270,22 +1246,6 @@ int alloc_sweep(ksim_handle* h, int32_t lanes) {
   }
   h->sweep_n = h->dc.n;
   h->sweep_lanes = lanes;
-  return KSIM_OK;
-}
-
-// A grow-only device buffer of at least `bytes` (the stream idle: nothing reads the old one).
-int sweep_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
-  if (a.cap >= bytes && a.p) return KSIM_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (a.p) (void)hipFree(a.p);
-  a.p = nullptr;
-  a.cap = 0;
-  const hipError_t e = hipMalloc(&a.p, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    a.p = nullptr;
-    return hip_fail(h, e, "hipMalloc");
-  }
-  a.cap = bytes ? bytes : 16;
   return KSIM_OK;
 }
 
@@ -1336,7 +1296,7 @@ int run_sweep(ksim_handle* h, int32_t a, int32_t b, int32_t n_profs, int32_t lan
   int rc;
   if ((rc = alloc_sweep(h, lanes))) return rc;
   const int32_t np = h->dp.n_pods, count = b - a;
-  if ((rc = sweep_reserve(h, h->sweep_rows, 4 * (size_t)lanes * (size_t)std::max(np, 1)))) return rc;
+  if ((rc = h->sweep_rows.reserve(h, 4 * (size_t)lanes * (size_t)std::max(np, 1), Idle::kSync))) return rc;
   int32_t* rows = (int32_t*)h->sweep_rows.p;
   LaunchArgs la = make_args(h, h->dp, nullptr);
   const DevCluster c = la.c;
@@ -1757,7 +1717,7 @@ int shard_run_lazy(const Group& g, int32_t a, int32_t b) {
     for (auto* h : g.hs) launch_lazy_flush(lazy_batch(h, shard_args(h, true), i), stream);
     HIPCHK(h0, hipGetLastError());
     DevState st;
-    HIPCHK(h0, hipMemcpyAsync(&st, (i & 1) ? h0->lazy_st1 : h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
+    HIPCHK(h0, hipMemcpyAsync(&st, (i & 1) ? h0->lazy.st1 : h0->st, sizeof(st), hipMemcpyDeviceToHost, stream));
     HIPCHK(h0, hipStreamSynchronize(stream));
     if (st.cursor <= cursor) return set_err(h0, KSIM_E_DEVICE, "replicated deferred-commit batches made no progress");
     cursor = st.cursor;
@@ -1884,18 +1844,18 @@ bool adapt_shard_layout(const Group& g) {
 }
 
 int adapt_shard_buffers(ksim_handle* h, int32_t world, int32_t W) {
-  if (h->ash_world == world && h->ash_w == W) return KSIM_OK;
+  if (h->ash.world == world && h->ash.w == W) return KSIM_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   drop_cycle_graphs(h);                           // shard batch graphs captured over the old buffers
-  free_bufs(h->ash_bufs);
+  h->ash = AshBufs{};
   const size_t nw = (size_t)(h->dc.n_total + 63) / 64;
   int rc;
-  if ((rc = dev_alloc(h, h->ash_bufs, h->ash_send, 8 * (size_t)kBatchPods * W)) ||
-      (rc = dev_alloc(h, h->ash_bufs, h->ash_recv, 8 * (size_t)world * kBatchPods * W)) ||
-      (rc = dev_alloc(h, h->ash_bufs, h->ash_gmask, 8 * (size_t)kBatchPods * nw)))
+  if ((rc = h->ash.bufs.alloc(h, h->ash.send, 8 * (size_t)kBatchPods * W)) ||
+      (rc = h->ash.bufs.alloc(h, h->ash.recv, 8 * (size_t)world * kBatchPods * W)) ||
+      (rc = h->ash.bufs.alloc(h, h->ash.gmask, 8 * (size_t)kBatchPods * nw)))
     return rc;
-  h->ash_world = world;
-  h->ash_w = W;
+  h->ash.world = world;
+  h->ash.w = W;
   return KSIM_OK;
 }
 
@@ -1903,13 +1863,13 @@ int adapt_shard_buffers(ksim_handle* h, int32_t world, int32_t W) {
 // pod, records, M).
 int shard_batch_adapt(const Group& g, int32_t W, bool fast) {
   int rc;
-  for (auto* h : g.hs) launch_adapt_sh_mask(shard_args(h, fast), h->ash_send, W, g.stream);
-  if ((rc = group_all_gather(g, [](ksim_handle* h) { return h->ash_send; },
-                             [](ksim_handle* h) { return h->ash_recv; }, (size_t)kBatchPods * W)))
+  for (auto* h : g.hs) launch_adapt_sh_mask(shard_args(h, fast), h->ash.send, W, g.stream);
+  if ((rc = group_all_gather(g, [](ksim_handle* h) { return h->ash.send; },
+                             [](ksim_handle* h) { return h->ash.recv; }, (size_t)kBatchPods * W)))
     return rc;
-  for (auto* h : g.hs) launch_adapt_sh_window(shard_args(h, fast), h->ash_recv, W, h->ash_gmask, g.stream);
+  for (auto* h : g.hs) launch_adapt_sh_window(shard_args(h, fast), h->ash.recv, W, h->ash.gmask, g.stream);
   if ((rc = group_all_gather(g, sc_xsend, sc_xrecv, (size_t)kBatchPods * kXRec))) return rc;
-  for (auto* h : g.hs) launch_adapt_sh_pairs(shard_args(h, fast), h->ash_gmask, g.world, g.stream);
+  for (auto* h : g.hs) launch_adapt_sh_pairs(shard_args(h, fast), h->ash.gmask, g.world, g.stream);
   if ((rc = group_all_reduce(g, sc_pmax, 2 * kBatchPods, true))) return rc;
   for (auto* h : g.hs) launch_adapt_sh_commit(shard_args(h, fast), g.stream);
   HIPCHK(g.h0, hipGetLastError());
@@ -2013,64 +1973,30 @@ int ksim_create(int device, ksim_handle** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return KSIM_E_DEVICE;
   if (device < 0 || device >= ndev) return KSIM_E_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return KSIM_E_DEVICE;
   auto* h = new ksim_handle();
   h->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-      hipMalloc(&h->st, sizeof(DevState)) != hipSuccess || hipMemset(h->st, 0, sizeof(DevState)) != hipSuccess ||
-      // written only by ksim_set_profile, on the engine's stream (a null-stream
-      // memset here would not be ordered before that copy)
-      hipMalloc(&h->d_prof, sizeof(ksim_profile)) != hipSuccess ||
-      hipMalloc(&h->d_bp, sizeof(BatchProg)) != hipSuccess) {
-    delete h;
+  // d_prof / d_bp are written only by ksim_set_profile, on the engine's stream
+  // (like the zero fill here); st is zero before any stream reads it
+  if (hipStreamCreateWithFlags(h->stream.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreate(h->ev0.out()) != hipSuccess || hipEventCreate(h->ev1.out()) != hipSuccess ||
+      h->life_bufs.alloc(h, h->st, sizeof(DevState)) || h->life_bufs.alloc(h, h->d_prof, sizeof(ksim_profile)) ||
+      h->life_bufs.alloc(h, h->d_bp, sizeof(BatchProg)) || hipStreamSynchronize(h->stream) != hipSuccess) {
+    delete h;                                      // on its device (set above): releases what was made
     return KSIM_E_DEVICE;
   }
   *out = h;
   return KSIM_OK;
 }
 
+// Everything the handle owns goes in its members' destructors (ksim_mem.h), on
+// the handle's device, the stream drained first.
 void ksim_destroy(ksim_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   drop_graphs(h);
   if (h->comm && rccl().ok) (void)rccl().comm_destroy(h->comm);
-  free_bufs(h->cluster_bufs);
-  free_bufs(h->vol_bufs);
-  free_bufs(h->scratch_bufs);
-  free_bufs(h->ash_bufs);
-  free_bufs(h->lazy_bufs);
-  if (h->sweep_slab) (void)hipFree(h->sweep_slab);
-  if (h->sweep_tab) (void)hipFree(h->sweep_tab);
-  if (h->sweep_profs.p) (void)hipFree(h->sweep_profs.p);
-  if (h->sweep_rows.p) (void)hipFree(h->sweep_rows.p);
-  free_bufs(h->stab_bufs);
-  free_bufs(h->rtab_bufs);
-  drop_loaded_pods(h);
-  if (h->pod1_arena.p) (void)hipFree(h->pod1_arena.p);
-  if (h->nom_arena.p) (void)hipFree(h->nom_arena.p);
-  if (h->many_arena.p) (void)hipFree(h->many_arena.p);
-  if (h->many_out.p) (void)hipFree(h->many_out.p);
-  if (h->many_stage.p) (void)hipHostFree(h->many_stage.p);
-  if (h->many_host.p) (void)hipHostFree(h->many_host.p);
-  for (auto& a : h->fw_arena)
-    if (a.p) (void)hipFree(a.p);
-  if (h->fwh) (void)hipHostFree(h->fwh);
-  if (h->prog) (void)hipHostFree(h->prog);
-  if (h->pin) (void)hipHostFree(h->pin);
-  if (h->pout) (void)hipHostFree(h->pout);
-  drop_bound_pods(h);
-  if (h->d_chosen) (void)hipFree(h->d_chosen);
-  if (h->st) (void)hipFree(h->st);
-  if (h->d_prof) (void)hipFree(h->d_prof);
-  if (h->d_bp) (void)hipFree(h->d_bp);
-  for (auto& r : h->ring) {
-    if (r.p) (void)hipHostFree(r.p);
-    if (r.ev) (void)hipEventDestroy(r.ev);
-  }
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -2249,33 +2175,6 @@ static void single_pod_set(const ksim_pod_set* ps, int32_t i, ksim_pod& pod, std
   copy_terms(pod.vz_first, pod.vz_count);
 }
 
-int ksim_host::arena_reserve(ksim_handle* h, DevArena& a, size_t bytes) {
-  if (bytes <= a.cap) return KSIM_OK;
-  if (a.p) (void)hipFree(a.p);
-  a.p = nullptr;
-  a.cap = 0;
-  const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-  const hipError_t e = hipMalloc(&a.p, cap);
-  if (e != hipSuccess) return hip_fail(h, e, "hipMalloc (arena)");
-  a.cap = cap;
-  return KSIM_OK;
-}
-
-// The handle's pinned staging (the stream must be idle: a copy from it may be
-// in flight otherwise).
-int ksim_host::pin_reserve(ksim_handle* h, size_t bytes) {
-  if (bytes <= h->pin_cap) return KSIM_OK;
-  if (h->pin) (void)hipHostFree(h->pin);
-  h->pin = h->pin_d = nullptr;
-  h->pin_cap = 0;
-  const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-  hipError_t e = hipHostMalloc(&h->pin, cap, hipHostMallocCoherent | hipHostMallocMapped);
-  if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (staging)");
-  if ((e = hipHostGetDevicePointer(&h->pin_d, h->pin, 0)) != hipSuccess) return hip_fail(h, e, "hipHostGetDevicePointer");
-  h->pin_cap = cap;
-  return KSIM_OK;
-}
-
 // Copies to / from the pinned staging by one kernel (launch_copy_list).
 struct Copies {
   CopyList l{};
@@ -2308,21 +2207,6 @@ struct Copies {
     return KSIM_OK;
   }
 };
-
-// The results' pinned staging (callers sync before reading it).
-static int pout_reserve(ksim_handle* h, size_t bytes) {
-  if (bytes <= h->pout_cap) return KSIM_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->pout) (void)hipHostFree(h->pout);
-  h->pout = h->pout_d = nullptr;
-  h->pout_cap = 0;
-  const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-  hipError_t e = hipHostMalloc(&h->pout, cap, hipHostMallocCoherent | hipHostMallocMapped);
-  if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (results)");
-  if ((e = hipHostGetDevicePointer(&h->pout_d, h->pout, 0)) != hipSuccess) return hip_fail(h, e, "hipHostGetDevicePointer");
-  h->pout_cap = cap;
-  return KSIM_OK;
-}
 
 static void build_pod_blob(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, PodBlob& b) {
   ksim_pod pod;
@@ -2405,21 +2289,12 @@ static int ring_slot(ksim_handle* h, size_t bytes, ksim_handle::PinSlot** out) {
   h->ring_next = (h->ring_next + 1) % ksim_handle::kPinRing;
   if (sl.pending) HIPCHK(h, hipEventSynchronize(sl.ev));   // this slot's last reader (four uploads ago)
   sl.pending = false;
-  if (bytes > sl.cap) {
-    if (sl.p) (void)hipHostFree(sl.p);
-    sl.p = sl.d = nullptr;
-    sl.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1 << 14);
-    hipError_t e = hipHostMalloc(&sl.p, cap, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (upload ring)");
-    if ((e = hipHostGetDevicePointer(&sl.d, sl.p, 0)) != hipSuccess) return hip_fail(h, e, "hipHostGetDevicePointer");
-    sl.cap = cap;
-  }
+  if (const int rc = sl.buf.reserve(h, bytes, Idle::kCaller)) return rc;   // its reader has run, above
   *out = &sl;
   return KSIM_OK;
 }
 
-static int upload_blob(ksim_handle* h, const PodBlob& b, DevArena& arena, DevPods& P,
+static int upload_blob(ksim_handle* h, const PodBlob& b, DevGrow& arena, DevPods& P,
                        WinState* begin_win = nullptr, bool record = false, bool synced = false) {
   const size_t total = b.bytes.size();
   if (h->pend_bind.on && arena.p && (const char*)h->pend_bind.P.pods >= (const char*)arena.p &&
@@ -2437,10 +2312,10 @@ static int upload_blob(ksim_handle* h, const PodBlob& b, DevArena& arena, DevPod
   int rc;
   if ((rc = ring_slot(h, total, &slp))) return rc;
   ksim_handle::PinSlot& sl = *slp;
-  if ((rc = arena_reserve(h, arena, total))) return rc;
-  std::memcpy(sl.p, b.bytes.data(), total);
+  if ((rc = arena.reserve(h, total, Idle::kCaller))) return rc;   // drained above when it grows
+  std::memcpy(sl.buf.p, b.bytes.data(), total);
   Copies cp;
-  cp.add(sl.d, arena.p, total);
+  cp.add(sl.buf.d, arena.p, total);
   if (begin_win) cp.begin(h->st, begin_win, 0, 1);
   if (record && h->pend_bind.on) {         // the last cycle's queued Reserve, ahead of this pass
     cp.bind(h->dc, h->pend_bind.P, h->pend_bind.node, h->pend_bind.sign);
@@ -2448,7 +2323,7 @@ static int upload_blob(ksim_handle* h, const PodBlob& b, DevArena& arena, DevPod
   }
   if ((rc = cp.run(h))) return rc;
   if (!synced) {                           // synced: the caller drains the stream before returning
-    if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(sl.ev.out(), hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(sl.ev, h->stream));
     sl.pending = true;
   }
@@ -2461,7 +2336,7 @@ static int upload_blob(ksim_handle* h, const PodBlob& b, DevArena& arena, DevPod
 }
 
 // Upload one pod (re-based) as a device pod set of its own.
-int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena) {
+int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevGrow& arena) {
   PodBlob b;
   build_pod_blob(h, ps, pod_index, b);
   return upload_blob(h, b, arena, P);
@@ -2469,18 +2344,6 @@ int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod
 
 int ksim_host::upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P) {
   return upload_single(h, ps, pod_index, P, h->pod1_arena);
-}
-
-int ksim_host::pinbuf_reserve(ksim_handle* h, PinBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return KSIM_OK;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-  const hipError_t e = hipHostMalloc(&b.p, cap, hipHostMallocDefault);
-  if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (pinned buffer)");
-  b.cap = cap;
-  return KSIM_OK;
 }
 
 int ksim_host::upload_many(ksim_handle* h, const ksim_pod_set* ps, const int32_t* idx, int32_t n, size_t extra,
@@ -2493,10 +2356,9 @@ int ksim_host::upload_many(ksim_handle* h, const ksim_pod_set* ps, const int32_t
     at[i] = total;
     total += (blobs[i].bytes.size() + 63) & ~(size_t)63;
   }
-  if (total + extra > h->many_arena.cap || total + extra > h->many_stage.cap)
-    HIPCHK(h, hipStreamSynchronize(h->stream));          // reallocated: nothing may read them
   int rc;
-  if ((rc = arena_reserve(h, h->many_arena, total + extra)) || (rc = pinbuf_reserve(h, h->many_stage, total + extra)))
+  if ((rc = h->many_arena.reserve(h, total + extra, Idle::kSync)) ||   // reallocated: nothing may read them
+      (rc = h->many_stage.reserve(h, total + extra, Idle::kSync)))
     return rc;
   char* stage = (char*)h->many_stage.p;
   std::memset(stage, 0, total + extra);
@@ -2674,19 +2536,9 @@ int ksim_fw_prefilter(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index,
   const size_t o_fail = 64, o_det = o_fail + ((N + 63) & ~(size_t)63),
                o_raw = o_det + ((4 * N + 63) & ~(size_t)63), o_part = o_raw + ((8 * (size_t)S * N + 63) & ~(size_t)63),
                need = o_part + 8 * N;
-  if (need > h->fwh_cap) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->fwh) (void)hipHostFree(h->fwh);
-    h->fwh = h->fwh_d = nullptr;
-    h->fwh_cap = 0;
-    hipError_t e = hipHostMalloc(&h->fwh, need, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e != hipSuccess) return hip_fail(h, e, "hipHostMalloc (fw answers)");
-    if ((e = hipHostGetDevicePointer(&h->fwh_d, h->fwh, 0)) != hipSuccess)
-      return hip_fail(h, e, "hipHostGetDevicePointer");
-    h->fwh_cap = need;
-  }
-  char* fo = (char*)h->fwh;
-  char* fd = (char*)h->fwh_d;
+  if ((rc = h->fwh.reserve(h, need, Idle::kSync))) return rc;
+  char* fo = (char*)h->fwh.p;
+  char* fd = (char*)h->fwh.d;
   // the pod, and the run header / window state / topology flags reset, in one
   // launch (upload_blob's begin job)
   build_pod_blob(h, ps, pod_index, h->fw_blob);
@@ -2863,8 +2715,8 @@ static int fw_score_host(ksim_handle* h, const int32_t* nodes, int32_t n, ksim_e
   for (int32_t j = 0; j < n; j++) seen[nodes[j]] = 0;
   // the filter pass's answers: node-major int32 rows [n][S + 1] (the kernel's
   // own copy), or slot-major int64 [S][n] and [n] (a copy launch)
-  const char* rawb = (const char*)h->fwh + h->fw_oraw;
-  const char* partb = (const char*)h->fwh + h->fw_opart;
+  const char* rawb = (const char*)h->fwh.p + h->fw_oraw;
+  const char* partb = (const char*)h->fwh.p + h->fw_opart;
   const bool w32 = h->fw_raw32;
   const size_t W = (size_t)S + 1;
   auto raw_at = [&](int k, size_t node) -> int64_t {
@@ -2967,9 +2819,9 @@ int ksim_fw_score(ksim_handle* h, const int32_t* nodes, int32_t n, ksim_eval_out
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));    // the upload staging is free again
   const size_t o_list = (64 + N + 63) & ~(size_t)63;
-  if ((rc = pin_reserve(h, o_list + 4 * (size_t)n))) return rc;
+  if ((rc = h->pin.reserve(h, o_list + 4 * (size_t)n, Idle::kCaller))) return rc;   // idle: drained above
   // the list: feasible nodes of the filter pass, each once (the mask in staging)
-  uint8_t* out_of_list = (uint8_t*)h->pin + 64;
+  uint8_t* out_of_list = (uint8_t*)h->pin.p + 64;
   std::memset(out_of_list, 1, N);
   for (int32_t j = 0; j < n; j++) {
     const int32_t x = nodes[j];
@@ -2977,15 +2829,15 @@ int ksim_fw_score(ksim_handle* h, const int32_t* nodes, int32_t n, ksim_eval_out
       return set_err(h, KSIM_E_INVALID, "node list: not a feasible node of the filter pass, or repeated");
     out_of_list[x] = 0;
   }
-  std::memcpy((char*)h->pin + o_list, nodes, 4 * (size_t)n);
+  std::memcpy((char*)h->pin.p + o_list, nodes, 4 * (size_t)n);
   // the window of the filter pass covers the whole scan set (k_window's
   // extender branch keeps it and drops the unlisted nodes)
-  std::memcpy(h->pin, &h->fw_ns, sizeof(int32_t));
+  std::memcpy(h->pin.p, &h->fw_ns, sizeof(int32_t));
   {
     Copies cp;
-    cp.add((char*)h->pin_d + 64, h->ext_fail, N);
-    cp.add(h->pin_d, &h->sc.win->cut, sizeof(int32_t));
-    cp.add((char*)h->pin_d + o_list, h->fw_nodes, 4 * (size_t)n);
+    cp.add((char*)h->pin.d + 64, h->ext_fail, N);
+    cp.add(h->pin.d, &h->sc.win->cut, sizeof(int32_t));
+    cp.add((char*)h->pin.d + o_list, h->fw_nodes, 4 * (size_t)n);
     if ((rc = cp.run(h))) return rc;
   }
   LaunchArgs a = make_args(h, h->pod1, nullptr);
@@ -2997,10 +2849,10 @@ int ksim_fw_score(ksim_handle* h, const int32_t* nodes, int32_t n, ksim_eval_out
   // the pinned staging, one synchronization; the caller's entries of
   // unlisted nodes are left as they are (ksim_engine.h)
   const size_t o_comp = (sizeof(WinState) + 63) & ~(size_t)63, nb = (16 * (size_t)S + 9) * n;
-  if ((rc = pout_reserve(h, o_comp + nb))) return rc;
-  char* po = (char*)h->pout;
-  launch_fw_gather(h->eo, h->fw_nodes, n, (int32_t)N, S, (int64_t*)((char*)h->pout_d + o_comp), h->sc.win,
-                   h->pout_d, h->stream);
+  if ((rc = h->pout.reserve(h, o_comp + nb, Idle::kSync))) return rc;
+  char* po = (char*)h->pout.p;
+  launch_fw_gather(h->eo, h->fw_nodes, n, (int32_t)N, S, (int64_t*)((char*)h->pout.d + o_comp), h->sc.win,
+                   h->pout.d, h->stream);
   HIPCHK(h, hipGetLastError());
   h->fw_pending = false;
   h->fw_dom_dirty = false;                 // k_select re-zeroed the domain sums
@@ -3073,24 +2925,26 @@ int ksim_fw_normalize(ksim_handle* h, int32_t score_slot, const int32_t* nodes, 
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));    // the staging is free again
   const size_t o_vals = (4 * (size_t)n + 63) & ~(size_t)63;
-  if ((rc = pin_reserve(h, o_vals + 8 * (size_t)n)) || (rc = pout_reserve(h, 8 * (size_t)n))) return rc;
-  std::memcpy(h->pin, nodes, 4 * (size_t)n);
-  std::memcpy((char*)h->pin + o_vals, scores, 8 * (size_t)n);
+  if ((rc = h->pin.reserve(h, o_vals + 8 * (size_t)n, Idle::kCaller)) ||   // idle: drained above
+      (rc = h->pout.reserve(h, 8 * (size_t)n, Idle::kSync)))
+    return rc;
+  std::memcpy(h->pin.p, nodes, 4 * (size_t)n);
+  std::memcpy((char*)h->pin.p + o_vals, scores, 8 * (size_t)n);
   {
     Copies cp;
-    cp.add(h->pin_d, h->fw_nodes, 4 * (size_t)n);
-    cp.add((char*)h->pin_d + o_vals, h->fw_vals, 8 * (size_t)n);
+    cp.add(h->pin.d, h->fw_nodes, 4 * (size_t)n);
+    cp.add((char*)h->pin.d + o_vals, h->fw_vals, 8 * (size_t)n);
     if ((rc = cp.run(h))) return rc;
   }
   launch_fw_normalize(make_args(h, h->pod1, nullptr), score_slot, h->fw_nodes, h->fw_vals, n, h->fw_out, h->stream);
   HIPCHK(h, hipGetLastError());
   {
     Copies cp;
-    cp.add(h->fw_out, h->pout_d, 8 * (size_t)n);
+    cp.add(h->fw_out, h->pout.d, 8 * (size_t)n);
     if ((rc = cp.run(h))) return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  std::memcpy(out, h->pout, 8 * (size_t)n);
+  std::memcpy(out, h->pout.p, 8 * (size_t)n);
   return KSIM_OK;
 }
 
@@ -3124,11 +2978,11 @@ static int apply_bind(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index,
   // one launch, no arena copy
   ksim_handle::PinSlot* sl = nullptr;
   if ((rc = ring_slot(h, b.bytes.size(), &sl))) return rc;
-  std::memcpy(sl->p, b.bytes.data(), b.bytes.size());
-  P = blob_pods(h, b, (char*)sl->d);
+  std::memcpy(sl->buf.p, b.bytes.data(), b.bytes.size());
+  P = blob_pods(h, b, (char*)sl->buf.d);
   launch_assume(h->dc, P, 0, node, sign, h->stream);
   HIPCHK(h, hipGetLastError());
-  if (!sl->ev) HIPCHK(h, hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
+  if (!sl->ev) HIPCHK(h, hipEventCreateWithFlags(sl->ev.out(), hipEventDisableTiming));
   HIPCHK(h, hipEventRecord(sl->ev, h->stream));
   sl->pending = true;
   // no synchronization: every later call is ordered after it on the stream
@@ -3414,17 +3268,16 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
   const bool reuse = h->d_chosen && h->pod_buf_bytes == bytes;
   auto drop_queue = [&](int code) {
     drop_graphs(h);
-    free_bufs(h->pod_bufs);
+    h->pod_bufs.clear();
     h->pod_buf_bytes.clear();
-    if (h->d_chosen) (void)hipFree(h->d_chosen);
-    h->d_chosen = nullptr;
+    h->d_chosen = nullptr;                         // in pod_bufs
     return code;
   };
   if (!reuse) drop_queue(KSIM_OK);
   size_t next_buf = 0;
   auto put = [&](auto*& dst, const void* src, size_t nbytes) -> int {
-    if (!reuse) return dev_alloc(h, h->pod_bufs, dst, nbytes, src);
-    DevBuf& b = h->pod_bufs[next_buf++];
+    if (!reuse) return h->pod_bufs.alloc(h, dst, nbytes, src);
+    const DevBuf& b = h->pod_bufs[next_buf++];
     const hipError_t e = (src && nbytes) ? hipMemcpyAsync(b.p, src, nbytes, hipMemcpyHostToDevice, h->stream)
                                          : hipMemsetAsync(b.p, 0, b.bytes, h->stream);
     if (e != hipSuccess) return hip_fail(h, e, "pod upload");
@@ -3589,12 +3442,8 @@ int ksim_load_pods(ksim_handle* h, const ksim_pod_set* ps) {
   P.n_exprs = ps->n_exprs;
   P.n_terms = ps->n_terms;
   hipError_t e = hipSuccess;
-  if (!reuse) {
-    e = hipMalloc(&h->d_chosen, 4 * np1);
-    if (e != hipSuccess) {
-      h->d_chosen = nullptr;
-      return drop_queue(hip_fail(h, e, "hipMalloc"));
-    }
+  if (!reuse) {                                    // behind the arrays put() reuses by position
+    if ((rc = h->pod_bufs.alloc(h, h->d_chosen, 4 * np1))) return drop_queue(rc);
     h->pod_buf_bytes = bytes;
   }
   if ((e = hipMemsetAsync(h->d_chosen, 0xff, 4 * np1, h->stream)) != hipSuccess ||
@@ -3714,7 +3563,7 @@ int ksim_sweep_loaded(ksim_handle* h, int32_t first, int32_t count, const ksim_p
   const int32_t lanes = std::min(max_lanes ? max_lanes : KSIM_SWEEP_DEFAULT_LANES, n_profs);
   // the vectors' device copies: [n_profs] ksim_profile, then [n_profs] BatchProg
   const size_t pbytes = (sizeof(ksim_profile) * (size_t)n_profs + 255) & ~(size_t)255;
-  if ((rc = sweep_reserve(h, h->sweep_profs, pbytes + sizeof(BatchProg) * (size_t)n_profs))) return rc;
+  if ((rc = h->sweep_profs.reserve(h, pbytes + sizeof(BatchProg) * (size_t)n_profs, Idle::kSync))) return rc;
   ksim_profile* d_profs = (ksim_profile*)h->sweep_profs.p;
   BatchProg* d_bps = (BatchProg*)((char*)h->sweep_profs.p + pbytes);
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
@@ -4012,7 +3861,7 @@ int ksim_time_kernels(ksim_handle* h, int32_t first, int32_t count, double* avg_
             [&]() -> int {
               lazy_flush(h, lazy_batch(h, a, i, plan.rt), h->stream);
               HIPCHK(h, hipGetLastError());
-              return read_state_at(h, (i & 1) ? h->lazy_st1 : h->st, st);
+              return read_state_at(h, (i & 1) ? h->lazy.st1 : h->st, st);
             },
             [&] { return std::min<int32_t>(iters, st.batches - done_batches); });
         if (r) return r;

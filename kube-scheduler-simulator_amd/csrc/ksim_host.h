@@ -14,28 +14,9 @@
 #include <vector>
 
 #include "ksim_internal.h"
+#include "ksim_mem.h"
 
 using namespace ksim;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-// A device buffer reused across calls, grown (never shrunk) on demand: the
-// per-call uploads of the framework-driven calls (one pod, its terms and uses)
-// without a hipMalloc / hipFree pair per call.
-struct DevArena {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
-// Pinned host memory reused across calls, grown on demand (pinbuf_reserve; the
-// stream must be idle when it grows).
-struct PinBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
 
 // One pod (re-based) as a device pod set of its own, packed the way it is
 // uploaded: every piece at a 64-byte aligned offset of one blob.
@@ -80,10 +61,93 @@ struct GraphKey {
   bool operator<(const GraphKey& o) const { return std::tie(kind, arg) < std::tie(o.kind, o.arg); }
 };
 
+// State of the handle that is dropped together lives together: a pool, the
+// typed views into it and its sizes in one struct, dropped by assigning a
+// fresh value (`h->lazy = LazyBufs{}`).
+
+// One list set on the bound-pod table's rows: the list as its setter uploaded
+// it (`ents` entries) and, after a commit, its second buffers.
+struct KSIM_HIDDEN BoundList {
+  DevPool bufs;
+  size_t ents = 0;
+};
+
+// ksim_preempt_many's per-row slabs of one launch group, allocated at the
+// first call that needs them (`rows` rows of PreemptNode[n] and of
+// uint8_t[bound.n]), and ksim_preempt_many_dom's PreFilter states of one group
+// of domain rows (`dom_rows` rows of int64[KSIM_MAX_USES][vmax] and of
+// PreemptDomHead).  Sized by the bound table and the cluster: they go with the table.
+struct KSIM_HIDDEN ManySlabs {
+  DevPool bufs, dom_bufs;
+  PreemptNode* res = nullptr;
+  uint8_t* vflag = nullptr;
+  int32_t rows = 0;
+  int64_t* dom = nullptr;
+  PreemptDomHead* heads = nullptr;
+  int32_t dom_rows = 0;
+};
+
+// DefaultPreemption: the bound pods per node in importance order
+// (ksim_set_bound_pods), the three lists set on their rows, and what
+// ksim_preempt_commit keeps of the table.
+struct KSIM_HIDDEN BoundPods {
+  DevPool bufs;                         // the table, its second set and the scan's scratch
+  DevPool nom_bufs;                     // ksim_preempt_nominated's group requests
+  BoundList add, pdb, vol;              // ksim_set_bound_pod_adds, _pdbs, _volumes (vol: ksim_set_volume_limits drops it too)
+  DevPreempt d{};
+  int64_t* smin = nullptr;              // ksim_preempt_spread's per-use minima (k_preempt_spread_mins)
+  const int32_t* voff = nullptr;        // [n + 1] CSR order: the rows' volume holdings (null: none set)
+  const VolHold* vols = nullptr;
+  std::vector<int32_t> index;           // CSR position -> bound-pod table index
+  const int32_t* dindex = nullptr;      // its device copy (ksim_preempt_many)
+  int32_t n = 0;                        // the caller's rows (ksim_set_bound_pods), evicted ones included
+  int32_t maxrow = 0;                   // the most bound pods one node holds
+  // ksim_preempt_commit.  Per caller's row: its node and requests as
+  // ksim_set_bound_pods took them, and whether a commit evicted it since
+  // (dead; 2 inside a call: named by it).  `live` rows are left, at the
+  // table's positions [0, live).  A commit compacts the device's arrays and
+  // leaves `index` as it was (index_stale): the setters compact it, and until
+  // then a single dry run reads its victims' rows from dindex.  alt holds the
+  // table's second buffer set and the scan's scratch (its *2 fields and pos /
+  // dead / before / tile; null: not allocated), owned by bufs and, each
+  // list's, by the list; every commit swaps the two sets.
+  std::vector<int32_t> row_node;
+  std::vector<int64_t> row_req;
+  std::vector<uint8_t> dead;
+  int32_t live = 0;
+  bool index_stale = false;
+  DevCommit alt{};
+  ManySlabs many;
+};
+
+// Deferred-commit FAST batches (ksim_internal.h): the second snapshot buffer
+// X[1] and state st[1], the ring of chain + pairs outputs, sized by dc.n
+// (alloc_lazy; n: the node count they were allocated for, -1: none).
+struct KSIM_HIDDEN LazyBufs {
+  DevPool bufs;
+  int32_t n = -1;
+  DynCols x1{};
+  DevState* st1 = nullptr;
+  uint64_t *g = nullptr, *m = nullptr;             // [kLazySlots][kBatchPods]
+  int32_t* e = nullptr;                            // [kLazySlots] prefix length, -1 = empty slot
+  int32_t *ab = nullptr, *aw = nullptr;            // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
+};
+
+// Node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and the
+// global bitmap (adapt_shard_buffers: allocated at the first such run).
+struct KSIM_HIDDEN AshBufs {
+  DevPool bufs;
+  uint64_t *send = nullptr, *recv = nullptr, *gmask = nullptr;
+  int32_t world = 0, w = 0;
+};
+
+// Members are destroyed last to first: the stream and the events, which the
+// buffers' frees may still need, come first.
 struct ksim_handle {
+  KSIM_HIDDEN ksim_handle() = default;   // (the library exports the C ABI, not this)
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HipStream stream;
+  HipEvent ev0, ev1;
   std::string err;
 
   bool has_profile = false;
@@ -93,11 +157,14 @@ struct ksim_handle {
   // batch graph then survives a weight change (ksim_set_profile)
   ksim_profile* d_prof = nullptr;
   BatchProg* d_bp = nullptr;
+  // what lives as long as the handle, at a fixed address: st, d_prof, d_bp
+  // (ksim_create) and sweep_tab (alloc_sweep)
+  DevPool life_bufs;
   std::vector<size_t> pod_buf_bytes;    // sizes of pod_bufs (ksim_load_pods reuses same-sized buffers)
 
   bool has_cluster = false;
   DevCluster dc{};
-  std::vector<DevBuf> cluster_bufs;
+  DevPool cluster_bufs;
   std::vector<uint8_t> taint_effect;    // host copy (batchability analysis)
   std::vector<uint16_t> hard_taints;    // taint ids with effect NoSchedule/NoExecute on some node
   bool any_unschedulable = false;       // some node has spec.unschedulable
@@ -111,7 +178,7 @@ struct ksim_handle {
   } init{};
   // node volume limits (ksim_set_volume_limits): limit, attached and the copy
   // of attached that ksim_reset_cluster restores
-  std::vector<DevBuf> vol_bufs;
+  DevPool vol_bufs;
   int32_t* vol_init = nullptr;
   std::vector<int32_t> col_nvals;       // host copy (pod validation)
   std::vector<uint8_t> col_unique;      // host copy of DevCluster.col_unique (kUseUniqueCol on upload)
@@ -119,15 +186,15 @@ struct ksim_handle {
 
   DevScratch sc{};
   DevEvalOut eo{};
-  std::vector<DevBuf> scratch_bufs;
+  DevPool scratch_bufs;
 
   DevState* st = nullptr;
   int32_t run_hdr[2] = {0, 0};
 
   // loaded pod queue (batch mode)
   DevPods dp{};
+  DevPool pod_bufs;                     // the queue's arrays in ksim_load_pods' order, then d_chosen
   int32_t* d_chosen = nullptr;
-  std::vector<DevBuf> pod_bufs;
   std::vector<uint8_t> batchable;       // per loaded pod
   std::vector<uint8_t> topo;            // per loaded pod: 0 no topology uses, 1 uses (k_topo_prefilter), 2 uses
                                         // read from persistent tables (kPlanPtab)
@@ -141,7 +208,7 @@ struct ksim_handle {
   int32_t* d_srep = nullptr;
   int32_t stab_ncls = 0;
   bool stab_dirty = true, stab_ready = false;
-  std::vector<DevBuf> stab_bufs;
+  DevPool stab_bufs;
   size_t stab_bytes = 0;
   std::vector<int32_t> sclass;          // host copy of d_sclass
   std::vector<uint8_t> hard_small;      // per loaded pod: every hard spread key column has <= kFuseMinValues values
@@ -152,8 +219,8 @@ struct ksim_handle {
   std::vector<int64_t> xreg_len;        // per loaded pod: sharded cycle, registration words (0: no soft spread)
 
   // compat-mode single pod
-  DevArena pod1_arena;                  // the single-pod uploads (upload_single)
-  DevArena nom_arena;                   // a nominated pod (ksim_fw_filter_nominated)
+  DevGrow pod1_arena;                   // the single-pod uploads (upload_single)
+  DevGrow nom_arena;                    // a nominated pod (ksim_fw_filter_nominated)
   // Reserve / Unreserve calls that arrive while a framework cycle sits between
   // its PreFilter and Score (the binding goroutine's Unreserve):
   // upstream's running cycle keeps its snapshot, so the engine applies them
@@ -171,9 +238,7 @@ struct ksim_handle {
   std::vector<DeferredBind> deferred_binds;
   // pinned, coherent host staging for the per-call uploads / results, and the
   // device's addresses of it (copy kernels read / write it directly)
-  void* pin = nullptr;
-  void* pin_d = nullptr;
-  size_t pin_cap = 0;
+  PinGrow pin{kPinMapped, 1 << 16, "hipHostMalloc (staging)"};
   // the last pod upload's copy out of the staging (upload_blob waits on it
   // instead of the whole stream); the pod last uploaded into pod1_arena (its
   // bytes and device address: a Reserve / Unreserve of the same pod binds
@@ -182,10 +247,8 @@ struct ksim_handle {
   // pod deltas, another pod's Reserve, the next cycle's pod) do not wait for
   // each other's copies; a slot is reused once its copy has run (its event)
   struct PinSlot {
-    void* p = nullptr;
-    void* d = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
+    PinGrow buf{kPinMapped, 1 << 14, "hipHostMalloc (upload ring)"};
+    HipEvent ev;
     bool pending = false;
   };
   static constexpr int kPinRing = 4;
@@ -204,7 +267,7 @@ struct ksim_handle {
   // the framework-driven filter passes alternate two arenas, so the Reserve of
   // cycle i (binding from cycle i's arena) can wait, queued, and run inside
   // cycle i+1's upload launch (pend_bind); any other call launches it first
-  DevArena fw_arena[2];
+  DevGrow fw_arena[2];
   int fw_flip = 0;
   struct PendBind {
     bool on = false;
@@ -213,60 +276,15 @@ struct ksim_handle {
     int sign = 0;
   } pend_bind;
   int64_t pend_reuse = 0;                      // upload_blob found the queued Reserve's arena reused (flushed)
-  void* pout = nullptr;
-  void* pout_d = nullptr;
-  size_t pout_cap = 0;
-  // DefaultPreemption: bound pods per node in importance order
-  std::vector<DevBuf> pre_bufs;
-  std::vector<DevBuf> pre_nom_bufs;     // ksim_preempt_nominated's group requests
-  int64_t* pre_smin = nullptr;          // ksim_preempt_spread's per-use minima (in pre_bufs; k_preempt_spread_mins)
-  std::vector<DevBuf> pre_add_bufs;     // ksim_set_bound_pod_adds (dropped by ksim_set_bound_pods)
-  std::vector<DevBuf> pre_pdb_bufs;     // ksim_set_bound_pod_pdbs (likewise)
-  std::vector<DevBuf> pre_vol_bufs;     // ksim_set_bound_pod_volumes (likewise, and by ksim_set_volume_limits)
-  const int32_t* pre_voff = nullptr;    // [pre_n + 1] CSR order: the rows' volume holdings (null: none set)
-  const VolHold* pre_vols = nullptr;
-  DevPreempt pre{};
-  std::vector<int32_t> pre_index;       // CSR position -> bound-pod table index
-  int32_t pre_n = 0;                    // the caller's rows (ksim_set_bound_pods), evicted ones included
-  // ksim_preempt_commit.  Per caller's row: its node and requests as
-  // ksim_set_bound_pods took them, and whether a commit evicted it since
-  // (pre_dead; 2 inside a call: named by it).  pre_live rows are left, at the
-  // table's positions [0, pre_live).  A commit compacts the device's arrays and
-  // leaves pre_index as it was (pre_index_stale): the setters compact it, and
-  // until then a single dry run reads its victims' rows from pre_dindex.
-  // pre_alt holds the table's second buffer set and the scan's scratch (its
-  // *2 fields and pos / dead / before / tile; null: not allocated), owned by
-  // pre_bufs and, each list's, by the list's owner; every commit swaps the two
-  // sets.  pre_*_ents: the entries of each list as its setter uploaded it.
-  std::vector<int32_t> pre_row_node;
-  std::vector<int64_t> pre_row_req;
-  std::vector<uint8_t> pre_dead;
-  int32_t pre_live = 0;
-  bool pre_index_stale = false;
-  DevCommit pre_alt{};
-  size_t pre_add_ents = 0, pre_pdb_ents = 0, pre_vol_ents = 0;
-  // ksim_preempt_many.  With the bound table (dropped where pre_bufs is): the
-  // device copy of pre_index (in pre_bufs), the most bound pods one node holds,
-  // and, allocated at the first call that needs them, the per-row slabs of one
-  // launch group (many_slab_rows rows of PreemptNode[n] and of uint8_t[pre_n]).
-  // With the handle: the call's preemptor records and row table (one upload
-  // out of the pinned many_stage), the result buffer (pick records, then the
-  // victims lists) and its pinned host copy many_host; every call ends
-  // synchronized, so neither is in flight when the next call writes it.
-  const int32_t* pre_dindex = nullptr;
-  int32_t pre_maxrow = 0;
-  std::vector<DevBuf> many_bufs;
-  PreemptNode* many_res = nullptr;
-  uint8_t* many_vflag = nullptr;
-  int32_t many_slab_rows = 0;
-  // ksim_preempt_many_dom's PreFilter states of one launch group of domain rows
-  // (many_dom_rows rows of int64[KSIM_MAX_USES][vmax] and of PreemptDomHead), kept and dropped with the slabs above
-  std::vector<DevBuf> many_dom_bufs;
-  int64_t* many_dom = nullptr;
-  PreemptDomHead* many_heads = nullptr;
-  int32_t many_dom_rows = 0;
-  DevArena many_arena, many_out;
-  PinBuf many_stage, many_host;
+  PinGrow pout{kPinMapped, 1 << 16, "hipHostMalloc (results)"};
+  BoundPods bound;                      // DefaultPreemption; dropped whole by ksim_set_bound_pods and ksim_set_cluster
+  // ksim_preempt_many, with the handle: the call's preemptor records and row
+  // table (one upload out of the pinned many_stage), the result buffer (pick
+  // records, then the victims lists) and its pinned host copy many_host; every
+  // call ends synchronized, so neither is in flight when the next call writes it.
+  DevGrow many_arena, many_out;
+  PinGrow many_stage{hipHostMallocDefault, 1 << 16, "hipHostMalloc (pinned buffer)"};
+  PinGrow many_host{hipHostMallocDefault, 1 << 16, "hipHostMalloc (pinned buffer)"};
   size_t many_stage_bytes = 0;          // of the call in flight
   int64_t many_rows = 0, many_single = 0;   // rows answered by the batched / the single-pod launches (ksim_get_diag)
   int64_t many_dom_answered = 0;        // ksim_preempt_many_dom's domain rows, by the batched launches
@@ -294,9 +312,7 @@ struct ksim_handle {
   int64_t fw_counts[4] = {0, 0, 0, 0};   // Score on the host / device, NormalizeScore cached / device
   std::vector<uint8_t> fw_seen;    // list validation (all zero between calls)
   std::vector<int64_t> fw_tot;
-  void* fwh = nullptr;             // pinned: [S][n] raw, [n] part
-  void* fwh_d = nullptr;
-  size_t fwh_cap = 0;
+  PinGrow fwh{kPinMapped, 0, "hipHostMalloc (fw answers)"};   // [S][n] raw, [n] part
   uint32_t fw_tflags = 0;
   size_t fw_oraw = 0, fw_opart = 0;  // fwh offsets of the raw scores and the weighted part
   bool fw_raw32 = false;             // ... as int32 (the filter kernel's own copy) or int64 (a copy launch)
@@ -318,21 +334,11 @@ struct ksim_handle {
   // every graph of this handle's own runs, by what it holds (ksim_engine.cpp
   // handle_graph captures them, drop_graphs_if destroys them)
   std::map<GraphKey, hipGraphExec_t> graphs;
-  // deferred-commit FAST batches (ksim_internal.h): the second snapshot buffer
-  // X[1] and state st[1], the ring of chain + pairs outputs; kGraphBatches
-  // batches as one graph (starting at a batch index divisible by kLazySlots)
-  // and, captured with it, the tail graph of kLazySlots batches
-  std::vector<DevBuf> lazy_bufs;
-  int32_t lazy_n = -1;
-  DynCols lazy_x1{};
-  DevState* lazy_st1 = nullptr;
-  uint64_t *lazy_g = nullptr, *lazy_m = nullptr;   // [kLazySlots][kBatchPods]
-  int32_t* lazy_e = nullptr;                        // [kLazySlots] prefix length, -1 = empty slot
-  int32_t *lazy_ab = nullptr, *lazy_aw = nullptr;   // ADAPT: [kLazySlots][kBatchPods] broken flags, [..][2 B] windows
-  // run_lazy's progress words (host-mapped pinned, alloc_lazy): [0] the last
-  // state writer's lazy_progress, [1] the batch counter the run started from
-  unsigned long long* prog = nullptr;
-  unsigned long long* prog_d = nullptr;
+  LazyBufs lazy;                        // deferred-commit batches (alloc_lazy)
+  // run_lazy's progress words (host-mapped pinned; alloc_lazy reserves them
+  // once, and the graphs hold their address): [0] the last state writer's
+  // lazy_progress, [1] the batch counter the run started from
+  PinGrow prog{kPinMapped, 0, "hipHostMalloc (progress word)"};
   // ksim_schedule_loaded leaves the zeroing of the call's counters to its first
   // run (run_range: run_lazy's begin launch takes it, every other run calls
   // reset_counters first)
@@ -353,14 +359,10 @@ struct ksim_handle {
   uint16_t* d_rcls = nullptr;
   PodReq* d_rreq = nullptr;
   int32_t rq_ncls = 0;                             // > kReqMaxClasses: too many, no table
-  std::vector<DevBuf> rtab_bufs;
+  DevPool rtab_bufs;
   size_t rtab_bytes = 0;
   int64_t rtab_runs = 0;                           // runs that took the table (ksim_get_diag out[27])
-  // node-sharded ADAPT batch: this shard's bitmaps, the all-gathered ones and
-  // the global bitmap (allocated at the first such run)
-  std::vector<DevBuf> ash_bufs;
-  uint64_t *ash_send = nullptr, *ash_recv = nullptr, *ash_gmask = nullptr;
-  int32_t ash_world = 0, ash_w = 0;
+  AshBufs ash;                          // node-sharded ADAPT batches (adapt_shard_buffers)
   // packed policy sweep (ksim_sweep_loaded, run_sweep): the lanes' buffers as
   // one slab sized by (dc.n, lanes), the lane table [kLazySlots][kSweepMaxLanes]
   // (its address is all a sweep graph holds of them), the vectors' profile
@@ -373,12 +375,12 @@ struct ksim_handle {
     int32_t *topk_cnt, *topk_complete, *pinv;
     int64_t* pnorm;
   };
-  void* sweep_slab = nullptr;
+  DevPool sweep_slab;                            // one entry
   int32_t sweep_n = -1, sweep_lanes = 0;
   std::vector<SweepLaneBufs> sweep_lane;
   DevState* sweep_st = nullptr;                  // [sweep_lanes][2]
-  SweepLane* sweep_tab = nullptr;
-  DevArena sweep_profs, sweep_rows;
+  SweepLane* sweep_tab = nullptr;                // in life_bufs
+  DevGrow sweep_profs{0, "hipMalloc"}, sweep_rows{0, "hipMalloc"};
   // deferred-commit batches end at their first pair cut (KSIM_ONE_CUT=1 at the
   // last run's start): the setting the handle's deferred-commit graphs hold
   bool one_cut = false;
@@ -405,24 +407,8 @@ namespace ksim_host __attribute__((visibility("hidden"))) {
 int set_err(ksim_handle* h, int code, const std::string& msg);
 int hip_fail(ksim_handle* h, hipError_t e, const char* what);
 hipError_t hcopy(ksim_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
-void free_bufs(std::vector<DevBuf>& v);
-int upload(ksim_handle* h, std::vector<DevBuf>& owner, const void* src, size_t bytes, void** out);
-
-// upload into a typed field: the one way the host runtime allocates a device
-// array (src null: zero-filled).  T may be const-qualified, as the fields the
-// kernels only read are.
-template <class T>
-int dev_alloc(ksim_handle* h, std::vector<DevBuf>& owner, T*& dst, size_t bytes, const void* src = nullptr) {
-  void* p = nullptr;
-  if (const int rc = upload(h, owner, src, bytes, &p)) return rc;
-  dst = (T*)p;
-  return KSIM_OK;
-}
-
 void drop_graphs(ksim_handle* h);
 void drop_loaded_pods(ksim_handle* h);
-void drop_many_slabs(ksim_handle* h);
-void drop_bound_pods(ksim_handle* h);
 bool is_sharded(const ksim_handle* h);
 int validate_pod(ksim_handle* h, const ksim_pod_set* ps, int32_t i);
 int flush_pend_bind(ksim_handle* h);
@@ -430,8 +416,7 @@ int flush_idle(ksim_handle* h);
 int ensure_ready(ksim_handle* h, bool fw = false, bool keep_pend = false);
 LaunchArgs make_args(ksim_handle* h, const DevPods& P, int32_t* chosen);
 int set_run(ksim_handle* h, int32_t first, int32_t end);
-int pin_reserve(ksim_handle* h, size_t bytes);
-int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevArena& arena);
+int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P, DevGrow& arena);
 int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, DevPods& P);
 // Pods idx[0 .. n) of ps, each as upload_single would upload it, packed into
 // h->many_stage with `extra` more bytes behind them (64-byte aligned), and
@@ -442,6 +427,4 @@ int upload_single(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, Dev
 int upload_many(ksim_handle* h, const ksim_pod_set* ps, const int32_t* idx, int32_t n, size_t extra,
                 std::vector<DevPods>& Ps, char** extra_host, char** extra_dev);
 int upload_many_commit(ksim_handle* h);
-int arena_reserve(ksim_handle* h, DevArena& a, size_t bytes);
-int pinbuf_reserve(ksim_handle* h, PinBuf& b, size_t bytes);
 }  // namespace ksim_host

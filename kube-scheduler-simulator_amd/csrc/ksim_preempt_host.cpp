@@ -49,44 +49,34 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
   }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  free_bufs(h->pre_bufs);
-  free_bufs(h->pre_add_bufs);                  // the adds belonged to the old table's rows
-  free_bufs(h->pre_pdb_bufs);                  // and so did the budgets
-  free_bufs(h->pre_vol_bufs);                  // and the volume holdings
-  drop_many_slabs(h);                          // and ksim_preempt_many's slabs are sized by it
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  h->pre_dindex = nullptr;
+  // the old table goes whole: the lists belonged to its rows, ksim_preempt_many's slabs are sized by it
+  h->bound = BoundPods{};
   DevPreempt d{};
-  if ((rc = dev_alloc(h, h->pre_bufs, d.off, 4 * off.size(), off.data())) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.prio, 4 * prio.size(), prio.data())) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.start, 8 * start.size(), start.data())) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.req, 8 * req.size(), req.data())) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.vflag, (size_t)std::max(n, 1))) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.res, sizeof(PreemptNode) * (size_t)N)) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.pick, 32)) ||
-      (rc = dev_alloc(h, h->pre_bufs, d.nslot, 4 * (size_t)std::max(N, 1))))
+  if ((rc = h->bound.bufs.alloc(h, d.off, 4 * off.size(), off.data())) ||
+      (rc = h->bound.bufs.alloc(h, d.prio, 4 * prio.size(), prio.data())) ||
+      (rc = h->bound.bufs.alloc(h, d.start, 8 * start.size(), start.data())) ||
+      (rc = h->bound.bufs.alloc(h, d.req, 8 * req.size(), req.data())) ||
+      (rc = h->bound.bufs.alloc(h, d.vflag, (size_t)std::max(n, 1))) ||
+      (rc = h->bound.bufs.alloc(h, d.res, sizeof(PreemptNode) * (size_t)N)) ||
+      (rc = h->bound.bufs.alloc(h, d.pick, 32)) ||
+      (rc = h->bound.bufs.alloc(h, d.nslot, 4 * (size_t)std::max(N, 1))))
     return rc;
   HIPCHK(h, hipMemsetAsync(d.nslot, 0xff, 4 * (size_t)std::max(N, 1), h->stream));   // -1: no group
   d.nreq = nullptr;
-  if ((rc = dev_alloc(h, h->pre_bufs, d.afftot, 8 * (size_t)KSIM_MAX_USES)) ||
-      (rc = dev_alloc(h, h->pre_bufs, h->pre_smin, 8 * 3 * (size_t)KSIM_MAX_USES)) ||
-      (rc = dev_alloc(h, h->pre_bufs, h->pre_dindex, 4 * (size_t)std::max(n, 1), n > 0 ? ix.data() : nullptr)))
+  if ((rc = h->bound.bufs.alloc(h, d.afftot, 8 * (size_t)KSIM_MAX_USES)) ||
+      (rc = h->bound.bufs.alloc(h, h->bound.smin, 8 * 3 * (size_t)KSIM_MAX_USES)) ||
+      (rc = h->bound.bufs.alloc(h, h->bound.dindex, 4 * (size_t)std::max(n, 1), n > 0 ? ix.data() : nullptr)))
     return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->pre = d;
-  h->pre_index = ix;
-  h->pre_n = n;
-  // what ksim_preempt_commit checks its rows against; its buffers went with pre_bufs and the lists
-  h->pre_row_node.assign(b->node, b->node + n);
-  h->pre_row_req.assign(b->req, b->req + (size_t)n * KSIM_PREEMPT_REQ);
-  h->pre_dead.assign((size_t)n, 0);
-  h->pre_live = n;
-  h->pre_index_stale = false;
-  h->pre_alt = DevCommit{};
-  h->pre_add_ents = h->pre_pdb_ents = h->pre_vol_ents = 0;
-  h->pre_maxrow = 0;
-  for (int32_t v = 0; v < N; v++) h->pre_maxrow = std::max(h->pre_maxrow, off[v + 1] - off[v]);
+  h->bound.d = d;
+  h->bound.index = ix;
+  h->bound.n = n;
+  // what ksim_preempt_commit checks its rows against
+  h->bound.row_node.assign(b->node, b->node + n);
+  h->bound.row_req.assign(b->req, b->req + (size_t)n * KSIM_PREEMPT_REQ);
+  h->bound.dead.assign((size_t)n, 0);
+  h->bound.live = n;
+  for (int32_t v = 0; v < N; v++) h->bound.maxrow = std::max(h->bound.maxrow, off[v + 1] - off[v]);
   return KSIM_OK;
 }
 
@@ -96,7 +86,7 @@ extern "C" int ksim_set_bound_pods(ksim_handle* h, const ksim_bound_pods* b) {
 // is not empty.  fn: the calling function, as the error texts name it.
 static int bound_csr_check(ksim_handle* h, const std::string& fn, const int32_t* off, bool have_entries,
                            const char* what, bool from_zero) {
-  const int32_t n = h->pre_n;
+  const int32_t n = h->bound.n;
   if (!off || (from_zero ? off[0] != 0 : off[0] < 0))
     return set_err(h, KSIM_E_INVALID, fn + (from_zero ? ": bad offsets (they start at 0)" : ": bad offsets"));
   for (int32_t i = 0; i < n; i++)
@@ -106,42 +96,41 @@ static int bound_csr_check(ksim_handle* h, const std::string& fn, const int32_t*
 }
 
 // ... and, every entry validated by the caller: the rows go into the table's
-// per-node importance order (CSR position k = caller row pre_index[k]; conv
+// per-node importance order (CSR position k = caller row bound.index[k]; conv
 // makes the device's entry of the caller's), the old list is freed (every dry
 // run ends synchronized: nothing reads it) and the new one uploaded, and
 // published once the copies have read this call's vectors.  off == null only
 // clears the list.  extra: one more int32 array that goes with the list (the
 // budgets' allowed counts).  After a ksim_preempt_commit the caller's CSR still
 // spans all its rows; the table's positions are the rows left, so an evicted
-// row's entries are passed over (the host's pre_index is compacted here, where
-// the work is O(rows) anyway).  ents: the entries uploaded; alt_off / alt_ent:
+// row's entries are passed over (the host's bound.index is compacted here, where
+// the work is O(rows) anyway).  list: its owner (the entries uploaded counted there); alt_off / alt_ent:
 // the commit's second buffers of this list, which go with the old ones.
 template <class E, class In, class Conv>
-static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_t* off, const In* in, Conv conv,
-                         const int32_t*& d_off, const E*& d_ent, size_t& ents, int32_t*& alt_off, E*& alt_ent,
+static int bound_csr_set(ksim_handle* h, BoundList& list, const int32_t* off, const In* in, Conv conv,
+                         const int32_t*& d_off, const E*& d_ent, int32_t*& alt_off, E*& alt_ent,
                          const int32_t* extra = nullptr, size_t n_extra = 0, const int32_t** d_extra = nullptr) {
-  if (h->pre_index_stale) {
-    h->pre_index.erase(std::remove_if(h->pre_index.begin(), h->pre_index.end(),
-                                      [&](int32_t i) { return h->pre_dead[i] != 0; }),
-                       h->pre_index.end());
-    h->pre_index_stale = false;
+  if (h->bound.index_stale) {
+    h->bound.index.erase(std::remove_if(h->bound.index.begin(), h->bound.index.end(),
+                                      [&](int32_t i) { return h->bound.dead[i] != 0; }),
+                       h->bound.index.end());
+    h->bound.index_stale = false;
   }
-  const int32_t n = h->pre_live;
+  const int32_t n = h->bound.live;
   std::vector<int32_t> poff((size_t)n + 1, 0);
   std::vector<E> perm;
   if (off) {
-    perm.reserve((size_t)(off[h->pre_n] - off[0]));
+    perm.reserve((size_t)(off[h->bound.n] - off[0]));
     for (int32_t k = 0; k < n; k++) {
-      const int32_t i = h->pre_index[k];
+      const int32_t i = h->bound.index[k];
       for (int32_t e = off[i]; e < off[i + 1]; e++) perm.push_back(conv(in[e]));
       poff[(size_t)k + 1] = (int32_t)perm.size();
     }
   }
   HIPCHK(h, hipSetDevice(h->device));
-  free_bufs(bufs);
+  list = BoundList{};
   d_off = nullptr;
   d_ent = nullptr;
-  ents = 0;
   alt_off = nullptr;
   alt_ent = nullptr;
   if (d_extra) *d_extra = nullptr;
@@ -149,40 +138,40 @@ static int bound_csr_set(ksim_handle* h, std::vector<DevBuf>& bufs, const int32_
   const int32_t *po = nullptr, *px = nullptr;
   const E* pe = nullptr;
   int rc;
-  if ((rc = dev_alloc(h, bufs, po, 4 * poff.size(), poff.data())) ||
-      (rc = dev_alloc(h, bufs, pe, sizeof(E) * perm.size(), perm.data())) ||
-      (d_extra && (rc = dev_alloc(h, bufs, px, 4 * n_extra, extra))))
+  if ((rc = list.bufs.alloc(h, po, 4 * poff.size(), poff.data())) ||
+      (rc = list.bufs.alloc(h, pe, sizeof(E) * perm.size(), perm.data())) ||
+      (d_extra && (rc = list.bufs.alloc(h, px, 4 * n_extra, extra))))
     return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the copies read this call's vectors
   d_off = po;
   d_ent = pe;
-  ents = perm.size();
+  list.ents = perm.size();
   if (d_extra) *d_extra = px;
   return KSIM_OK;
 }
 
 extern "C" int ksim_set_bound_pod_adds(ksim_handle* h, const int32_t* off, const ksim_class_add* adds) {
   if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: ksim_set_bound_pods first");
+  if (!h->bound.d.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: ksim_set_bound_pods first");
   if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_adds", off, adds != nullptr, "adds", false)) return rc;
-  for (int32_t e = off[0]; e < off[h->pre_n]; e++)
+  for (int32_t e = off[0]; e < off[h->bound.n]; e++)
     if (adds[e].cls < 0 || adds[e].cls >= h->dc.n_classes)
       return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_adds: class out of range");
-  return bound_csr_set(h, h->pre_add_bufs, off, adds, [](const ksim_class_add& a) { return a; }, h->pre.aoff,
-                       h->pre.adds, h->pre_add_ents, h->pre_alt.aoff2, h->pre_alt.adds2);
+  return bound_csr_set(h, h->bound.add, off, adds, [](const ksim_class_add& a) { return a; }, h->bound.d.aoff,
+                       h->bound.d.adds, h->bound.alt.aoff2, h->bound.alt.adds2);
 }
 
 extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int32_t* allowed, const int32_t* off,
                                        const int32_t* ids) {
   if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ksim_set_bound_pods first");
+  if (!h->bound.d.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: ksim_set_bound_pods first");
   if (n_pdbs < 0) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: negative budget count");
   if (n_pdbs > 0) {
     // the offsets start at 0 here, and the allowed counts are as much a part of them as the array itself
     if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_pdbs", allowed ? off : nullptr, ids != nullptr, "ids", true))
       return rc;
     std::vector<int32_t> last((size_t)n_pdbs, -1);   // the last row that named the budget
-    for (int32_t i = 0; i < h->pre_n; i++)
+    for (int32_t i = 0; i < h->bound.n; i++)
       for (int32_t e = off[i]; e < off[i + 1]; e++) {
         if (ids[e] < 0 || ids[e] >= n_pdbs)
           return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_pdbs: budget id out of range");
@@ -191,18 +180,18 @@ extern "C" int ksim_set_bound_pod_pdbs(ksim_handle* h, int32_t n_pdbs, const int
       }
   }
   // n_pdbs == 0 clears: the dry run takes the forms without budgets
-  return bound_csr_set(h, h->pre_pdb_bufs, n_pdbs > 0 ? off : nullptr, ids, [](int32_t id) { return id; }, h->pre.poff,
-                       h->pre.pids, h->pre_pdb_ents, h->pre_alt.poff2, h->pre_alt.pids2, allowed, (size_t)n_pdbs,
-                       &h->pre.pallowed);
+  return bound_csr_set(h, h->bound.pdb, n_pdbs > 0 ? off : nullptr, ids, [](int32_t id) { return id; }, h->bound.d.poff,
+                       h->bound.d.pids, h->bound.alt.poff2, h->bound.alt.pids2, allowed, (size_t)n_pdbs,
+                       &h->bound.d.pallowed);
 }
 
 extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, const ksim_topo_use* uses) {
   if (!h) return KSIM_E_INVALID;
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: ksim_set_bound_pods first");
+  if (!h->bound.d.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: ksim_set_bound_pods first");
   if (!h->dc.vol_nf)
     return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: no volume table (ksim_set_volume_limits)");
   if (const int rc = bound_csr_check(h, "ksim_set_bound_pod_volumes", off, uses != nullptr, "uses", false)) return rc;
-  for (int32_t e = off[0]; e < off[h->pre_n]; e++) {
+  for (int32_t e = off[0]; e < off[h->bound.n]; e++) {
     const ksim_topo_use& u = uses[e];
     if (u.kind != KSIM_USE_VOLUME)
       return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: a use that is no KSIM_USE_VOLUME");
@@ -212,9 +201,9 @@ extern "C" int ksim_set_bound_pod_volumes(ksim_handle* h, const int32_t* off, co
     if (u.cls < 0 ? u.arg < 1 : u.arg != 1)
       return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pod_volumes: bad volume use count");
   }
-  return bound_csr_set(h, h->pre_vol_bufs, off, uses,
-                       [](const ksim_topo_use& u) { return VolHold{u.cls, (int32_t)u.col, u.arg}; }, h->pre_voff,
-                       h->pre_vols, h->pre_vol_ents, h->pre_alt.voff2, h->pre_alt.vols2);
+  return bound_csr_set(h, h->bound.vol, off, uses,
+                       [](const ksim_topo_use& u) { return VolHold{u.cls, (int32_t)u.col, u.arg}; }, h->bound.voff,
+                       h->bound.vols, h->bound.alt.voff2, h->bound.alt.vols2);
 }
 
 extern "C" int ksim_preempt(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index, int32_t priority,
@@ -253,7 +242,7 @@ static int preempt_check_args(ksim_handle* h, const ksim_pod_set* ps, int32_t po
     for (int32_t j = ng.first[k]; j < ng.first[k] + ng.count[k]; j++)
       if ((rc = validate_pod(h, ng.ps, j))) return rc;
   }
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pods first");
+  if (!h->bound.d.off) return set_err(h, KSIM_E_INVALID, "ksim_set_bound_pods first");
   if (is_sharded(h)) return set_err(h, KSIM_E_UNSUPPORTED, "preemption runs on unsharded handles");
   if (prof_has_filter(h->prof, KSIM_PL_NETWORK_BANDWIDTH))
     return set_err(h, KSIM_E_UNSUPPORTED, "preemption dry runs re-run Fit only, not NetworkBandwidth");
@@ -271,7 +260,7 @@ static int preempt_plan(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_inde
                         PreemptEntry entry, PreemptPlan& q) {
   q = PreemptPlan{};
   q.fit = q.port = q.ipa = q.pts = -1;
-  q.prio = priority, q.smin = h->pre_smin;
+  q.prio = priority, q.smin = h->bound.smin;
   for (int f = 0; f < h->prof.n_filter; f++) {
     if (h->prof.filter[f] == KSIM_PL_NODE_RESOURCES_FIT) q.fit = f;
     if (h->prof.filter[f] == KSIM_PL_NODE_PORTS) q.port = f;
@@ -301,21 +290,21 @@ static int preempt_plan(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_inde
     if (kind == KSIM_USE_PTS_HARD && q.pts >= 0) q.hard |= 1u << k;
   }
   const bool dom = q.reads_domains();
-  if (q.hard && !h->pre.aoff)
+  if (q.hard && !h->bound.d.aoff)
     return set_err(h, KSIM_E_INVALID, "ksim_preempt_spread for a pod with DoNotSchedule spread: "
                                       "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
-  if (q.ports && !dom && !h->pre.aoff)
+  if (q.ports && !dom && !h->bound.d.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with host ports: ksim_set_bound_pod_adds first "
                                       "(after ksim_set_bound_pods)");
-  if (vol_form && !h->pre_voff)
+  if (vol_form && !h->bound.voff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with a KSIM_USE_VOLUME use: ksim_set_bound_pod_volumes "
                                       "first (after ksim_set_bound_pods)");
   // what the profile's limit plugins read of the pod (validate_pod checked the families)
   PreemptVol& vm = q.vol;
   vm.at = 0xffffffffu;
   if (vol_form) {
-    vm.voff = h->pre_voff;
-    vm.vols = h->pre_vols;
+    vm.voff = h->bound.voff;
+    vm.vols = h->bound.vols;
     for (int f = 0; f < h->prof.n_filter; f++) {
       const int32_t k = h->prof.filter[f] - KSIM_PL_EBS_LIMITS;
       if (k >= 0 && k < 4) vm.at = (vm.at & ~(255u << (8 * k))) | ((uint32_t)f << (8 * k));
@@ -330,7 +319,7 @@ static int preempt_plan(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_inde
       if (pl == (uint32_t)(KSIM_PL_NODE_VOLUME_LIMITS - KSIM_PL_EBS_LIMITS)) vm.csi |= 1u << u.col;
     }
   }
-  if (dom && !h->pre.aoff)
+  if (dom && !h->bound.d.aoff)
     return set_err(h, KSIM_E_INVALID, "preemption for a pod with required pod (anti-)affinity: "
                                       "ksim_set_bound_pod_adds first (after ksim_set_bound_pods), every class");
   // the static volume filters of a preemptor with groups
@@ -404,16 +393,16 @@ static int preempt_statuses(ksim_handle* h, const LaunchArgs& a, const Nominated
     gvoff[(size_t)k + 1] = (int32_t)gvols.size();
   }
   if (n_groups > 0) {
-    free_bufs(h->pre_nom_bufs);
-    if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.nreq, 8 * nreq.size(), nreq.data()))) return rc;
+    h->bound.nom_bufs.clear();
+    if ((rc = h->bound.nom_bufs.alloc(h, pre.nreq, 8 * nreq.size(), nreq.data()))) return rc;
     if (adds_form) {                                       // the groups' holdings stay on their nodes too
-      if ((rc = dev_alloc(h, h->pre_nom_bufs, pre.goff, 4 * goff.size(), goff.data())) ||
-          (rc = dev_alloc(h, h->pre_nom_bufs, pre.gadds, sizeof(ksim_class_add) * gadds.size(), gadds.data())))
+      if ((rc = h->bound.nom_bufs.alloc(h, pre.goff, 4 * goff.size(), goff.data())) ||
+          (rc = h->bound.nom_bufs.alloc(h, pre.gadds, sizeof(ksim_class_add) * gadds.size(), gadds.data())))
         return rc;
     }
     if (vol_form) {
-      if ((rc = dev_alloc(h, h->pre_nom_bufs, plan.vol.gvoff, 4 * gvoff.size(), gvoff.data())) ||
-          (rc = dev_alloc(h, h->pre_nom_bufs, plan.vol.gvols, sizeof(VolHold) * gvols.size(), gvols.data())))
+      if ((rc = h->bound.nom_bufs.alloc(h, plan.vol.gvoff, 4 * gvoff.size(), gvoff.data())) ||
+          (rc = h->bound.nom_bufs.alloc(h, plan.vol.gvols, sizeof(VolHold) * gvols.size(), gvols.data())))
         return rc;
     }
   }
@@ -434,7 +423,7 @@ static int preempt_statuses(ksim_handle* h, const LaunchArgs& a, const Nominated
 // victims violating a PDB, then the others, each in CSR order.
 static int preempt_read_back(ksim_handle* h, ksim_preempt_out* out) {
   int32_t pick[5];
-  HIPCHK(h, hipMemcpyAsync(pick, h->pre.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(pick, h->bound.d.pick, sizeof(pick), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   out->nominated = pick[0];
   out->n_victims = pick[1];
@@ -443,17 +432,17 @@ static int preempt_read_back(ksim_handle* h, ksim_preempt_out* out) {
   out->n_pdb_violations = pick[4];
   if (pick[0] >= 0 && out->victims && out->victims_cap > 0) {
     std::vector<int32_t> off(2);
-    HIPCHK(h, hcopy(h, off.data(), h->pre.off + pick[0], 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hcopy(h, off.data(), h->bound.d.off + pick[0], 8, hipMemcpyDeviceToHost));
     std::vector<uint8_t> flag((size_t)std::max(off[1] - off[0], 1));
     if (off[1] > off[0])
-      HIPCHK(h, hcopy(h, flag.data(), h->pre.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
+      HIPCHK(h, hcopy(h, flag.data(), h->bound.d.vflag + off[0], (size_t)(off[1] - off[0]), hipMemcpyDeviceToHost));
     // the positions' caller rows: the host's copy, or after a ksim_preempt_commit (which leaves
     // that one uncompacted) the node's range of the device's
     std::vector<int32_t> moved;
-    const int32_t* index = h->pre_index.data() + off[0];
-    if (h->pre_index_stale && off[1] > off[0]) {
+    const int32_t* index = h->bound.index.data() + off[0];
+    if (h->bound.index_stale && off[1] > off[0]) {
       moved.resize((size_t)(off[1] - off[0]));
-      HIPCHK(h, hcopy(h, moved.data(), h->pre_dindex + off[0], 4 * moved.size(), hipMemcpyDeviceToHost));
+      HIPCHK(h, hcopy(h, moved.data(), h->bound.dindex + off[0], 4 * moved.size(), hipMemcpyDeviceToHost));
       index = moved.data();
     }
     int32_t k = 0;
@@ -478,7 +467,7 @@ static int preempt_run(ksim_handle* h, const ksim_pod_set* ps, int32_t pod_index
   if ((rc = upload_single(h, ps, pod_index, P))) return rc;
   if ((rc = set_run(h, 0, 1))) return rc;
   const LaunchArgs a = make_args(h, P, nullptr);
-  DevPreempt pre = h->pre;
+  DevPreempt pre = h->bound.d;
   if ((rc = preempt_statuses(h, a, ng, ps->pods[pod_index].use_count > 0, plan, pre))) return rc;
   launch_preempt(a, pre, plan, h->stream);
   HIPCHK(h, hipGetLastError());
@@ -525,21 +514,21 @@ extern "C" int32_t ksim_preempt_many_dom_rows(int32_t n_nodes, int32_t n_bound, 
 // and for `dom_rows` of them the PreFilter states of domain rows.
 static int many_slabs(ksim_handle* h, int32_t rows, int32_t dom_rows) {
   int rc;
-  if (rows > h->many_slab_rows) {              // (every call ends synchronized: nothing reads them)
-    free_bufs(h->many_bufs);
-    h->many_slab_rows = 0;
-    if ((rc = dev_alloc(h, h->many_bufs, h->many_res, sizeof(PreemptNode) * (size_t)rows * std::max(h->dc.n, 1))) ||
-        (rc = dev_alloc(h, h->many_bufs, h->many_vflag, (size_t)rows * std::max(h->pre_n, 1))))
+  if (rows > h->bound.many.rows) {              // (every call ends synchronized: nothing reads them)
+    h->bound.many.bufs.clear();
+    h->bound.many.rows = 0;
+    if ((rc = h->bound.many.bufs.alloc(h, h->bound.many.res, sizeof(PreemptNode) * (size_t)rows * std::max(h->dc.n, 1))) ||
+        (rc = h->bound.many.bufs.alloc(h, h->bound.many.vflag, (size_t)rows * std::max(h->bound.n, 1))))
       return rc;
-    h->many_slab_rows = rows;
+    h->bound.many.rows = rows;
   }
-  if (dom_rows > h->many_dom_rows) {
-    free_bufs(h->many_dom_bufs);
-    h->many_dom_rows = 0;
-    if ((rc = dev_alloc(h, h->many_dom_bufs, h->many_dom, 8 * (size_t)dom_rows * KSIM_MAX_USES * h->dc.vmax)) ||
-        (rc = dev_alloc(h, h->many_dom_bufs, h->many_heads, sizeof(PreemptDomHead) * (size_t)dom_rows)))
+  if (dom_rows > h->bound.many.dom_rows) {
+    h->bound.many.dom_bufs.clear();
+    h->bound.many.dom_rows = 0;
+    if ((rc = h->bound.many.dom_bufs.alloc(h, h->bound.many.dom, 8 * (size_t)dom_rows * KSIM_MAX_USES * h->dc.vmax)) ||
+        (rc = h->bound.many.dom_bufs.alloc(h, h->bound.many.heads, sizeof(PreemptDomHead) * (size_t)dom_rows)))
       return rc;
-    h->many_dom_rows = dom_rows;
+    h->bound.many.dom_rows = dom_rows;
   }
   return KSIM_OK;
 }
@@ -595,7 +584,7 @@ static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, c
     const size_t row_bytes = (sizeof(PreemptRow) * (size_t)nb + 63) / 64 * 64;   // then the domain rows' records
     if ((rc = upload_many(h, ps, bidx.data(), nb, row_bytes + sizeof(PreemptDomRow) * (size_t)nb, Ps, &thost, &tdev)))
       return rc;
-    const int32_t R = preempt_many_rows(N, h->pre_n), RD = preempt_many_dom_rows(N, h->pre_n, h->dc.vmax);
+    const int32_t R = preempt_many_rows(N, h->bound.n), RD = preempt_many_dom_rows(N, h->bound.n, h->dc.vmax);
     // a group ends with its form or at its form's row count
     std::vector<int32_t> gfirst((size_t)nb);    // table position -> its group's first position
     int32_t most = 0, most_dom = 0, n_dom = 0;
@@ -611,12 +600,12 @@ static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, c
     std::vector<int32_t> vat((size_t)nb + 1, 0), dcap((size_t)nb);
     for (int32_t k = 0; k < nb; k++) {
       const ksim_preempt_out& o = outs[brow[k]];
-      dcap[k] = o.victims && o.victims_cap > 0 ? std::min(o.victims_cap, h->pre_maxrow) : 0;
+      dcap[k] = o.victims && o.victims_cap > 0 ? std::min(o.victims_cap, h->bound.maxrow) : 0;
       vat[(size_t)k + 1] = vat[k] + dcap[k];
     }
     const size_t words = (size_t)kPickWords * nb + (size_t)vat[nb];
-    if (4 * words > h->many_out.cap || 4 * words > h->many_host.cap) HIPCHK(h, hipStreamSynchronize(h->stream));
-    if ((rc = arena_reserve(h, h->many_out, 4 * words)) || (rc = pinbuf_reserve(h, h->many_host, 4 * words))) return rc;
+    if ((rc = h->many_out.reserve(h, 4 * words, Idle::kSync)) || (rc = h->many_host.reserve(h, 4 * words, Idle::kSync)))
+      return rc;
     int32_t* dout = (int32_t*)h->many_out.p;
     const size_t dom_words = (size_t)KSIM_MAX_USES * h->dc.vmax;   // of one row's tables
     std::vector<PreemptRow> table((size_t)nb);
@@ -627,8 +616,8 @@ static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, c
       PreemptRow& r = table[k];
       r.P = Ps[k];
       r.vm = q.vol;
-      r.res = h->many_res + (size_t)at * N;
-      r.vflag = h->many_vflag + (size_t)at * std::max(h->pre_n, 1);
+      r.res = h->bound.many.res + (size_t)at * N;
+      r.vflag = h->bound.many.vflag + (size_t)at * std::max(h->bound.n, 1);
       r.victims = dout + (size_t)kPickWords * nb + vat[k];
       r.cap = dcap[k];
       r.prio = q.prio;
@@ -637,8 +626,8 @@ static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, c
       PreemptDomRow& d = dtable[k];
       d = PreemptDomRow{};
       if (bform[k] >= 2) {
-        d.dom = h->many_dom + (size_t)at * dom_words;
-        d.head = h->many_heads + at;
+        d.dom = h->bound.many.dom + (size_t)at * dom_words;
+        d.head = h->bound.many.heads + at;
         d.aff = q.aff, d.anti = q.anti, d.exist = q.exist, d.hard = q.hard;
       }
     }
@@ -646,15 +635,15 @@ static int preempt_many_run(ksim_handle* h, const ksim_pod_set* ps, int32_t n, c
     std::memcpy(thost + row_bytes, dtable.data(), sizeof(PreemptDomRow) * (size_t)nb);
     if ((rc = upload_many_commit(h))) return rc;
     const LaunchArgs a = make_args(h, DevPods{}, nullptr);
-    DevPreempt pre = h->pre;
+    DevPreempt pre = h->bound.d;
     pre.res = nullptr, pre.vflag = nullptr, pre.pick = nullptr, pre.nslot = nullptr;   // per row; no groups
     pre.afftot = nullptr;                      // (a domain row's is in its head)
     for (int32_t g0 = 0; g0 < nb;) {           // no host synchronization between the groups
       int32_t g1 = g0 + 1;
       while (g1 < nb && gfirst[g1] == g0) g1++;
       const int form = bform[g0];
-      const PreemptMany g{(const PreemptRow*)tdev + g0, g1 - g0, form == 1, h->many_res, dout + (size_t)kPickWords * g0,
-                          h->pre_dindex, h->bp.rank_lo, h->bp.rank_hi};
+      const PreemptMany g{(const PreemptRow*)tdev + g0, g1 - g0, form == 1, h->bound.many.res, dout + (size_t)kPickWords * g0,
+                          h->bound.dindex, h->bp.rank_lo, h->bp.rank_hi};
       if (form >= 2) {
         bool spread = false;
         for (int32_t k = g0; k < g1; k++) spread |= plans[brow[k]].hard != 0;
@@ -709,26 +698,26 @@ extern "C" int ksim_preempt_many_dom(ksim_handle* h, const ksim_pod_set* ps, int
 // and kept until the table or the list goes.
 static int commit_buffers(ksim_handle* h) {
   int rc;
-  DevCommit& a = h->pre_alt;
-  const size_t n = (size_t)std::max(h->pre_n, 1), N = (size_t)h->dc.n;
+  DevCommit& a = h->bound.alt;
+  const size_t n = (size_t)std::max(h->bound.n, 1), N = (size_t)h->dc.n;
   if (!a.pos &&
-      ((rc = dev_alloc(h, h->pre_bufs, a.off2, 4 * (N + 1))) || (rc = dev_alloc(h, h->pre_bufs, a.prio2, 4 * n)) ||
-       (rc = dev_alloc(h, h->pre_bufs, a.index2, 4 * n)) || (rc = dev_alloc(h, h->pre_bufs, a.start2, 8 * n)) ||
-       (rc = dev_alloc(h, h->pre_bufs, a.req2, 8 * n * KSIM_PREEMPT_REQ)) ||
-       (rc = dev_alloc(h, h->pre_bufs, a.dead, n + 1)) || (rc = dev_alloc(h, h->pre_bufs, a.before, 4 * (n + 1))) ||
-       (rc = dev_alloc(h, h->pre_bufs, a.tile, sizeof(CommitSum) * (size_t)commit_tiles(h->pre_n))) ||
-       (rc = dev_alloc(h, h->pre_bufs, a.pos, 4 * n))))   // pos last: set once the rest is there
+      ((rc = h->bound.bufs.alloc(h, a.off2, 4 * (N + 1))) || (rc = h->bound.bufs.alloc(h, a.prio2, 4 * n)) ||
+       (rc = h->bound.bufs.alloc(h, a.index2, 4 * n)) || (rc = h->bound.bufs.alloc(h, a.start2, 8 * n)) ||
+       (rc = h->bound.bufs.alloc(h, a.req2, 8 * n * KSIM_PREEMPT_REQ)) ||
+       (rc = h->bound.bufs.alloc(h, a.dead, n + 1)) || (rc = h->bound.bufs.alloc(h, a.before, 4 * (n + 1))) ||
+       (rc = h->bound.bufs.alloc(h, a.tile, sizeof(CommitSum) * (size_t)commit_tiles(h->bound.n))) ||
+       (rc = h->bound.bufs.alloc(h, a.pos, 4 * n))))   // pos last: set once the rest is there
     return rc;
-  const size_t offs = 4 * ((size_t)h->pre_live + 1);
-  if (h->pre.aoff && !a.aoff2 &&
-      ((rc = dev_alloc(h, h->pre_add_bufs, a.adds2, sizeof(ksim_class_add) * h->pre_add_ents)) ||
-       (rc = dev_alloc(h, h->pre_add_bufs, a.aoff2, offs))))
+  const size_t offs = 4 * ((size_t)h->bound.live + 1);
+  if (h->bound.d.aoff && !a.aoff2 &&
+      ((rc = h->bound.add.bufs.alloc(h, a.adds2, sizeof(ksim_class_add) * h->bound.add.ents)) ||
+       (rc = h->bound.add.bufs.alloc(h, a.aoff2, offs))))
     return rc;
-  if (h->pre.poff && !a.poff2 && ((rc = dev_alloc(h, h->pre_pdb_bufs, a.pids2, 4 * h->pre_pdb_ents)) ||
-                                  (rc = dev_alloc(h, h->pre_pdb_bufs, a.poff2, offs))))
+  if (h->bound.d.poff && !a.poff2 && ((rc = h->bound.pdb.bufs.alloc(h, a.pids2, 4 * h->bound.pdb.ents)) ||
+                                  (rc = h->bound.pdb.bufs.alloc(h, a.poff2, offs))))
     return rc;
-  if (h->pre_voff && !a.voff2 && ((rc = dev_alloc(h, h->pre_vol_bufs, a.vols2, sizeof(VolHold) * h->pre_vol_ents)) ||
-                                  (rc = dev_alloc(h, h->pre_vol_bufs, a.voff2, offs))))
+  if (h->bound.voff && !a.voff2 && ((rc = h->bound.vol.bufs.alloc(h, a.vols2, sizeof(VolHold) * h->bound.vol.ents)) ||
+                                  (rc = h->bound.vol.bufs.alloc(h, a.voff2, offs))))
     return rc;
   return KSIM_OK;
 }
@@ -749,7 +738,7 @@ extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32
   if (rc) return rc;
   if (is_sharded(h) || h->replicated)
     return set_err(h, KSIM_E_UNSUPPORTED, "ksim_preempt_commit: preemption runs on unsharded handles");
-  if (!h->pre.off) return set_err(h, KSIM_E_INVALID, "ksim_preempt_commit: ksim_set_bound_pods first");
+  if (!h->bound.d.off) return set_err(h, KSIM_E_INVALID, "ksim_preempt_commit: ksim_set_bound_pods first");
   // pre_dead[row] = 2 while this call names the row; the guard takes the marks back unless the call ran
   int32_t marked = 0;
   bool ran = false;
@@ -759,26 +748,26 @@ extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32
     const int32_t& marked;
     const bool& ran;
     ~Marks() {
-      for (int32_t i = 0; i < marked; i++) h->pre_dead[rows[i]] = ran ? 1 : 0;
+      for (int32_t i = 0; i < marked; i++) h->bound.dead[rows[i]] = ran ? 1 : 0;
     }
   } marks{h, rows, marked, ran};
   for (int32_t i = 0; i < n; i++) {
     const std::string at = "ksim_preempt_commit entry " + std::to_string(i) + ": ";
     const int32_t r = rows[i], j = pod_index[i];
-    if (r < 0 || r >= h->pre_n) return set_err(h, KSIM_E_INVALID, at + "row outside the bound-pod table");
-    if (h->pre_dead[r] == 1) return set_err(h, KSIM_E_INVALID, at + "row already evicted");
-    if (h->pre_dead[r] == 2) return set_err(h, KSIM_E_INVALID, at + "row named twice");
+    if (r < 0 || r >= h->bound.n) return set_err(h, KSIM_E_INVALID, at + "row outside the bound-pod table");
+    if (h->bound.dead[r] == 1) return set_err(h, KSIM_E_INVALID, at + "row already evicted");
+    if (h->bound.dead[r] == 2) return set_err(h, KSIM_E_INVALID, at + "row named twice");
     if (j < 0 || j >= ps->n_pods) return set_err(h, KSIM_E_INVALID, at + "pod index outside the pod set");
     if ((rc = validate_pod(h, ps, j))) {
       h->err = at + h->err;
       return rc;
     }
     const ksim_pod& p = ps->pods[j];
-    const int64_t* q = h->pre_row_req.data() + (size_t)r * KSIM_PREEMPT_REQ;
+    const int64_t* q = h->bound.row_req.data() + (size_t)r * KSIM_PREEMPT_REQ;
     bool same = p.req_cpu == q[0] && p.req_mem == q[1] && p.req_eph == q[2];
     for (int c = 0; c < KSIM_MAX_SCALAR; c++) same = same && p.scalar_req[c] == q[3 + c];
     if (!same) return set_err(h, KSIM_E_INVALID, at + "the pod's requests differ from the row's");
-    h->pre_dead[r] = 2;
+    h->bound.dead[r] = 2;
     marked = i + 1;
   }
   HIPCHK(h, hipSetDevice(h->device));
@@ -787,17 +776,17 @@ extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32
   char *thost = nullptr, *tdev = nullptr;
   if ((rc = upload_many(h, ps, pod_index, n, sizeof(CommitRec) * (size_t)n, Ps, &thost, &tdev))) return rc;
   CommitRec* recs = (CommitRec*)thost;
-  for (int32_t i = 0; i < n; i++) recs[i] = CommitRec{Ps[i], rows[i], h->pre_row_node[rows[i]]};
+  for (int32_t i = 0; i < n; i++) recs[i] = CommitRec{Ps[i], rows[i], h->bound.row_node[rows[i]]};
   if ((rc = upload_many_commit(h))) return rc;
-  DevPreempt& t = h->pre;
-  DevCommit& a = h->pre_alt;
+  DevPreempt& t = h->bound.d;
+  DevCommit& a = h->bound.alt;
   DevCommit m = a;                               // the second set and the scratch; then the table as it is
-  m.n = h->pre_live;
+  m.n = h->bound.live;
   m.n_nodes = h->dc.n;
-  m.off = t.off, m.prio = t.prio, m.index = h->pre_dindex, m.start = t.start, m.req = t.req;
+  m.off = t.off, m.prio = t.prio, m.index = h->bound.dindex, m.start = t.start, m.req = t.req;
   m.aoff = t.aoff, m.adds = t.adds;
   m.poff = t.poff, m.pids = t.pids;
-  m.voff = h->pre_voff, m.vols = h->pre_vols;
+  m.voff = h->bound.voff, m.vols = h->bound.vols;
   launch_preempt_commit(h->dc, m, (const CommitRec*)tdev, n, h->stream);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));    // the staging is the next call's to write
@@ -805,7 +794,7 @@ extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32
   a.off2 = const_cast<int32_t*>(m.off), a.prio2 = const_cast<int32_t*>(m.prio);
   a.index2 = const_cast<int32_t*>(m.index), a.start2 = const_cast<int64_t*>(m.start);
   a.req2 = const_cast<int64_t*>(m.req);
-  t.off = m.off2, t.prio = m.prio2, h->pre_dindex = m.index2, t.start = m.start2, t.req = m.req2;
+  t.off = m.off2, t.prio = m.prio2, h->bound.dindex = m.index2, t.start = m.start2, t.req = m.req2;
   if (m.aoff) {
     a.aoff2 = const_cast<int32_t*>(m.aoff), a.adds2 = const_cast<ksim_class_add*>(m.adds);
     t.aoff = m.aoff2, t.adds = m.adds2;
@@ -816,10 +805,10 @@ extern "C" int ksim_preempt_commit(ksim_handle* h, const ksim_pod_set* ps, int32
   }
   if (m.voff) {
     a.voff2 = const_cast<int32_t*>(m.voff), a.vols2 = const_cast<VolHold*>(m.vols);
-    h->pre_voff = m.voff2, h->pre_vols = m.vols2;
+    h->bound.voff = m.voff2, h->bound.vols = m.vols2;
   }
-  h->pre_live -= n;
-  h->pre_index_stale = true;
+  h->bound.live -= n;
+  h->bound.index_stale = true;
   ran = true;
   return KSIM_OK;
 }
@@ -878,29 +867,25 @@ extern "C" int ksim_match_terms(ksim_handle* h, const ksim_match_problem* mp, ui
   m.cw = (q.n_classes + 31) / 32;
   m.p = q.n_classes > 0 ? q.n_pods : 0;
   m.n = q.n_nodes;
-  std::vector<DevBuf> bufs;
-  struct Guard {
-    std::vector<DevBuf>& b;
-    ~Guard() { free_bufs(b); }
-  } guard{bufs};
+  DevPool bufs;                                // this call's: freed on every way out
   int rc;
   std::vector<uint8_t> neg((size_t)m.rp, 0);
   std::copy(q.req_neg, q.req_neg + q.n_reqs, neg.begin());
-  if ((rc = dev_alloc(h, bufs, m.a, (size_t)m.sp * m.fp)) || (rc = dev_alloc(h, bufs, m.bt, (size_t)m.rp * m.fp)) ||
-      (rc = dev_alloc(h, bufs, m.neg, neg.size(), neg.data())))
+  if ((rc = bufs.alloc(h, m.a, (size_t)m.sp * m.fp)) || (rc = bufs.alloc(h, m.bt, (size_t)m.rp * m.fp)) ||
+      (rc = bufs.alloc(h, m.neg, neg.size(), neg.data())))
     return rc;
   auto put = [&](const int32_t* src, int64_t n, const int32_t*& dst) {
-    return dev_alloc(h, bufs, dst, (size_t)std::max<int64_t>(n, 0) * 4, src);
+    return bufs.alloc(h, dst, (size_t)std::max<int64_t>(n, 0) * 4, src);
   };
   if ((rc = put(q.sig_feat_off, q.n_sigs + 1, m.sig_off)) || (rc = put(q.sig_feat, q.sig_feat_off[q.n_sigs], m.sig_feat)) ||
       (rc = put(q.req_feat_off, q.n_reqs + 1, m.req_off)) || (rc = put(q.req_feat, q.req_feat_off[q.n_reqs], m.req_feat)) ||
       (rc = put(q.m_req_off, q.n_matchers + 1, m.m_off)) || (rc = put(q.m_req, q.m_req_off[q.n_matchers], m.m_req)))
     return rc;
-  if ((rc = dev_alloc(h, bufs, m.bits, (size_t)m.s * std::max(m.w, 1) * 4))) return rc;
+  if ((rc = bufs.alloc(h, m.bits, (size_t)m.s * std::max(m.w, 1) * 4))) return rc;
   if (m.c > 0) {
     if ((rc = put(q.class_matcher, m.c, m.cls_matcher)) || (rc = put(q.pod_sig, m.p, m.pod_sig)) ||
-        (rc = put(q.pod_node, m.p, m.pod_node)) || (rc = dev_alloc(h, bufs, m.cls_bits, (size_t)m.s * m.cw * 4)) ||
-        (rc = dev_alloc(h, bufs, m.cnt, (size_t)m.c * std::max(m.n, 1) * 4)))
+        (rc = put(q.pod_node, m.p, m.pod_node)) || (rc = bufs.alloc(h, m.cls_bits, (size_t)m.s * m.cw * 4)) ||
+        (rc = bufs.alloc(h, m.cnt, (size_t)m.c * std::max(m.n, 1) * 4)))
       return rc;
   }
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));

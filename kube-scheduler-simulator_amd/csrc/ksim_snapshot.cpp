@@ -3,7 +3,8 @@
 // ksim_update_node_rows, ksim_remove_node), ksim_reset_cluster, the volume
 // limit table and the state getters and setters.  The dynamic columns, the
 // cluster facts and the teardowns are each said once here (for_dyn_cols,
-// cluster_facts) or in ksim_engine.cpp (drop_loaded_pods, drop_bound_pods).
+// cluster_facts), in ksim_engine.cpp (drop_loaded_pods) or are an assignment
+// of a fresh value to a struct of the handle (ksim_host.h BoundPods, LazyBufs).
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -147,20 +148,17 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   // range (a replica calls ksim_set_eval_range again)
   h->replicated = false;
   drop_graphs(h);
-  free_bufs(h->cluster_bufs);
-  free_bufs(h->vol_bufs);               // the volume table belongs to the old snapshot (DevCluster c{} below)
+  h->cluster_bufs.clear();
+  h->vol_bufs.clear();               // the volume table belongs to the old snapshot (DevCluster c{} below)
   h->vol_init = nullptr;
-  free_bufs(h->scratch_bufs);
-  free_bufs(h->ash_bufs);
-  free_bufs(h->lazy_bufs);
-  h->lazy_n = -1;
-  h->ash_send = h->ash_recv = h->ash_gmask = nullptr;
-  h->ash_world = h->ash_w = 0;
-  drop_loaded_pods(h);
+  h->scratch_bufs.clear();
+  h->ash = AshBufs{};
+  h->lazy = LazyBufs{};
+  drop_loaded_pods(h);                  // d_chosen with it
   h->has_cluster = false;
   // node positions of the old snapshot: the bound-pod table and a pending
   // extender round trip do not carry over
-  drop_bound_pods(h);
+  h->bound = BoundPods{};
   h->ext_pending = false;
   h->fw_pending = h->fw_scored = h->fw_dom_dirty = false;   // fresh scratch below
   h->deferred_binds.clear();           // Reserve / Unreserve queued against the old node positions
@@ -182,7 +180,7 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   c.n_label_values = v->n_label_values;
   const size_t N = (size_t)n;
   int rc;
-  auto up = [&](auto*& dst, const void* src, size_t bytes) { return dev_alloc(h, h->cluster_bufs, dst, bytes, src); };
+  auto up = [&](auto*& dst, const void* src, size_t bytes) { return h->cluster_bufs.alloc(h, dst, bytes, src); };
   // label columns whose every value sits on at most one node (hostname):
   // InterPodAffinity reads the node's own count there (kUseUniqueCol)
   std::vector<uint8_t> uniq;
@@ -228,7 +226,7 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   // the dynamic columns as uploaded: what ksim_reset_cluster restores
   rc = for_dyn_cols(h, nullptr, [&](auto col) -> int {
     const size_t bytes = sizeof(*col.live) * N * (size_t)col.rows;
-    if (const int r = dev_alloc(h, h->cluster_bufs, col.snap, bytes)) return r;
+    if (const int r = h->cluster_bufs.alloc(h, col.snap, bytes)) return r;
     HIPCHK(h, hipMemcpyAsync(col.snap, col.live, bytes, hipMemcpyDeviceToDevice, h->stream));
     return KSIM_OK;
   });
@@ -236,7 +234,7 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
 
   DevScratch s{};
   DevEvalOut o{};
-  auto scr = [&](auto*& dst, size_t bytes) { return dev_alloc(h, h->scratch_bufs, dst, bytes); };
+  auto scr = [&](auto*& dst, size_t bytes) { return h->scratch_bufs.alloc(h, dst, bytes); };
   const size_t NT = N <= (size_t)kTbMaxBlocks * 256 ? N : 0;   // topology batches (tbatch_admit)
   const size_t NW = (N + 63) / 64 <= 128 ? N : 0;   // the doubling window's tables (clusters of <= 128 bitmap words)
   if ((rc = scr(s.fail, N)) ||
@@ -305,8 +303,6 @@ int ksim_set_cluster(ksim_handle* h, const ksim_node_table* t, const ksim_vocab*
   HIPCHK(h, hipMemcpyAsync(h->st, &zero, sizeof(zero), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->has_cluster = true;
-  if (h->d_chosen) (void)hipFree(h->d_chosen);
-  h->d_chosen = nullptr;
   return KSIM_OK;
 }
 
@@ -434,8 +430,8 @@ int ksim_update_node_rows(ksim_handle* h, const ksim_node_table* t, const ksim_v
   HIPCHK(h, hipStreamSynchronize(h->stream));     // the pinned staging is free
   const int32_t words = 1 + 8 + KSIM_MAX_NODE_TAINTS + c.n_scalar + c.n_label_cols;
   int rc;
-  if ((rc = pin_reserve(h, 8 * (size_t)words * (size_t)std::max(n_rows, 1)))) return rc;
-  int64_t* rec = (int64_t*)h->pin;
+  if ((rc = h->pin.reserve(h, 8 * (size_t)words * (size_t)std::max(n_rows, 1), Idle::kCaller))) return rc;   // idle: drained above
+  int64_t* rec = (int64_t*)h->pin.p;
   for (int32_t q = 0; q < n_rows; q++) {
     const int32_t r = rows[q];
     int64_t* w = rec + (size_t)q * words;
@@ -455,7 +451,7 @@ int ksim_update_node_rows(ksim_handle* h, const ksim_node_table* t, const ksim_v
     for (int k = 0; k < c.n_label_cols; k++)
       w[9 + KSIM_MAX_NODE_TAINTS + c.n_scalar + k] = t->labels[(size_t)k * N + r];
   }
-  launch_node_rows(c, (const int64_t*)h->pin_d, n_rows, words, h->stream);
+  launch_node_rows(c, (const int64_t*)h->pin.d, n_rows, words, h->stream);
   HIPCHK(h, hipGetLastError());
   // the cluster facts, from the whole table
   std::vector<uint8_t> uniq;
@@ -614,12 +610,12 @@ int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* fa
   drop_graphs(h);
   h->dp = DevPods{};
   h->batchable.clear();
-  free_bufs(h->vol_bufs);
-  free_bufs(h->pre_vol_bufs);           // the bound pods' holdings named the old table's families
-  h->pre_voff = nullptr;
-  h->pre_vols = nullptr;
-  h->pre_alt.voff2 = nullptr;           // (ksim_preempt_commit's second set of them went with the buffers)
-  h->pre_alt.vols2 = nullptr;
+  h->vol_bufs.clear();
+  h->bound.vol = BoundList{};           // the bound pods' holdings named the old table's families
+  h->bound.voff = nullptr;
+  h->bound.vols = nullptr;
+  h->bound.alt.voff2 = nullptr;           // (ksim_preempt_commit's second set of them went with the buffers)
+  h->bound.alt.vols2 = nullptr;
   h->vol_init = nullptr;
   h->dc.vol_nf = 0;
   h->dc.vol_plug = 0;
@@ -630,9 +626,9 @@ int ksim_set_volume_limits(ksim_handle* h, int32_t n_families, const int32_t* fa
   const int32_t* dl = nullptr;
   int32_t *da = nullptr, *di = nullptr;
   int rc;
-  if ((rc = dev_alloc(h, h->vol_bufs, dl, bytes, limit)) || (rc = dev_alloc(h, h->vol_bufs, da, bytes, attached)) ||
-      (rc = dev_alloc(h, h->vol_bufs, di, bytes, attached))) {
-    free_bufs(h->vol_bufs);
+  if ((rc = h->vol_bufs.alloc(h, dl, bytes, limit)) || (rc = h->vol_bufs.alloc(h, da, bytes, attached)) ||
+      (rc = h->vol_bufs.alloc(h, di, bytes, attached))) {
+    h->vol_bufs.clear();
     return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
